@@ -2,6 +2,7 @@
 
     python bench.py --gpus N --steps K --warmup W        (N>1: one rank per GPU over RCCL -- either started by torch.distributed.run, or, when
                                                           no rank environment is set, bench.py starts the N ranks itself as child processes)
+    [--dump-outputs DIR]                                 (the edited images of the last timed step as .npy files, to compare two builds)
 
 One "step" = one pass of the hot path over one batch of synthetic inputs = `--concurrent` x `--batch` full `FreeFine_generation`
 edits at 512x512 on SD-2.1-base topology (865.9 M parameter UNet + SD VAE, seeded synthetic weights: no checkpoints exist
@@ -23,7 +24,8 @@ trajectory is a denoising one with O(1) latents (with purely random weights noth
 The text encoder inside the timed region is a real-size CLIP-shaped transformers model on the device; its prompt cache is emptied before every
 batch of edits, so every step pays for its prompts.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line, with --side-legs (measurements of their own after the timed steps, about three minutes whatever --steps is;
+without it a run is set-up plus --warmup and --steps steps, so that ms_per_step predicts its length; --no-<leg> drops one leg):
   parity        this run's own check: the headline mode's latent trajectory against the f32 mode's over the FULL schedule (absolute L-inf,
                 `passes`), beside the names of the gates that pin both modes to the reference / oracle.
   fast_modes    bf16 (and with --fp8-leg the e4m3-convolution variant): throughput by the same protocol at the headline's own layout (--batch images per UNet batch; the f32 leg at --extra-batch, like
@@ -58,6 +60,7 @@ F_UP2X_B = 16.78e9      # ... of a reference row in phase B (only up_blocks[2]'s
 F_VAE_UP2X = 386.5e9
 F_REF_TAIL = 57.8e9     # what a reference row runs behind the K / V projection of transformer block 15: both TCA passes of that block's self attention
                         # (2 x 21.5 GFLOP at S = 4096, C = 320) + to_out, cross attention, feed-forward, proj_out, conv_out (14.8 GFLOP)
+DUMP_BYTES = 63 * 10**6   # payload of --dump-outputs: 64 MB in all with the .npy headers
 
 
 def synth_inputs(idx=0):
@@ -127,6 +130,7 @@ def build_model(args, device, rank, world):
 
 
 def edit_once(model, args, idx):
+    """one batch of edits through the timed path; returns what its caller receives: the list of edited 512x512x3 uint8 images"""
     K = getattr(args, "batch", 1)
     model._text_cache.clear()           # no embedding survives from one batch of edits to the next: the text encoder runs inside every timed step
     if K > 1:       # image-level batching (SURVEY 8f N3): K independent edits (own images / seeds) in one image-major UNet batch
@@ -136,11 +140,25 @@ def edit_once(model, args, idx):
             cases.append(dict(ori_img=ori_img, ori_mask=ori_mask, coarse_input=coarse, target_mask=tgt_mask,
                               guidance_text="a photo of a cup", draw_mask=draw))
         return model.FreeFine_generation_batch(cases, 7.5, 1.0, end_step=args.num_step, num_step=args.num_step, start_step=args.start_step,
-                                               method_type="tca", seeds=[42 + j for j in range(K)], end_scale=0.0)[0]
+                                               method_type="tca", seeds=[42 + j for j in range(K)], end_scale=0.0)
     ori_img, ori_mask, coarse, tgt_mask, draw = synth_inputs(idx)
-    return model.FreeFine_generation(ori_img, ori_mask, coarse, tgt_mask, "a photo of a cup", 7.5, 1.0, end_step=args.num_step,
-                                     num_step=args.num_step, start_step=args.start_step, method_type="tca", verbose=True, seed=42,
-                                     draw_mask=draw, end_scale=0.0)
+    return [model.FreeFine_generation(ori_img, ori_mask, coarse, tgt_mask, "a photo of a cup", 7.5, 1.0, end_step=args.num_step,
+                                      num_step=args.num_step, start_step=args.start_step, method_type="tca", verbose=True, seed=42,
+                                      draw_mask=draw, end_scale=0.0)]
+
+
+def dump_outputs(dirname, outs):
+    """--dump-outputs: the edited images of the last timed step, one float32 file per stream, [K, P, 3] with K the images of the
+    batch and P pixels of each 512 x 512 image: all of them, or, when all files together would exceed DUMP_BYTES, the same fixed seeded
+    sample of pixel positions in every image, stream and run (the inputs of a step depend only on the arguments, so two builds of
+    the project compare output for output)"""
+    imgs = [np.stack(o) for o in outs]                      # per stream: [K, H, W, 3] uint8
+    _, H, W, C = imgs[0].shape
+    keep = min(H * W, DUMP_BYTES // (4 * C * sum(a.shape[0] for a in imgs)))
+    pix = np.sort(np.random.default_rng(0).choice(H * W, keep, replace=False)) if keep < H * W else slice(None)
+    os.makedirs(dirname, exist_ok=True)
+    for j, a in enumerate(imgs):
+        np.save(os.path.join(dirname, f"edited_images_stream{j}.npy"), a.reshape(a.shape[0], H * W, C)[:, pix].astype(np.float32))
 
 
 def roofline_leg(model, args):
@@ -371,11 +389,14 @@ def main():
     ap.add_argument("--vae", default="sd")
     ap.add_argument("--num-step", dest="num_step", type=int, default=50)
     ap.add_argument("--start-step", dest="start_step", type=int, default=0)
-    ap.add_argument("--concurrent", type=int, default=2)
+    ap.add_argument("--concurrent", type=int, default=1, help="HIP streams, each running its own batch of edits over the same weights.  At 24 edits "
+                    "per UNet batch one stream fills the device (2.03 images/s against 2.00-2.06 with two streams), and a step takes half as long")
     ap.add_argument("--extra-batch", dest="extra_batch", type=int, default=8, help="images per UNet batch of the f32 / fast-mode side legs (min with --batch)")
-    ap.add_argument("--batch", type=int, default=24, help="independent edits per UNet batch (image-level batching).  24 x 2 streams: the 32x32 level's inversion "
-                    "batches fill 256 CUs without split-K (profiles/r5_batch_x_streams.txt: 8 x 2 1.91, 16 x 2 1.97, 16 x 3 2.01, 24 x 2 2.02 images/s); a step is 48 images, "
-                    "the driver's --steps 20 --warmup 5 about 12 minutes with the side legs at --extra-batch")
+    ap.add_argument("--batch", type=int, default=24, help="independent edits per UNet batch (image-level batching).  24: the 32x32 level's inversion "
+                    "batches fill 256 CUs without split-K (profiles/r5_batch_x_streams.txt: 8 x 2 1.91, 16 x 2 1.97, 16 x 3 2.01, 24 x 2 2.02 images/s); a step is "
+                    "--batch x --concurrent images, about 12 s at the defaults")
+    ap.add_argument("--side-legs", dest="side_legs", action="store_true", help="after the timed steps, also run the reference batch layout, roofline, "
+                    "parity, fast-mode and CPU-baseline legs (see the module docstring)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-dedup", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -390,7 +411,11 @@ def main():
     ap.add_argument("--no-fp8-leg", dest="no_fp8_leg", action="store_true", help="accepted and ignored (round-3 profiling scripts): the fp8 leg is opt-in now")
     ap.add_argument("--no-parity", action="store_true", help="skip the parity leg (f32 trajectory + throughput, the headline mode's latent deviation)")
     ap.add_argument("--no-fast-modes", dest="no_fast_modes", action="store_true", help="skip the bf16 fast-mode leg")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the edited images of the last timed step (rank 0) as DIR/edited_images_stream<j>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     rc = maybe_launch_ranks(args, sys.argv[1:])
     if rc is not None:
         sys.exit(rc)
@@ -464,14 +489,15 @@ def main():
         [t.join() for t in th]
     barrier()
     dt = time.time() - t0
-    out = outs[0]
     if world > 1:
         tt = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = tt.item()
-    assert out.shape == (512, 512, 3) and out.dtype == np.uint8
+    assert all(len(o) == args.batch and all(im.shape == (512, 512, 3) and im.dtype == np.uint8 for im in o) for o in outs)
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outs)
         n = args.num_step - args.start_step
         f_img = n * (2 * F_UNET + 4 * F_UNET + 4 * F_TCA) + F_VAE
         # executed FLOPs: the exact (math-preserving) reductions that are ON lower what runs, not what the algorithm needs -- row
@@ -521,7 +547,7 @@ def main():
                        "executed_tflops_per_gpu": round(f_exec * value / world / 1e12, 1),
                        "executed_frac_of_mfma_peak": round(f_exec * value / world / 1e12 / PEAK_TFLOPS[args.dtype], 4)},
         }
-        if args.batch > 1 and not args.no_ref_layout and world == 1:
+        if args.side_legs and args.batch > 1 and not args.no_ref_layout and world == 1:
             # the reference's own batch layout (one image per UNet call: inversion B=2, guided denoising B=4 -- BASELINE.json configs[1]
             # "batch=4"), same streams, measured beside the batched figure so both are on record
             import copy
@@ -556,18 +582,18 @@ def main():
                 "note": "same path, one image per UNet call (inversion B=2, guided B=4 logical / 3 physical rows; the reference row re-enters at up_blocks[2])"}
             del models1[len(models):], streams1[len(streams):]
             torch.cuda.empty_cache()
-        if not args.no_roofline:
+        if args.side_legs and not args.no_roofline:
             line["roofline"], table = roofline_leg(model, args)
             os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
             with open(os.path.join(ROOT, "gpurun_out", "bench_kernel_table.txt"), "w") as f:
                 f.write("kernel\tcalls\ttotal_ms\talgorithmic_TFLOP/s\talgorithmic_GB/s\n")
                 for k, c, ms, gf, gbs in table:
                     f.write(f"{k}\t{c}\t{ms:.3f}\t{gf:.1f}\t{gbs:.1f}\n")
-        if not args.no_parity and world == 1:
+        if args.side_legs and not args.no_parity and world == 1:
             line["parity"] = parity_leg(args, device, model)
-        if not args.no_fast_modes and world == 1 and args.dtype != "bf16":
+        if args.side_legs and not args.no_fast_modes and world == 1 and args.dtype != "bf16":
             line["fast_modes"] = fast_modes_leg(args, device)
-        if not args.no_cpu_baseline and world == 1:
+        if args.side_legs and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline_leg(args)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -46,6 +46,7 @@ class HipUNet:
         self.in_channels = cfg.in_channels
         self.hook, self.controller = "edit", None
         self._graphs = {}
+        self._capture_stream = None
         self._text_bufs = {}
         self.use_graph = False
         self._row_map = None
@@ -164,7 +165,7 @@ class HipUNet:
         self.t_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.cg_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
 
-    _INSTANCE_STATE = ("hook", "controller", "_graphs", "_text_bufs", "use_graph", "_row_map", "_plan_cache", "_row_idx", "t_dev", "cg_dev",
+    _INSTANCE_STATE = ("hook", "controller", "_graphs", "_capture_stream", "_text_bufs", "use_graph", "_row_map", "_plan_cache", "_row_idx", "t_dev", "cg_dev",
                        "_reuse", "_reuse_idx", "_enc_a", "last_boundary", "last_kv")
 
     def share(self):
@@ -174,6 +175,7 @@ class HipUNet:
         other.__dict__.update({k: v for k, v in self.__dict__.items() if k not in self._INSTANCE_STATE})
         other.hook, other.controller = "edit", None
         other._graphs, other._text_bufs, other._plan_cache, other._row_idx = {}, {}, {}, {}
+        other._capture_stream = None
         other._reuse, other._reuse_idx, other._enc_a, other.last_boundary, other.last_kv = None, {}, {}, None, None
         other.use_graph, other._row_map = self.use_graph, None
         other.t_dev, other.cg_dev = torch.zeros_like(self.t_dev), torch.zeros_like(self.cg_dev)
@@ -573,7 +575,11 @@ class HipUNet:
             c.cur_att_layer, c.cur_step = st
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        # captured on this executor's own stream, not torch's one default capture stream: ops._workspace picks the split-K scratch by
+        # stream, and executors whose graphs replay concurrently on different streams (share()) must not bake in the same buffer
+        if self._capture_stream is None:
+            self._capture_stream = torch.cuda.Stream(device=x_static.device)
+        with torch.cuda.graph(graph, stream=self._capture_stream):
             out = self._run(x_static, text_kv)
         rec = ru is not None and ru["mode"] == "record"
         g = dict(graph=graph, x=x_static, out=out, ref_in=ref_in, ref_bufs=ru.get("static_bufs") if ru is not None else None,

@@ -7,11 +7,18 @@ CPU restatement of the DDIM schedule and of FreeFine's two scheduler steps:
 The schedule is diffusers' DDIMScheduler as configured by SD's scheduler_config.json (scaled_linear betas 0.00085 ->
 0.012, 1000 train steps, steps_offset=1, set_alpha_to_one=False, "leading" spacing; in-tree corroboration:
 evaluation/DragDiffusion/geobench_eval.py:77-79).
+The reference writes the square roots of the step coefficients as `** 0.5`; here they are correctly rounded (_sqrt), because torch's
+float32 sqrt / pow(x, 0.5) misses by one ulp for some inputs, and for different inputs on different CPUs.
 """
 from types import SimpleNamespace
 
 import numpy as np
 import torch
+
+
+def _sqrt(x):
+    """float32 square root, correctly rounded on every host: numpy's IEEE float64 sqrt, then one rounding to float32 (exact for sqrt)"""
+    return torch.tensor(np.sqrt(x.numpy().astype(np.float64)).astype(np.float32))
 
 
 class DDIMSchedule:
@@ -35,8 +42,8 @@ def inv_step(sched, eps, timestep, x):
     t = min(next_step - sched.config.num_train_timesteps // sched.num_inference_steps, 999)
     a_t = sched.alphas_cumprod[t] if t >= 0 else sched.final_alpha_cumprod
     a_next = sched.alphas_cumprod[next_step]
-    pred_x0 = (x - (1 - a_t) ** 0.5 * eps) / a_t ** 0.5
-    x_next = a_next ** 0.5 * pred_x0 + (1 - a_next) ** 0.5 * eps
+    pred_x0 = (x - _sqrt(1 - a_t) * eps) / _sqrt(a_t)
+    x_next = _sqrt(a_next) * pred_x0 + _sqrt(1 - a_next) * eps
     return x_next, pred_x0
 
 
@@ -53,14 +60,14 @@ def ctrl_step(sched, eps, timestep, x, mask, eta, noise=None):
     prev_t = t - sched.config.num_train_timesteps // sched.num_inference_steps
     a_t = sched.alphas_cumprod[t]
     a_prev = sched.alphas_cumprod[prev_t] if prev_t > 0 else sched.final_alpha_cumprod
-    pred_x0 = (x - (1 - a_t) ** 0.5 * eps) / a_t ** 0.5
-    std = eta * get_variance(sched, t, prev_t).to(eps.dtype) ** 0.5
+    pred_x0 = (x - _sqrt(1 - a_t) * eps) / _sqrt(a_t)
+    std = eta * _sqrt(get_variance(sched, t, prev_t).to(eps.dtype))
     if eps.shape[0] == 2:
         std = torch.cat((std[None], torch.zeros_like(std)[None]))[:, None, None, None]
         mask = mask.repeat(1, 4, 1, 1)
         mask = torch.cat((mask, torch.ones_like(mask)))
-    pred_dir = (1 - a_prev) ** 0.5 * eps * (1 - mask) + (1 - a_prev - std ** 2) ** 0.5 * eps * mask
-    x_prev = a_prev ** 0.5 * pred_x0 + pred_dir
+    pred_dir = _sqrt(1 - a_prev) * eps * (1 - mask) + _sqrt(1 - a_prev - std ** 2) * eps * mask
+    x_prev = _sqrt(a_prev) * pred_x0 + pred_dir
     if eta > 0:
         x_prev = x_prev + std * noise * mask
     return x_prev, pred_x0
