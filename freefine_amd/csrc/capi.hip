@@ -238,15 +238,6 @@ extern "C" int ffn_igemm_variant(const ffn_igemm_desc* d, int* bm, int* bn) {
     igemm_tile_for(*d, bm, bn);
     return FFN_OK;
 }
-extern "C" int ffn_attn_variant(int dtype, int D, int* dp, int* qf) {
-    REQUIRE(dp && qf, "attn_variant: null argument");
-    if (dtype == FFN_F32) {
-        if (D <= 48) { *dp = 48; *qf = 2; } else if (D <= 64) { *dp = 64; *qf = 2; } else if (D <= 80) { *dp = 80; *qf = 2; } else { *dp = 160; *qf = 1; }
-    } else {
-        if (D <= 64) { *dp = 64; *qf = 2; } else if (D <= 96) { *dp = 96; *qf = 2; } else { *dp = 160; *qf = 1; }
-    }
-    return FFN_OK;
-}
 
 
 // ---- bf16 tile configurations and first-use autotuning ------------------------------------------------------------------
@@ -1015,133 +1006,149 @@ extern "C" int ffn_igemm(void* stream, int dtype, const ffn_igemm_desc* d) {
 extern "C" int ffn_igemm_tune(void* stream, int dtype, const ffn_igemm_desc* d) { return ffn_igemm(stream, dtype, d); }
 
 // ---- attention ---------------------------------------------------------------------------------------------------
-template <typename T, int DP, int QF, int KT = 64, int OCC = 1, bool MASKS = true>
-static int launch_attn(hipStream_t s, const ffn_attn_desc& d) {
-    constexpr int SZ = sizeof(T);
-    // double-buffered K and V^T tiles + the per-wave multi-pass accumulator
-    constexpr int krow = (DP * SZ == 128) ? 128 : DP * SZ + 16;
-    constexpr int vrow = (DP * SZ == 128 && KT * SZ == 128) ? 128 : KT * SZ + 16;
-    constexpr int lds = 2 * (KT * krow + DP * vrow) + 4 * (DP / 16) * QF * 64 * 16 + 2 * KT;   // + key-mask bytes of the two staged tiles
-    static_assert(lds <= 160 * 1024, "attention tile does not fit the 160 KiB LDS");
-    auto kern = attn_kernel<T, DP, QF, KT, OCC, MASKS>;
-    if (int rc = set_lds(kern, lds)) return rc;      // memoised under a mutex: safe from several host threads
-    // 1-D grid, decoded in the kernel through xcd_remap: the query blocks of one (row, head) run on ONE XCD, whose 4 MiB L2 then
-    // serves that head's K / V^T (1 MiB at S = 4096) to all of them (measured before: 721 MB fetched for 126 MB of operands)
-    dim3 grid(((d.S + 64 * QF - 1) / (64 * QF)) * d.heads * d.Bo);
-    LAUNCH(kern, grid, dim3(256), lds, s, d);
-    return check_launch("attn");
+// attn_kernel's instantiations (attention.h), by head dim: the first row whose padded head dim DP >= D (the last row also answers
+// ffn_attn_variant for larger D, which ffn_attn refuses)
+struct AttnTile { int dp, qf, kt, occ; };      // padded head dim, 16-query fragments per wave, keys per tile, workgroups per CU
+static const AttnTile kAttnTileF32[] = {{48, 2, 64, 1}, {64, 2, 64, 1}, {80, 2, 64, 1}, {160, 1, 32, 1}};
+static const AttnTile kAttnTileBf16[] = {{64, 2, 64, 2}, {96, 2, 64, 1}, {160, 1, 64, 1}};
+static AttnTile attn_tile(bool f32, int D) {
+    const AttnTile* t = f32 ? kAttnTileF32 : kAttnTileBf16;
+    const int n = f32 ? 4 : 3;
+    int i = 0;
+    while (i + 1 < n && D > t[i].dp) ++i;
+    return t[i];
 }
-// bf16 launches: whether some active entry carries a key mask (-> the kernel variant with the mask-on-MFMA tile) and whether the
-// launch runs on the ping-pong schedule (attention_pp.h): d = 64, whole 64-key tiles, at least half a 256-query workgroup of queries,
-// no degenerate uniform-softmax entries (those need the generic tile)
-static void attn_bf16_choice(const ffn_attn_desc& d, bool* masks, bool* pp) {
-    bool m = false, uniform = false;
+extern "C" int ffn_attn_variant(int dtype, int D, int* dp, int* qf) {
+    REQUIRE(dp && qf, "attn_variant: null argument");
+    const AttnTile t = attn_tile(dtype == FFN_F32, D);
+    *dp = t.dp;
+    *qf = t.qf;
+    return FFN_OK;
+}
+// double-buffered K and V^T tiles + the per-wave multi-pass accumulator + the key-mask bytes of the two staged tiles
+static constexpr int attn_kernel_lds(int esz, int dp, int qf, int kt) {
+    return 2 * (kt * (dp * esz == 128 ? 128 : dp * esz + 16) + dp * ((dp * esz == 128 && kt * esz == 128) ? 128 : kt * esz + 16)) + 4 * (dp / 16) * qf * 64 * 16 + 2 * kt;
+}
+static_assert(attn_kernel_lds(4, 160, 1, 32) <= 160 * 1024 && attn_kernel_lds(2, 160, 1, 64) <= 160 * 1024, "attention tile does not fit the 160 KiB LDS");
+
+// attn_x3w_kernel lives in its own translation unit (attn_x3w.hip: different code generation flags)
+typedef void (*attn_x3w_t)(ffn_attn_desc);
+extern "C" __attribute__((visibility("hidden"))) attn_x3w_t fx3w_kernel(int masks);
+extern "C" __attribute__((visibility("hidden"))) int fx3w_lds_bytes(void);
+
+enum AttnKind { ATT_KERNEL, ATT_PP, ATT_X, ATT_X_MP, ATT_X3, ATT_X3P, ATT_X3W, ATT_XX3 };
+struct AttnPlan {
+    AttnKind kind;
+    bool f32;           // ATT_KERNEL: fp32 (else bf16) operands
+    bool masks;         // the instantiation for launches with key masks
+    AttnTile tile;      // ATT_KERNEL
+    int nkf, nw;        // xattn*: 16-key fragments; waves that share a workgroup's work split (xattn_kernel: 1, its waves work alone)
+    int lds;
+    dim3 grid, block;   // (xattn*: the grid depends on the CU count and is set at launch)
+};
+// The one statement of which kernel ffn_attn launches for a descriptor: ffn_attn launches from it, ffn_attn_kernel_name spells it.
+//   FFN_BF16X3, D <= 64 (split-bf16 arithmetic on fp32 operands):
+//     xattn_x3_kernel (attention_xx3.h) for short unmasked key sequences (the text cross attention) whose fragment images fit the LDS;
+//     else on the ping-pong preconditions (D = 64, Sk % 64 == 0, S >= 128, no degenerate uniform-softmax entry): attn_x3w_kernel
+//     (attention_x3w.h) on pre-split K / V^T images (kv_pair), attn_x3p_kernel (attention_x3p.h) on fp32 K / V^T;
+//     else attn_x3_kernel (attention_x3.h).
+//   FFN_BF16: xattn_kernel / xattn_mp_kernel (attention_x.h) for short unmasked key sequences; attn_pp_kernel (attention_pp.h) on the
+//     ping-pong preconditions; else attn_kernel (attention.h).
+//   FFN_F32, and FFN_BF16X3 with larger heads: the exact fp32 attn_kernel.
+// FFN_EINVAL: kv_pair for a launch that does not run attn_x3w_kernel; FFN_ENOSYS: head dim beyond 160.
+static int attn_plan(int dtype, const ffn_attn_desc& d, AttnPlan* p) {
+    bool masks = false, uniform = false, xok = true, multi = d.npass != 1;
+    int maxq = 0, maxkv = 0;
     for (int pi = 0; pi < d.npass; ++pi)
         for (int b = 0; b < d.Bo; ++b) {
             const ffn_attn_entry& e = d.e[pi * FFN_ATT_MAXB + b];
-            if (e.w_const == 0.f && e.w_slope == 0.f) continue;
-            m |= e.kmask != nullptr;
+            if (e.w_const == 0.f && e.w_slope == 0.f) { multi = true; continue; }
+            masks |= e.kmask != nullptr;
             uniform |= e.kmask != nullptr && (e.flags & (FFN_ATT_UNIFORM_SEL1 | FFN_ATT_UNIFORM_SEL0));
-        }
-    static const bool pp_on = [] { const char* e = getenv("FFN_ATTN_PP"); return !(e && atoi(e) == 0); }();
-    *masks = m;
-    *pp = pp_on && d.D == 64 && d.Sk % 64 == 0 && d.S >= 128 && !uniform;
-}
-// cross attention against a short key sequence (attention_x.h): bf16, d = 64, Sk <= 96, ONE pass whose entries are all active and carry
-// no mask / selector / per-query weight.  Returns the key-fragment count of the instantiation (0: not this kernel).
-// *multi = 1: the launch has several passes, skipped entries or per-query weights -> xattn_mp_kernel (K / V^T fragment images in LDS).
-// esz = bytes per operand element: 2 (bf16 kernels) or 4 (xattn_x3_kernel, attention_xx3.h: fp32 operands in split-bf16 arithmetic)
-static int xattn_nkf(const ffn_attn_desc& d, int* multi = nullptr, int esz = 2) {
-    static const bool on = [] { const char* e = getenv("FFN_ATTN_X"); return !(e && atoi(e) == 0); }();
-    if (!on || d.D != 64 || d.Sk > 96 || (esz == 2 && d.ldo % 8 != 0)) return 0;
-    int maxq = 0, maxkv = 0, mp = d.npass != 1;
-    for (int pi = 0; pi < d.npass; ++pi)
-        for (int b = 0; b < d.Bo; ++b) {
-            const ffn_attn_entry& e = d.e[pi * FFN_ATT_MAXB + b];
-            if (e.w_const == 0.f && e.w_slope == 0.f) { mp = 1; continue; }
-            if (e.kmask || e.qsel) return 0;                    // (flags only qualify a key mask)
-            if (e.w_slope != 0.f && !d.w_dev) return 0;
-            if (e.wq) mp = 1;
+            xok &= !e.kmask && !e.qsel && (e.w_slope == 0.f || d.w_dev);      // (flags only qualify a key mask)
+            multi |= e.wq != nullptr;
             maxq = e.q_row > maxq ? e.q_row : maxq;
             maxkv = e.kv_row > maxkv ? e.kv_row : maxkv;
         }
-    if (multi) *multi = mp;
-    const long lim = (1l << 31) - 65536;              // 32-bit byte offsets into every operand
-    if ((long)(maxq + 1) * d.S * d.ldq * esz >= lim || (long)d.Bo * d.S * d.ldo * esz >= lim || (long)(maxkv + 1) * d.Sk * d.ldk * esz >= lim ||
-        (long)(maxkv + 1) * d.heads * 64 * d.ldvt * esz >= lim)
-        return 0;
-    const int need = (d.Sk + 15) / 16;
-    return need <= 2 ? 2 : (need <= 5 ? 5 : 6);
-}
-static int launch_xattn(hipStream_t s, const ffn_attn_desc& d, int nkf, int multi) {
-    const int pairs = d.Bo * d.heads, nblk = (d.S + 31) / 32;
-    if (multi) {                                      // one workgroup of 4 waves per (row, head, chunk): fragment images of all passes in LDS
-        int wpp = (8 * device_cus()) / pairs / 4;     // workgroups per (row, head)
-        if (wpp < 1) wpp = 1;
-        if (wpp > (nblk + 3) / 4) wpp = (nblk + 3) / 4;
-        const int bpw = (nblk + 4 * wpp - 1) / (4 * wpp);
-        wpp = (nblk + 4 * bpw - 1) / (4 * bpw);
-        const int nfr = nkf * 2 + 4 * ((nkf + 1) / 2);
-        const int lds = d.npass * nfr * 1024;
-        dim3 grid(pairs * wpp);
-        int rc;
-        if (nkf == 2) { if ((rc = set_lds(xattn_mp_kernel<2>, lds))) return rc; LAUNCH(xattn_mp_kernel<2>, grid, dim3(256), lds, s, d, wpp, bpw); }
-        else if (nkf == 5) { if ((rc = set_lds(xattn_mp_kernel<5>, lds))) return rc; LAUNCH(xattn_mp_kernel<5>, grid, dim3(256), lds, s, d, wpp, bpw); }
-        else { if ((rc = set_lds(xattn_mp_kernel<6>, lds))) return rc; LAUNCH(xattn_mp_kernel<6>, grid, dim3(256), lds, s, d, wpp, bpw); }
-        return check_launch("attn(cross, multi-pass)");
-    }
-    int wpp = (8 * device_cus()) / pairs;             // waves per (row, head): fill the chip's 8 waves per CU once
-    if (wpp < 1) wpp = 1;
-    if (wpp > nblk) wpp = nblk;
-    const int bpw = (nblk + wpp - 1) / wpp;
-    wpp = (nblk + bpw - 1) / bpw;
-    dim3 grid((pairs * wpp + 3) / 4);
-    if (nkf == 2) LAUNCH(xattn_kernel<2>, grid, dim3(256), 0, s, d, wpp, bpw);
-    else if (nkf == 5) LAUNCH(xattn_kernel<5>, grid, dim3(256), 0, s, d, wpp, bpw);
-    else LAUNCH(xattn_kernel<6>, grid, dim3(256), 0, s, d, wpp, bpw);
-    return check_launch("attn(cross)");
-}
-// the split-bf16 form: always the LDS-fragment-image structure (hi and lo images of every active pass: 2 x nfr KiB per pass)
-template <int NW>
-static int launch_xattn_x3_nw(hipStream_t s, const ffn_attn_desc& d, int nkf, int waves_per_cu) {
-    const int pairs = d.Bo * d.heads, nblk = (d.S + 31) / 32;
-    int wpp = (waves_per_cu * device_cus()) / pairs / NW;         // workgroups per (row, head)
-    if (wpp < 1) wpp = 1;
-    if (wpp > (nblk + NW - 1) / NW) wpp = (nblk + NW - 1) / NW;
-    const int bpw = (nblk + NW * wpp - 1) / (NW * wpp);
-    wpp = (nblk + NW * bpw - 1) / (NW * bpw);
-    const int nfr = nkf * 2 + 4 * ((nkf + 1) / 2);
-    const int lds = d.npass * 2 * nfr * 1024;
-    if (lds > 160 * 1024) return -1;                  // (more passes than fit: the caller takes the generic kernel)
-    dim3 grid(pairs * wpp);
-    int rc;
-    if (nkf == 2) { if ((rc = set_lds(xattn_x3_kernel<2, NW>, lds))) return rc; LAUNCH((xattn_x3_kernel<2, NW>), grid, dim3(64 * NW), lds, s, d, wpp, bpw); }
-    else if (nkf == 5) { if ((rc = set_lds(xattn_x3_kernel<5, NW>, lds))) return rc; LAUNCH((xattn_x3_kernel<5, NW>), grid, dim3(64 * NW), lds, s, d, wpp, bpw); }
-    else { if ((rc = set_lds(xattn_x3_kernel<6, NW>, lds))) return rc; LAUNCH((xattn_x3_kernel<6, NW>), grid, dim3(64 * NW), lds, s, d, wpp, bpw); }
-    return check_launch("attn(cross, split-bf16)");
-}
-static int launch_xattn_x3(hipStream_t s, const ffn_attn_desc& d, int nkf) {
-    // 8 waves per workgroup where the fragment images are large against a workgroup's share of the queries (two passes: 88 KiB, one workgroup per CU
-    // either way) or the launch is long; 4 (two workgroups per CU) for the short single-pass launches (profiles/r5_xattn_x3_waves_and_stores.txt)
-    static const int nw_env = [] { const char* e = getenv("FFN_XATT_NW"); return e ? atoi(e) : 0; }();
-    const int nw = nw_env ? nw_env : ((d.npass >= 2 || d.S >= 4096) ? 8 : 4);
-    return nw == 8 ? launch_xattn_x3_nw<8>(s, d, nkf, 8) : launch_xattn_x3_nw<4>(s, d, nkf, 8);
-}
-static bool xattn_x3_fits(const ffn_attn_desc& d, int nkf) { return d.npass * 2 * (nkf * 2 + 4 * ((nkf + 1) / 2)) * 1024 <= 160 * 1024; }
-// attn_x3w_kernel lives in its own translation unit (attn_x3w.hip: different code generation flags)
-extern "C" __attribute__((visibility("hidden"))) int fx3w_launch(hipStream_t s, const ffn_attn_desc* d, int masks);
-static bool attn_x3w_on() {       // FFN_ATTN_X3W=0: attn_x3p_kernel<., PAIRKV> (round 5) instead; read per call so that tests can compare the two
-    const char* e = getenv("FFN_ATTN_X3W");
-    return !e || atoi(e) != 0;
-}
-static bool attn_has_masks(const ffn_attn_desc& d) {
-    for (int pi = 0; pi < d.npass; ++pi)
-        for (int b = 0; b < d.Bo; ++b) {
-            const ffn_attn_entry& e = d.e[pi * FFN_ATT_MAXB + b];
-            if ((e.w_const != 0.f || e.w_slope != 0.f) && e.kmask) return true;
+    const bool pp = d.D == 64 && d.Sk % 64 == 0 && d.S >= 128 && !uniform;
+    // the short-key kernels: D = 64, Sk <= 96, 32-bit byte offsets into every operand (esz = bytes per operand element); key-fragment count
+    auto xattn_nkf = [&](int esz) {
+        const long lim = (1l << 31) - 65536;
+        if (!xok || d.D != 64 || d.Sk > 96 || (esz == 2 && d.ldo % 8 != 0) || (long)(maxq + 1) * d.S * d.ldq * esz >= lim ||
+            (long)d.Bo * d.S * d.ldo * esz >= lim || (long)(maxkv + 1) * d.Sk * d.ldk * esz >= lim || (long)(maxkv + 1) * d.heads * 64 * d.ldvt * esz >= lim)
+            return 0;
+        const int need = (d.Sk + 15) / 16;
+        return need <= 2 ? 2 : (need <= 5 ? 5 : 6);
+    };
+    *p = AttnPlan{};
+    p->masks = masks;
+    p->grid = dim3(((d.S + 255) / 256) * d.heads * d.Bo);      // the 256-query workgroups of the ping-pong and split-bf16 kernels
+    p->block = dim3(512);
+    if (dtype == FFN_BF16X3 && d.D <= 64) {
+        p->nkf = xattn_nkf(4);
+        const int nfr = p->nkf * 2 + 4 * ((p->nkf + 1) / 2);   // 1 KiB fragment images per pass: hi and lo each
+        if (p->nkf && d.npass * 2 * nfr * 1024 <= 160 * 1024) {
+            // 8 waves per workgroup where the fragment images are large against a workgroup's share of the queries (two passes: 88 KiB, one workgroup
+            // per CU either way) or the launch is long; 4 (two workgroups per CU) for the short single-pass launches (profiles/r5_xattn_x3_waves_and_stores.txt)
+            p->kind = ATT_XX3;
+            p->nw = (d.npass >= 2 || d.S >= 4096) ? 8 : 4;
+            p->lds = d.npass * 2 * nfr * 1024;
+            p->block = dim3(64 * p->nw);
+        } else if (pp && d.kv_pair) {                           // one wave per SIMD on 32x32x16 MFMAs
+            p->kind = ATT_X3W;
+            p->lds = fx3w_lds_bytes();
+            p->block = dim3(256);
+        } else if (pp) {
+            p->kind = ATT_X3P;
+            p->lds = 5 * (2 * 8192) + 8 * 4 * 2 * 64 * 16;      // K ring of 2 + V^T ring of 3 [hi | lo] images, multi-pass sums
+        } else {
+            p->kind = ATT_X3;
+            p->lds = 2 * (4 * 8192) + 8 * 4 * 2 * 64 * 16;
         }
-    return false;
+    } else if (dtype == FFN_BF16 && (p->nkf = xattn_nkf(2))) {
+        // one pass of plain active entries: K / V^T of a (row, head) in a wave's registers; several passes, skipped entries or per-query
+        // weights: one workgroup of 4 waves per (row, head, chunk) with the fragment images of every pass in LDS
+        p->kind = multi ? ATT_X_MP : ATT_X;
+        p->nw = multi ? 4 : 1;
+        p->lds = multi ? d.npass * (p->nkf * 2 + 4 * ((p->nkf + 1) / 2)) * 1024 : 0;
+        p->block = dim3(256);
+    } else if (dtype == FFN_BF16 && pp) {
+        p->kind = ATT_PP;
+        p->lds = 4 * 8192 + 4 * 8192 + 4 * 256 + 8 * 4 * 2 * 64 * 16;
+    } else {
+        p->kind = ATT_KERNEL;
+        p->f32 = dtype != FFN_BF16;
+        p->masks |= p->f32;                                     // (one fp32 instantiation, with key masks)
+        p->tile = attn_tile(p->f32, d.D);
+        p->lds = attn_kernel_lds(p->f32 ? 4 : 2, p->tile.dp, p->tile.qf, p->tile.kt);
+        // 1-D grid, decoded in the kernel through xcd_remap: the query blocks of one (row, head) run on ONE XCD, whose 4 MiB L2 then
+        // serves that head's K / V^T (1 MiB at S = 4096) to all of them (measured before: 721 MB fetched for 126 MB of operands)
+        p->grid = dim3(((d.S + 64 * p->tile.qf - 1) / (64 * p->tile.qf)) * d.heads * d.Bo);
+        p->block = dim3(256);
+    }
+    REQUIRE(!d.kv_pair || p->kind == ATT_X3W, "attn: kv_pair is for launches that run attn_x3w_kernel (FFN_BF16X3, D = 64, Sk %% 64 == 0, S >= 128, "
+                                              "no uniform-softmax entry, not the short-key kernel)");
+    if (p->kind == ATT_KERNEL && d.D > 160) return fail(FFN_ENOSYS, "attn: head dim %d not supported (max 160; use the GEMM path)", d.D);
+    return FFN_OK;
 }
+// the xattn kernels' work split over (row, head) pairs: wpp workgroups (xattn_kernel: waves) per pair, bpw 32-query blocks per wave, the chip's
+// 8 waves per CU filled once
+static dim3 xattn_grid(const ffn_attn_desc& d, int nw, int* wpp, int* bpw) {
+    const int pairs = d.Bo * d.heads, nblk = (d.S + 31) / 32;
+    int w = (8 * device_cus()) / pairs / nw;
+    if (w < 1) w = 1;
+    if (w > (nblk + nw - 1) / nw) w = (nblk + nw - 1) / nw;
+    *bpw = (nblk + nw * w - 1) / (nw * w);
+    *wpp = (nblk + nw * *bpw - 1) / (nw * *bpw);
+    return dim3(nw == 1 ? (pairs * *wpp + 3) / 4 : pairs * *wpp);
+}
+template <typename K, typename... A>
+static int attn_launch(const AttnPlan& p, K kern, hipStream_t s, A... args) {
+    if (int rc = set_lds(kern, p.lds)) return rc;       // memoised under a mutex: safe from several host threads
+    LAUNCH(kern, p.grid, p.block, p.lds, s, args...);
+    return check_launch("attn");
+}
+
 extern "C" int ffn_attn_presplit(void* stream, const float* k, const float* vt, void* k_pair, void* vt_pair, int rows, int Sk, int heads, int ldk, int ldvt) {
     REQUIRE(k && vt && k_pair && vt_pair && aligned16(k) && aligned16(vt) && aligned16(k_pair) && aligned16(vt_pair), "attn_presplit: null / unaligned pointer");
     REQUIRE(rows > 0 && heads > 0 && Sk > 0 && Sk % 64 == 0 && ldk >= heads * 64 && ldk % 4 == 0 && ldvt >= Sk && ldvt % 4 == 0,
@@ -1154,36 +1161,20 @@ extern "C" int ffn_attn_presplit(void* stream, const float* k, const float* vt, 
 }
 extern "C" int ffn_attn_kernel_name(int dtype, const ffn_attn_desc* d, char* buf, int len) {
     REQUIRE(d && buf && len > 0, "attn_kernel_name: null argument");
-    int dp = 0, qf = 0;
-    if (dtype == FFN_BF16X3 && d->D <= 64) {
-        if (const int nkf = xattn_nkf(*d, nullptr, 4)) {
-            if (xattn_x3_fits(*d, nkf)) {
-                snprintf(buf, len, "void xattn_x3_kernel<%d, %d>(ffn_attn_desc, int, int)", nkf, (d->npass >= 2 || d->S >= 4096) ? 8 : 4);
-                return FFN_OK;
-            }
-        }
-        bool masks, pp;
-        attn_bf16_choice(*d, &masks, &pp);
-        if (pp && d->kv_pair && attn_x3w_on()) snprintf(buf, len, "void attn_x3w_kernel<%s>(ffn_attn_desc)", attn_has_masks(*d) ? "true" : "false");
-        else if (pp) snprintf(buf, len, "void attn_x3p_kernel<%s, %s>(ffn_attn_desc)", attn_has_masks(*d) ? "true" : "false", d->kv_pair ? "true" : "false");
-        else snprintf(buf, len, "void attn_x3_kernel<%s>(ffn_attn_desc)", attn_has_masks(*d) ? "true" : "false");
-        return FFN_OK;
+    REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16 || dtype == FFN_BF16X3, "attn_kernel_name: bad dtype %d", dtype);
+    AttnPlan p;
+    if (int rc = attn_plan(dtype, *d, &p)) return rc;
+    const char* m = p.masks ? "true" : "false";
+    switch (p.kind) {
+    case ATT_KERNEL: snprintf(buf, len, "void attn_kernel<%s, %d, %d, %d, %d, %s>(ffn_attn_desc)", p.f32 ? "float" : "bf16", p.tile.dp, p.tile.qf, p.tile.kt, p.tile.occ, m); break;
+    case ATT_PP: snprintf(buf, len, "void attn_pp_kernel<%s>(ffn_attn_desc)", m); break;
+    case ATT_X: snprintf(buf, len, "void xattn_kernel<%d>(ffn_attn_desc, int, int)", p.nkf); break;
+    case ATT_X_MP: snprintf(buf, len, "void xattn_mp_kernel<%d>(ffn_attn_desc, int, int)", p.nkf); break;
+    case ATT_X3: snprintf(buf, len, "void attn_x3_kernel<%s>(ffn_attn_desc)", m); break;
+    case ATT_X3P: snprintf(buf, len, "void attn_x3p_kernel<%s>(ffn_attn_desc)", m); break;
+    case ATT_X3W: snprintf(buf, len, "void attn_x3w_kernel<%s>(ffn_attn_desc)", m); break;
+    case ATT_XX3: snprintf(buf, len, "void xattn_x3_kernel<%d, %d>(ffn_attn_desc, int, int)", p.nkf, p.nw); break;
     }
-    if (dtype == FFN_BF16X3) dtype = FFN_F32;
-    ffn_attn_variant(dtype, d->D, &dp, &qf);
-    if (dtype == FFN_F32) {
-        snprintf(buf, len, "void attn_kernel<float, %d, %d, %d, 1, true>(ffn_attn_desc)", dp, qf, dp == 160 ? 32 : 64);
-        return FFN_OK;
-    }
-    int multi = 0;
-    if (const int nkf = xattn_nkf(*d, &multi)) {
-        snprintf(buf, len, "void %s<%d>(ffn_attn_desc, int, int)", multi ? "xattn_mp_kernel" : "xattn_kernel", nkf);
-        return FFN_OK;
-    }
-    bool masks, pp;
-    attn_bf16_choice(*d, &masks, &pp);
-    if (pp) snprintf(buf, len, "void attn_pp_kernel<%s>(ffn_attn_desc)", masks ? "true" : "false");
-    else snprintf(buf, len, "void attn_kernel<bf16, %d, %d, 64, %d, %s>(ffn_attn_desc)", dp, qf, dp == 64 ? 2 : 1, masks ? "true" : "false");
     return FFN_OK;
 }
 extern "C" int ffn_attn(void* stream, int dtype, const ffn_attn_desc* d) {
@@ -1203,10 +1194,9 @@ extern "C" int ffn_attn(void* stream, int dtype, const ffn_attn_desc* d) {
         // the cross-attention kernel places pair columns by heads * D, the others by ldo / 2: the two agree in these cases only
         REQUIRE(d->ldo / 2 == d->heads * d->D || ((d->ldo / 2) % 32 == 0 && (d->heads * d->D) % 32 == 0), "attn: pair output into a wider row needs 32-column blocks (ldo=%d, heads*D=%d)", d->ldo, d->heads * d->D);
     }
+    AttnPlan p;
+    if (int rc = attn_plan(dtype, *d, &p)) return rc;
     if (d->kv_pair) {
-        bool m_, pp_;
-        attn_bf16_choice(*d, &m_, &pp_);
-        REQUIRE(dtype == FFN_BF16X3 && pp_ && !xattn_nkf(*d, nullptr, 4), "attn: kv_pair is for launches that run attn_x3p_kernel (FFN_BF16X3, D = 64, Sk %% 64 == 0, S >= 128, no uniform-softmax entry)");
         long maxkv = 0;
         for (int pi = 0; pi < d->npass; ++pi)
             for (int b = 0; b < d->Bo; ++b) maxkv = d->e[pi * FFN_ATT_MAXB + b].kv_row > maxkv ? d->e[pi * FFN_ATT_MAXB + b].kv_row : maxkv;
@@ -1216,81 +1206,41 @@ extern "C" int ffn_attn(void* stream, int dtype, const ffn_attn_desc* d) {
                 "attn: pre-split K / V^T images beyond 2 GiB (32-bit byte offsets)");
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int D = d->D;
-    if (dtype == FFN_BF16X3 && D <= 64) {      // split-bf16 arithmetic on fp32 operands (attention_x3.h); other head sizes: the exact fp32 kernel
-        if (const int nkf = xattn_nkf(*d, nullptr, 4)) {       // short unmasked key sequences (the text cross attention): attention_xx3.h
-            if (xattn_x3_fits(*d, nkf)) return launch_xattn_x3(s, *d, nkf);
-        }
-        constexpr int lds = 2 * (4 * 8192) + 8 * 4 * 2 * 64 * 16;
-        dim3 grid(((d->S + 255) / 256) * d->heads * d->Bo);
-        int rc;
-        bool masks_pp, pp;
-        attn_bf16_choice(*d, &masks_pp, &pp);      // the ping-pong schedule has the same preconditions as attn_pp_kernel's (d = 64, Sk % 64 == 0, S >= 128, ...)
-        if (pp) {
-            constexpr int lds = 5 * (2 * 8192) + 8 * 4 * 2 * 64 * 16;      // K ring of 2 + V^T ring of 3 [hi | lo] images, multi-pass sums
-            if (d->kv_pair && attn_x3w_on()) {      // round 6: one wave per SIMD on 32x32x16 MFMAs (attention_x3w.h), same pre-split images
-                const hipError_t e = (hipError_t)fx3w_launch(s, d, attn_has_masks(*d) ? 1 : 0);
-                if (e != hipSuccess) return fail(FFN_EHIP, "attn(split-bf16, one wave per SIMD): %s", hipGetErrorString(e));
-                return FFN_OK;
+    int wpp = 0, bpw = 0;
+    if (p.kind == ATT_X || p.kind == ATT_X_MP || p.kind == ATT_XX3) p.grid = xattn_grid(*d, p.nw, &wpp, &bpw);
+    switch (p.kind) {
+    case ATT_KERNEL:
+        if (p.f32) {
+            switch (p.tile.dp) {
+            case 48: return attn_launch(p, attn_kernel<float, 48, 2, 64, 1, true>, s, *d);
+            case 64: return attn_launch(p, attn_kernel<float, 64, 2, 64, 1, true>, s, *d);
+            case 80: return attn_launch(p, attn_kernel<float, 80, 2, 64, 1, true>, s, *d);
+            default: return attn_launch(p, attn_kernel<float, 160, 1, 32, 1, true>, s, *d);
             }
-            if (d->kv_pair) {                       // pre-split K / V^T images by LDS-DMA (+ 512 B of key-mask bytes)
-                constexpr int ldsp = lds + 512;
-                if (attn_has_masks(*d)) {
-                    if ((rc = set_lds(attn_x3p_kernel<true, true>, ldsp))) return rc;
-                    LAUNCH((attn_x3p_kernel<true, true>), grid, dim3(512), ldsp, s, *d);
-                } else {
-                    if ((rc = set_lds(attn_x3p_kernel<false, true>, ldsp))) return rc;
-                    LAUNCH((attn_x3p_kernel<false, true>), grid, dim3(512), ldsp, s, *d);
-                }
-                return check_launch("attn(split-bf16, ping-pong, pre-split K/V)");
-            }
-            if (attn_has_masks(*d)) {
-                if ((rc = set_lds(attn_x3p_kernel<true>, lds))) return rc;
-                LAUNCH(attn_x3p_kernel<true>, grid, dim3(512), lds, s, *d);
-            } else {
-                if ((rc = set_lds(attn_x3p_kernel<false>, lds))) return rc;
-                LAUNCH(attn_x3p_kernel<false>, grid, dim3(512), lds, s, *d);
-            }
-            return check_launch("attn(split-bf16, ping-pong)");
         }
-        if (attn_has_masks(*d)) {
-            if ((rc = set_lds(attn_x3_kernel<true>, lds))) return rc;
-            LAUNCH(attn_x3_kernel<true>, grid, dim3(512), lds, s, *d);
-        } else {
-            if ((rc = set_lds(attn_x3_kernel<false>, lds))) return rc;
-            LAUNCH(attn_x3_kernel<false>, grid, dim3(512), lds, s, *d);
+        switch (p.tile.dp) {
+        case 64: return p.masks ? attn_launch(p, attn_kernel<bf16, 64, 2, 64, 2, true>, s, *d) : attn_launch(p, attn_kernel<bf16, 64, 2, 64, 2, false>, s, *d);
+        case 96: return p.masks ? attn_launch(p, attn_kernel<bf16, 96, 2, 64, 1, true>, s, *d) : attn_launch(p, attn_kernel<bf16, 96, 2, 64, 1, false>, s, *d);
+        default: return p.masks ? attn_launch(p, attn_kernel<bf16, 160, 1, 64, 1, true>, s, *d) : attn_launch(p, attn_kernel<bf16, 160, 1, 64, 1, false>, s, *d);
         }
-        return check_launch("attn(split-bf16)");
+    case ATT_PP: return p.masks ? attn_launch(p, attn_pp_kernel<true>, s, *d) : attn_launch(p, attn_pp_kernel<false>, s, *d);
+    case ATT_X:
+        return p.nkf == 2 ? attn_launch(p, xattn_kernel<2>, s, *d, wpp, bpw)
+             : p.nkf == 5 ? attn_launch(p, xattn_kernel<5>, s, *d, wpp, bpw) : attn_launch(p, xattn_kernel<6>, s, *d, wpp, bpw);
+    case ATT_X_MP:
+        return p.nkf == 2 ? attn_launch(p, xattn_mp_kernel<2>, s, *d, wpp, bpw)
+             : p.nkf == 5 ? attn_launch(p, xattn_mp_kernel<5>, s, *d, wpp, bpw) : attn_launch(p, xattn_mp_kernel<6>, s, *d, wpp, bpw);
+    case ATT_X3: return p.masks ? attn_launch(p, attn_x3_kernel<true>, s, *d) : attn_launch(p, attn_x3_kernel<false>, s, *d);
+    case ATT_X3P: return p.masks ? attn_launch(p, attn_x3p_kernel<true>, s, *d) : attn_launch(p, attn_x3p_kernel<false>, s, *d);
+    case ATT_X3W: return attn_launch(p, fx3w_kernel(p.masks), s, *d);
+    case ATT_XX3:
+        if (p.nw == 8)
+            return p.nkf == 2 ? attn_launch(p, xattn_x3_kernel<2, 8>, s, *d, wpp, bpw)
+                 : p.nkf == 5 ? attn_launch(p, xattn_x3_kernel<5, 8>, s, *d, wpp, bpw) : attn_launch(p, xattn_x3_kernel<6, 8>, s, *d, wpp, bpw);
+        return p.nkf == 2 ? attn_launch(p, xattn_x3_kernel<2, 4>, s, *d, wpp, bpw)
+             : p.nkf == 5 ? attn_launch(p, xattn_x3_kernel<5, 4>, s, *d, wpp, bpw) : attn_launch(p, xattn_x3_kernel<6, 4>, s, *d, wpp, bpw);
     }
-    if (dtype == FFN_BF16X3) dtype = FFN_F32;
-    if (dtype == FFN_F32) {
-        if (D <= 48) return launch_attn<float, 48, 2>(s, *d);
-        if (D <= 64) return launch_attn<float, 64, 2>(s, *d);
-        if (D <= 80) return launch_attn<float, 80, 2>(s, *d);
-        if (D <= 160) return launch_attn<float, 160, 1, 32>(s, *d);
-    } else {
-        int multi = 0;
-        if (const int nkf = xattn_nkf(*d, &multi)) return launch_xattn(s, *d, nkf, multi);
-        bool masks, pp;
-        attn_bf16_choice(*d, &masks, &pp);
-        if (pp) {
-            constexpr int lds = 4 * 8192 + 4 * 8192 + 4 * 256 + 8 * 4 * 2 * 64 * 16;
-            dim3 grid(((d->S + 255) / 256) * d->heads * d->Bo);
-            int rc;
-            if (masks) {
-                if ((rc = set_lds(attn_pp_kernel<true>, lds))) return rc;
-                LAUNCH(attn_pp_kernel<true>, grid, dim3(512), lds, s, *d);
-            } else {
-                if ((rc = set_lds(attn_pp_kernel<false>, lds))) return rc;
-                LAUNCH(attn_pp_kernel<false>, grid, dim3(512), lds, s, *d);
-            }
-            return check_launch("attn(ping-pong)");
-        }
-        if (D <= 64) return masks ? launch_attn<bf16, 64, 2, 64, 2, true>(s, *d) : launch_attn<bf16, 64, 2, 64, 2, false>(s, *d);
-        if (D <= 96) return masks ? launch_attn<bf16, 96, 2, 64, 1, true>(s, *d) : launch_attn<bf16, 96, 2, 64, 1, false>(s, *d);
-        if (D <= 160) return masks ? launch_attn<bf16, 160, 1, 64, 1, true>(s, *d) : launch_attn<bf16, 160, 1, 64, 1, false>(s, *d);
-    }
-    return fail(FFN_ENOSYS, "attn: head dim %d not supported (max 160; use the GEMM path)", D);
+    return fail(FFN_EINVAL, "attn: no kernel planned");
 }
 
 // ---- elementwise / resampling helpers of the depth front end ----------------------------------------------------------

@@ -499,16 +499,49 @@ class AttnEntrySpec:
                              self.kmask, self.qsel, self.flags, logical_row if self.hr_row is None else self.hr_row)
 
 
+def _set_entries(d, passes, b0, nb, ptr=_p):
+    """the (pass, row) entries of descriptor d from rows b0 .. b0 + nb of `passes` (ptr: tensor -> address)"""
+    for p, rows in enumerate(passes):
+        for b in range(nb):
+            sp = rows[b0 + b]
+            e = d.e[p * L.ATT_MAXB + b]
+            if sp is None:
+                e.w_const = e.w_slope = 0.0
+                continue
+            e.q_row, e.kv_row, e.w_const, e.w_slope = sp.q_row, sp.kv_row, sp.w_const, sp.w_slope
+            e.wq, e.kmask, e.qsel, e.flags = ptr(sp.wq), ptr(sp.kmask), ptr(sp.qsel), sp.flags
+            # the tiled-head rule defaults to the OUTPUT row index, which a row-range launch shifts by b0: pin it
+            hr = sp.hr_row if sp.hr_row is not None else (b0 + b if b0 else None)
+            e.hr_row = 0 if hr is None else hr + 1
+
+
+def _takes_kv_images(lib, d):
+    """whether the library runs split-bf16 descriptor d on pre-split K / V^T images (kv_pair = 1): it names a kernel instead of refusing"""
+    probe = L.AttnDesc.from_buffer_copy(d)
+    probe.kv_pair = 1
+    return lib.ffn_attn_kernel_name(L.FFN_BF16X3, CT.byref(probe), CT.create_string_buffer(160), 160) == 0
+
+
 def kv_images_ok(Dh, S, Sk, passes=None, nbytes=0):
     """split-bf16 self attention whose K / V^T projections may write the attention kernel's pre-split images themselves (linear(kv64_from=...),
-    attention(kv_images=True)): the shapes attn_x3w_kernel / attn_x3p_kernel take, a plan without degenerate uniform-softmax entries (those run on
-    attn_x3_kernel, which reads fp32 K / V^T), and buffers the kernels' 32-bit byte offsets reach (nbytes = the larger of the K and V^T buffers)"""
-    if not (_ATTN_PRESPLIT and _KV64 and Dh == 64 and Sk % 64 == 0 and S >= 128 and nbytes < 2 ** 31 - 65536):
+    attention(kv_images=True)): the library takes the plan's launches on the images (asked with probe descriptors: the kernel choice depends on the
+    shapes and on which entries are active, masked or flagged), and the buffers are within the kernels' 32-bit byte offsets (nbytes = the larger of
+    the K and V^T buffers)"""
+    if not (_ATTN_PRESPLIT and _KV64 and nbytes < 2 ** 31 - 65536):
         return False
-    for rows in passes or ():
-        for sp in rows:
-            if sp is not None and (sp.w_const != 0.0 or sp.w_slope != 0.0) and sp.kmask is not None and (sp.flags & (L.ATT_UNIFORM_SEL1 | L.ATT_UNIFORM_SEL0)):
-                return False
+    lib = L.load()
+    passes = passes or [[AttnEntrySpec(0, 0)]]
+    Bo = len(passes[0])
+    for b0 in range(0, Bo, L.ATT_MAXB):
+        nb = min(L.ATT_MAXB, Bo - b0)
+        d = L.AttnDesc()
+        d.Bo, d.S, d.Sk, d.heads, d.D, d.npass = nb, S, Sk, 1, Dh, len(passes)
+        d.ldq = d.ldk = d.ldo = Dh
+        d.ldvt = Sk
+        d.w_dev = 1                          # (a blend scalar is assumed present: the stricter answer for the short-key kernels)
+        _set_entries(d, passes, b0, nb, lambda t: 0 if t is None else 1)
+        if not _takes_kv_images(lib, d):
+            return False
     return True
 
 
@@ -571,32 +604,16 @@ def attention(q, k, vt, heads, scale, passes=None, *, Sk=None, out=None, w_dev=N
         d.out_pair = 1 if out_pair else 0
         d.scale, d.npass = scale, len(passes)
         d.kv_pair = 1 if kv_images else 0
-        for p, rows in enumerate(passes):
-            for b in range(nb):
-                sp = rows[b0 + b]
-                e = d.e[p * L.ATT_MAXB + b]
-                if sp is None:
-                    e.w_const = e.w_slope = 0.0
-                    continue
-                e.q_row, e.kv_row, e.w_const, e.w_slope = sp.q_row, sp.kv_row, sp.w_const, sp.w_slope
-                e.wq, e.kmask, e.qsel, e.flags = _p(sp.wq), _p(sp.kmask), _p(sp.qsel), sp.flags
-                # the tiled-head rule defaults to the OUTPUT row index, which a row-range launch shifts by b0: pin it
-                hr = sp.hr_row if sp.hr_row is not None else (b0 + b if b0 else None)
-                e.hr_row = 0 if hr is None else hr + 1
+        _set_entries(d, passes, b0, nb)
         descs.append((b0, nb, d))
-    # split-bf16 self attention on the ping-pong kernel: K / V^T are split ONCE per call into the bf16 images the kernel stages by LDS-DMA
-    # (ffn_attn_presplit; the kernel's 16 query-block workgroups per (row, head) otherwise each split the whole K / V^T in their key loops)
+    # split-bf16 self attention: K / V^T are split ONCE per call into the bf16 images attn_x3w_kernel stages by LDS-DMA (ffn_attn_presplit) where the
+    # library runs the launches on them; otherwise attn_x3p_kernel's 16 query-block workgroups per (row, head) each split the whole K / V^T in their key loops
     # (the images are addressed with 32-bit byte offsets: K / V^T beyond 2 GiB keep the in-kernel split instead of failing in ffn_attn)
     if kv_images:
         assert dcode == L.FFN_BF16X3 and kv_images_ok(Dh, S, Sk)
-    elif dcode == L.FFN_BF16X3 and _ATTN_PRESPLIT and Dh == 64 and Sk % 64 == 0 and S >= 128 and k.stride(2) == 1 and vt.stride(2) == 1 \
-            and k.stride(0) == Sk * k.stride(1) and vt.stride(0) == heads * Dh * vt.stride(1) and k.shape[0] * Sk * heads * 256 < 2 ** 31 - 65536:
-        nbuf = CT.create_string_buffer(160)
-        names = []
-        for _, _, d in descs:
-            lib.ffn_attn_kernel_name(dcode, CT.byref(d), nbuf, 160)
-            names.append(nbuf.value.decode())
-        if all("attn_x3p_kernel" in n_ for n_ in names):
+    elif dcode == L.FFN_BF16X3 and _ATTN_PRESPLIT and k.stride(2) == 1 and vt.stride(2) == 1 and k.stride(0) == Sk * k.stride(1) \
+            and vt.stride(0) == heads * Dh * vt.stride(1) and k.shape[0] * Sk * heads * Dh * 4 < 2 ** 31 - 65536:
+        if all(_takes_kv_images(lib, d) for _, _, d in descs):
             Bk = k.shape[0]
             kp = torch.empty(Bk, Sk, 2 * heads * Dh, dtype=torch.bfloat16, device=q.device)
             vp = torch.empty(Bk, heads * Dh, 2 * Sk, dtype=torch.bfloat16, device=q.device)

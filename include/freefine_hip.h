@@ -184,25 +184,27 @@ typedef struct ffn_attn_desc {
     int npass;
     int out_pair;       /* FFN_BF16X3 with D <= 64 only: out is the bf16 PAIR form [Bo][S][ldo] of rows of ldo/2 columns (layout: FFN_BF16X3 above), the A operand of
                            the to_out projection's FFN_BF16X3 GEMM; 0 = fp32 rows */
-    int kv_pair;        /* FFN_BF16X3 launches that run attn_x3p_kernel (ffn_attn_kernel_name with kv_pair = 0 says so) only: k / vt are the PRE-SPLIT bf16
-                           images ffn_attn_presplit (or a projection with FFN_IG_OUT_KV64) wrote: k[row][key] = heads blocks of [hi(64) | lo(64)], ldk * 4
-                           bytes from key to key; vt[row][head * 64 + d] = Sk / 64 blocks of [hi(64 keys) | lo(64 keys)], ldvt * 4 bytes from row to row
-                           (i.e. ldk / ldvt are what they would be for the fp32 tensors the images replace: heads * 64 / Sk when compact).  The launch runs
-                           attn_x3w_kernel (attention_x3w.h, round 6: one wave per SIMD on 32x32x16 MFMAs) or, with FFN_ATTN_X3W=0 in the environment,
-                           attn_x3p_kernel<., PAIRKV>; 0 = fp32 k / vt */
+    int kv_pair;        /* 1: k / vt are the PRE-SPLIT bf16 images ffn_attn_presplit (or a projection with FFN_IG_OUT_KV64) wrote: k[row][key] = heads blocks
+                           of [hi(64) | lo(64)], ldk * 4 bytes from key to key; vt[row][head * 64 + d] = Sk / 64 blocks of [hi(64 keys) | lo(64 keys)], ldvt * 4
+                           bytes from row to row (i.e. ldk / ldvt are what they would be for the fp32 tensors the images replace: heads * 64 / Sk when compact).
+                           Only for launches whose kernel reads the images: attn_x3w_kernel (attention_x3w.h: one wave per SIMD on 32x32x16 MFMAs), i.e.
+                           FFN_BF16X3 launches that run attn_x3p_kernel with kv_pair = 0.  ffn_attn and ffn_attn_kernel_name return FFN_EINVAL for any other
+                           (ask ffn_attn_kernel_name with kv_pair = 1 whether a descriptor qualifies); 0 = fp32 k / vt */
     ffn_attn_entry e[FFN_ATT_MAXP * FFN_ATT_MAXB]; /* entry (p,b) at p*FFN_ATT_MAXB + b */
 } ffn_attn_desc;
 int ffn_attn(void* stream, int dtype, const ffn_attn_desc* d);
-/* dtype FFN_BF16X3: q / k / vt / out are fp32 exactly as with FFN_F32; head sizes D <= 64 run attn_x3_kernel (attention_x3.h: both
+/* The kernel follows from the descriptor alone (ffn_attn_kernel_name names it):
+ * dtype FFN_BF16X3: q / k / vt / out are fp32 exactly as with FFN_F32; head sizes D <= 64 run attn_x3_kernel (attention_x3.h: both
  * products in split-bf16 arithmetic, three bf16 MFMAs per term, fp32 softmax) -- or, under attn_pp_kernel's preconditions (D = 64,
- * Sk % 64 == 0, S >= 128, no uniform-softmax entry), attn_x3p_kernel (attention_x3p.h: the same arithmetic in the ping-pong schedule;
- * FFN_ATTN_PP=0 disables it too); larger heads fall back to the exact fp32 kernel. */
+ * Sk % 64 == 0, S >= 128, no uniform-softmax entry), attn_x3p_kernel (attention_x3p.h: the same arithmetic in the ping-pong schedule)
+ * and, on pre-split K / V^T (kv_pair), attn_x3w_kernel; short unmasked key sequences (D = 64, Sk <= 96, fragment images of all passes
+ * within the LDS) run xattn_x3_kernel (attention_xx3.h); larger heads fall back to the exact fp32 kernel. */
 /* bf16 launches with D = 64, Sk % 64 == 0, S >= 128 and no degenerate (uniform-softmax) entry run attn_pp_kernel (attention_pp.h:
  * software-pipelined, 8 waves in two alternating groups); everything else attn_kernel (attention.h).  Same results up to fp32
- * summation order.  FFN_ATTN_PP=0 in the environment forces attn_kernel.
- * bf16 launches with D = 64, Sk <= 96 and ONE pass whose entries carry no key mask / selector / per-query weight (the text
- * cross-attention) run xattn_kernel (attention_x.h: K and V^T of a (row, head) in a wave's registers); FFN_ATTN_X=0 disables it. */
-/* fp32 K [rows][Sk][ldk] (heads * 64 columns) and V^T [rows][heads * 64][ldvt] -> the bf16 images attn_x3p_kernel stages by LDS-DMA when
+ * summation order.
+ * bf16 launches with D = 64, Sk <= 96 and active entries that carry no key mask / selector (the text cross-attention) run xattn_kernel
+ * (attention_x.h: K and V^T of a (row, head) in a wave's registers) for ONE pass of plain entries, else xattn_mp_kernel. */
+/* fp32 K [rows][Sk][ldk] (heads * 64 columns) and V^T [rows][heads * 64][ldvt] -> the bf16 images attn_x3w_kernel stages by LDS-DMA when
  * desc.kv_pair = 1: k_pair [rows][Sk][heads][hi(64) | lo(64)], vt_pair [rows][heads * 64][Sk / 64][hi(64 keys) | lo(64 keys)] (each as many bytes
  * as its fp32 source; Sk % 64 == 0, head dim 64).  Once per attention call: the kernel's 16 query-block workgroups per (row, head) otherwise each
  * split the whole K / V^T in their key loops (16-25 % of the launch).  Reference call sites: the self-attention of the hooked Attention.forward,

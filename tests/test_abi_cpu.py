@@ -148,6 +148,78 @@ def test_kv_images_eligibility_rules():
     assert not ops.kv_images_ok(64, 4096, 4096, None, 2 ** 31)
 
 
+def test_attention_kernel_choice_table():
+    """ffn_attn_kernel_name (nothing is launched: no GPU needed) spells the plan ffn_attn launches from: the kernel of every kind of descriptor,
+    ENOSYS for head dims beyond 160 (which ffn_attn refuses), EINVAL for kv_pair (pre-split K / V^T images) on a launch that does not run
+    attn_x3w_kernel -- and ops.kv_images_ok gives the library's answer for the split-bf16 kv_pair rows."""
+    import ctypes
+    from freefine_amd import _lib, ops
+    lib = _lib.load()
+    F32, BF16, X3 = _lib.FFN_F32, _lib.FFN_BF16, _lib.FFN_BF16X3
+    km = object()                                  # stands for a device tensor: only its presence reaches the descriptor
+    plain, masked, wq = ops.AttnEntrySpec(0, 0), ops.AttnEntrySpec(0, 0, kmask=km), ops.AttnEntrySpec(0, 0, wq=km)
+    uniform = ops.AttnEntrySpec(0, 0, 1.0, 0.0, kmask=km, flags=_lib.ATT_UNIFORM_SEL1)
+
+    def name(dtype, D, S, Sk, passes, kv_pair=0):
+        heads = 5
+        d = _lib.AttnDesc()
+        d.Bo, d.S, d.Sk, d.heads, d.D, d.npass, d.kv_pair = len(passes[0]), S, Sk, heads, D, len(passes), kv_pair
+        d.ldq = d.ldk = d.ldo = heads * D
+        d.ldvt = Sk
+        for p, rows in enumerate(passes):
+            for b, sp in enumerate(rows):
+                e = d.e[p * _lib.ATT_MAXB + b]
+                if sp is not None:
+                    e.q_row, e.kv_row, e.w_const, e.w_slope, e.flags = sp.q_row, sp.kv_row, sp.w_const, sp.w_slope, sp.flags
+                    e.kmask, e.wq = (0 if sp.kmask is None else 0x10000), (0 if sp.wq is None else 0x20000)
+        buf = ctypes.create_string_buffer(160)
+        rc = lib.ffn_attn_kernel_name(dtype, ctypes.byref(d), buf, 160)
+        return buf.value.decode() if rc == 0 else rc
+    rows = [
+        (F32, 40, 1024, 77, [[plain]], 0, "attn_kernel<float, 48, 2, 64, 1, true>"),
+        (F32, 64, 4096, 4096, [[masked]], 0, "attn_kernel<float, 64, 2, 64, 1, true>"),
+        (F32, 80, 1024, 77, [[plain]], 0, "attn_kernel<float, 80, 2, 64, 1, true>"),
+        (F32, 160, 1024, 77, [[plain]], 0, "attn_kernel<float, 160, 1, 32, 1, true>"),
+        (F32, 200, 1024, 77, [[plain]], 0, -38),
+        (X3, 80, 1024, 1024, [[plain]], 0, "attn_kernel<float, 80, 2, 64, 1, true>"),
+        (BF16, 64, 4096, 77, [[plain]], 0, "xattn_kernel<5>"),
+        (BF16, 64, 4096, 30, [[plain]], 0, "xattn_kernel<2>"),
+        (BF16, 64, 1024, 77, [[plain, wq]], 0, "xattn_mp_kernel<5>"),
+        (BF16, 64, 1024, 96, [[plain, None], [plain, plain]], 0, "xattn_mp_kernel<6>"),
+        (BF16, 64, 4096, 4096, [[plain]], 0, "attn_pp_kernel<false>"),
+        (BF16, 64, 4096, 4096, [[masked]], 0, "attn_pp_kernel<true>"),
+        (BF16, 64, 4096, 4096, [[uniform]], 0, "attn_kernel<bf16, 64, 2, 64, 2, true>"),
+        (BF16, 80, 1024, 77, [[plain]], 0, "attn_kernel<bf16, 96, 2, 64, 1, false>"),
+        (BF16, 160, 1024, 77, [[masked]], 0, "attn_kernel<bf16, 160, 1, 64, 1, true>"),
+        (BF16, 200, 1024, 77, [[plain]], 0, -38),
+        (X3, 64, 1024, 77, [[plain]], 0, "xattn_x3_kernel<5, 4>"),
+        (X3, 64, 4096, 77, [[plain]], 0, "xattn_x3_kernel<5, 8>"),
+        (X3, 64, 1024, 30, [[plain], [plain]], 0, "xattn_x3_kernel<2, 8>"),
+        (X3, 64, 4096, 4096, [[masked]], 0, "attn_x3p_kernel<true>"),
+        (X3, 64, 1024, 1024, [[plain]], 0, "attn_x3p_kernel<false>"),
+        (X3, 64, 1024, 77, [[masked]], 0, "attn_x3_kernel<true>"),
+        (X3, 40, 1024, 1024, [[plain]], 0, "attn_x3_kernel<false>"),
+        (X3, 64, 1024, 1024, [[uniform]], 0, "attn_x3_kernel<true>"),
+        (X3, 64, 4096, 4096, [[masked, plain], [plain, None]], 1, "attn_x3w_kernel<true>"),
+        (X3, 64, 128, 128, [[plain]], 1, "attn_x3w_kernel<false>"),
+        (X3, 64, 1024, 1024, [[uniform]], 1, -22),
+        (X3, 40, 4096, 4096, [[plain]], 1, -22),
+        (X3, 64, 4096, 77, [[plain]], 1, -22),
+        (X3, 64, 64, 128, [[plain]], 1, -22),
+        (X3, 64, 1024, 64, [[plain]], 1, -22),
+        (BF16, 64, 4096, 4096, [[plain]], 1, -22),
+        (F32, 200, 1024, 1024, [[plain]], 1, -22),
+    ]
+    for dtype, D, S, Sk, passes, kv_pair, want in rows:
+        got = name(dtype, D, S, Sk, passes, kv_pair)
+        assert (got == want) if isinstance(want, int) else (got == f"void {want}({'ffn_attn_desc, int, int' if 'xattn' in want else 'ffn_attn_desc'})"), \
+            (dtype, D, S, Sk, kv_pair, got, want)
+        if want == -22:
+            assert b"kv_pair" in lib.ffn_last_error(), lib.ffn_last_error()
+        if dtype == X3 and kv_pair:
+            assert ops.kv_images_ok(D, S, Sk, passes) == (got != -22), (D, S, Sk, got)
+
+
 def test_attention_row_split_minimises_resident_rounds():
     """ops.attn_row_split: rows per launch of a self-attention call on the one-workgroup-per-CU kernels (256 CUs): never more than FFN_ATT_MAXB, never more rounds
     than the fixed 16-row split, the documented cases, every row covered once."""

@@ -1213,13 +1213,11 @@ def test_ffn_attn_vs_reference_g1_fixture(gpu, mode):
 
 
 @pytest.mark.parametrize("S,heads,passes", [(4096, 5, 2), (1024, 10, 1), (256, 20, 2), (320, 5, 2)])
-def test_x3_attention_presplit_kv_is_bit_identical(gpu, monkeypatch, S, heads, passes):
-    """Split-bf16 self attention with K / V^T pre-split ONCE per call (ffn_attn_presplit: bf16 hi / lo images staged by LDS-DMA).
-    Round 5: attn_x3p_kernel<., PAIRKV = true> against the same kernel splitting the fp32 tiles inside its key loop -- same split values, MFMA order
-    and softmax, so the results agree BIT FOR BIT (FFN_ATTN_X3W=0 selects that kernel).  Round 6: attn_x3w_kernel (one wave per SIMD, 32x32x16 MFMAs,
-    the default for pre-split launches) reads the same images and agrees with it to fp32 summation order -- masked two-pass TCA tables (key mask,
-    query selector, tiled-head rule, device-scalar blend) and the plain pass, rings wrapping 64 / 16 / 4 / 5 times; fp64 check on the plain pass;
-    bit-for-bit repeatability of the new kernel."""
+def test_x3_attention_presplit_kv_matches_in_kernel_split(gpu, monkeypatch, S, heads, passes):
+    """Split-bf16 self attention with K / V^T pre-split ONCE per call (ffn_attn_presplit: bf16 hi / lo images staged by LDS-DMA) runs attn_x3w_kernel
+    (one wave per SIMD, 32x32x16 MFMAs); without the pre-split pass (fp32 K / V^T) attn_x3p_kernel splits the tiles inside its key loop.  The two agree
+    to fp32 summation order -- masked two-pass TCA tables (key mask, query selector, tiled-head rule, device-scalar blend) and the plain pass, rings
+    wrapping 64 / 16 / 4 / 5 times; fp64 check on the plain pass; bit-for-bit repeatability of attn_x3w_kernel."""
     import ctypes
     from freefine_amd import _lib, ops
     from freefine_amd._lib import ATT_HEAD_RULE
@@ -1241,27 +1239,24 @@ def test_x3_attention_presplit_kv_is_bit_identical(gpu, monkeypatch, S, heads, p
     for b in range(B):
         d.e[b].q_row, d.e[b].kv_row, d.e[b].w_const = b, b, 1.0
     name = ctypes.create_string_buffer(160)
-    monkeypatch.setenv("FFN_ATTN_X3W", "0")
+    d.kv_pair = 0
     _lib.load().ffn_attn_kernel_name(_lib.FFN_BF16X3, ctypes.byref(d), name, 160)
-    assert b"attn_x3p_kernel<false, true>" in name.value, name.value
-    outs = {}
-    for pre in (True, False):
-        monkeypatch.setattr(ops, "_ATTN_PRESPLIT", pre)
-        outs[pre] = ops.attention(q, k, vt, heads, scale, P, w_dev=cg_dev, x3=True)
-    assert torch.equal(outs[True], outs[False])
-    monkeypatch.setenv("FFN_ATTN_X3W", "1")
-    monkeypatch.setattr(ops, "_ATTN_PRESPLIT", True)
+    assert b"attn_x3p_kernel<false>" in name.value, name.value
+    monkeypatch.setattr(ops, "_ATTN_PRESPLIT", False)
+    op = ops.attention(q, k, vt, heads, scale, P, w_dev=cg_dev, x3=True)
+    d.kv_pair = 1
     _lib.load().ffn_attn_kernel_name(_lib.FFN_BF16X3, ctypes.byref(d), name, 160)
     assert b"attn_x3w_kernel<false>" in name.value, name.value
+    monkeypatch.setattr(ops, "_ATTN_PRESPLIT", True)
     ow = ops.attention(q, k, vt, heads, scale, P, w_dev=cg_dev, x3=True)
-    e = relerr(ow, outs[True].double())
-    print(f"attn_x3w vs attn_x3p (pre-split images) S={S} h={heads} passes={passes}: {e:.2e}")
+    e = relerr(ow, op.double())
+    print(f"attn_x3w (pre-split images) vs attn_x3p (in-kernel split) S={S} h={heads} passes={passes}: {e:.2e}")
     assert e < 1e-5
     for _ in range(3):
         assert torch.equal(ops.attention(q, k, vt, heads, scale, P, w_dev=cg_dev, x3=True), ow)
     if passes == 1:
         ref = torch.stack([_ref_attention_gpu(q[b].double(), k[b].double(), v[b].double(), heads, scale) for b in range(B)])
-        assert relerr(outs[True], ref) < X3_TOL and relerr(ow, ref) < X3_TOL
+        assert relerr(op, ref) < X3_TOL and relerr(ow, ref) < X3_TOL
 
 
 @pytest.mark.parametrize("tuned", [False, True])

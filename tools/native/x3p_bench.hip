@@ -25,19 +25,9 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(dm, hm.data(), S, hipMemcpyHostToDevice)); CK(hipMemcpy(dsel, hs.data(), S, hipMemcpyHostToDevice));
     const float cg = 0.4f; CK(hipMemcpy(dw, &cg, 4, hipMemcpyHostToDevice));
     const bool masks = passes > 1;
-    const bool pairkv = getenv("X3P_PAIRKV") && atoi(getenv("X3P_PAIRKV"));       // pre-split K / V^T images + LDS-DMA staging (the shipped path)
-    bf16 *dkp = nullptr, *dvp = nullptr;
-    if (pairkv) {
-        CK(hipMalloc(&dkp, n * 4)); CK(hipMalloc(&dvp, n * 4));
-        const long nk = (long)B * S * heads * 8;
-        hipLaunchKernelGGL(attn_presplit_k_kernel, dim3(4096), dim3(256), 0, 0, dk, dkp, nk, heads, C);
-        hipLaunchKernelGGL(attn_presplit_vt_kernel, dim3(4096), dim3(256), 0, 0, dv, dvp, nk, S / 64, S);
-        CK(hipDeviceSynchronize());
-    }
     auto run = [&](int b0, int nb) {
         ffn_attn_desc d; memset(&d, 0, sizeof(d));
-        d.q = dq; d.k = pairkv ? (const void*)dkp : (const void*)dk; d.vt = pairkv ? (const void*)dvp : (const void*)dv; d.out = dout + (size_t)b0 * S * C; d.w_dev = dw;
-        d.kv_pair = pairkv;
+        d.q = dq; d.k = dk; d.vt = dv; d.out = dout + (size_t)b0 * S * C; d.w_dev = dw;
         d.Bo = nb; d.S = S; d.Sk = S; d.heads = heads; d.D = D; d.ldq = C; d.ldk = C; d.ldvt = S; d.ldo = C; d.scale = 0.125f; d.npass = passes;
         for (int b = 0; b < nb; ++b) {
             if (passes == 1) { d.e[b].q_row = b0 + b; d.e[b].kv_row = b0 + b; d.e[b].w_const = 1.f; }
@@ -48,11 +38,6 @@ int main(int argc, char** argv) {
         }
         constexpr int lds = 5 * (2 * 8192) + 8 * 4 * 2 * 64 * 16;
         dim3 grid(((S + 255) / 256) * heads * nb);
-        if (pairkv) {
-            if (masks) { CK(hipFuncSetAttribute((const void*)attn_x3p_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + 512)); hipLaunchKernelGGL((attn_x3p_kernel<true, true>), grid, dim3(512), lds + 512, 0, d); }
-            else { CK(hipFuncSetAttribute((const void*)attn_x3p_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + 512)); hipLaunchKernelGGL((attn_x3p_kernel<false, true>), grid, dim3(512), lds + 512, 0, d); }
-            return;
-        }
         if (masks) { CK(hipFuncSetAttribute((const void*)attn_x3p_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); hipLaunchKernelGGL(attn_x3p_kernel<true>, grid, dim3(512), lds, 0, d); }
         else { CK(hipFuncSetAttribute((const void*)attn_x3p_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); hipLaunchKernelGGL(attn_x3p_kernel<false>, grid, dim3(512), lds, 0, d); }
     };
@@ -68,6 +53,6 @@ int main(int argc, char** argv) {
         float t; CK(hipEventElapsedTime(&t, e0, e1)); t = t * 1e3f / reps;
         if (t < best) best = t;
     }
-    printf("pairkv=%d X3P_ABL=%d rows %d S %d heads %d passes %d: %.1f us  %.0f TFLOP/s nominal (%.2f of 833)\n", (int)pairkv, X3P_ABL, B, S, heads, passes, best, flops / best * 1e-6, flops / best * 1e-6 / 833.3);
+    printf("X3P_ABL=%d rows %d S %d heads %d passes %d: %.1f us  %.0f TFLOP/s nominal (%.2f of 833)\n", X3P_ABL, B, S, heads, passes, best, flops / best * 1e-6, flops / best * 1e-6 / 833.3);
     return 0;
 }

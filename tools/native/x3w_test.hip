@@ -1,4 +1,5 @@
-// Correctness + timing harness for attn_x3w_kernel (attention_x3w.h) against an fp64 statement of the pass table and against attn_x3p_kernel -- no torch.
+// Correctness + timing harness for attn_x3w_kernel (attention_x3w.h) against an fp64 statement of the pass table and against attn_x3p_kernel (fp32 K / V^T,
+// split in its key loop) -- no torch.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DX3W_ABL=n] -o build/native/x3w_test tools/native/x3w_test.hip
 //   ./x3w_test check                      small cases (ragged S, odd tile counts, masks + selectors + head rule, multi-pass, pair output) vs fp64
 //   ./x3w_test time rows S heads passes   random fp32 operands, both kernels interleaved in one process
@@ -127,15 +128,15 @@ static ffn_attn_desc desc_for(const Problem& P, int b0, int nb, bool pair, int v
     }
     return d;
 }
-constexpr int LDS_P = 5 * (2 * 8192) + 8 * 4 * 2 * 64 * 16 + 512;
+constexpr int LDS_P = 5 * (2 * 8192) + 8 * 4 * 2 * 64 * 16;
 constexpr int LDS_W = 6 * 8192 + 2 * 16384 + 1024 + 65536;
 static void run_p(const Problem& P, int variant, float* out) {
     for (int b0 = 0; b0 < P.B; b0 += 16) {
         const int nb = std::min(16, P.B - b0);
-        ffn_attn_desc d = desc_for(P, b0, nb, true, variant); d.out = out + (size_t)b0 * P.S * P.C;
+        ffn_attn_desc d = desc_for(P, b0, nb, false, variant); d.out = out + (size_t)b0 * P.S * P.C;
         dim3 grid(((P.S + 255) / 256) * P.heads * nb);
-        if (P.passes > 1) { CK(hipFuncSetAttribute((const void*)attn_x3p_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_P)); hipLaunchKernelGGL((attn_x3p_kernel<true, true>), grid, dim3(512), LDS_P, 0, d); }
-        else { CK(hipFuncSetAttribute((const void*)attn_x3p_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_P)); hipLaunchKernelGGL((attn_x3p_kernel<false, true>), grid, dim3(512), LDS_P, 0, d); }
+        if (P.passes > 1) { CK(hipFuncSetAttribute((const void*)attn_x3p_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_P)); hipLaunchKernelGGL(attn_x3p_kernel<true>, grid, dim3(512), LDS_P, 0, d); }
+        else { CK(hipFuncSetAttribute((const void*)attn_x3p_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_P)); hipLaunchKernelGGL(attn_x3p_kernel<false>, grid, dim3(512), LDS_P, 0, d); }
     }
 }
 static void run_w(const Problem& P, int variant, float* out) {
