@@ -69,7 +69,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 1; }
+extern "C" int ffn_version(void) { return 2; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -963,7 +963,7 @@ extern "C" int ffn_igemm(void* stream, int dtype, const ffn_igemm_desc* d) {
     }
     if (d->flags & FFN_IG_OUT_KV64) {
         REQUIRE(dtype == FFN_BF16X3 && !d->conv && !d->residual && !d->rowbias && d->splitk <= 1 &&
-                    !(d->flags & (FFN_IG_GEGLU | FFN_IG_OUT_PAIR | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU)),
+                    !(d->flags & (FFN_IG_GEGLU | FFN_IG_OUT_PAIR | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU)),
                 "igemm: FFN_IG_OUT_KV64 needs FFN_BF16X3, dense A, the plain epilogue and no forced split-K");
         if (d->flags & FFN_IG_OUT_TRANSPOSED) REQUIRE(d->rows_per_batch % 64 == 0 && d->M % d->rows_per_batch == 0 && d->ldo >= d->rows_per_batch && d->ldo % 64 == 0,
                                                       "igemm: KV64 transposed output needs rows_per_batch %% 64 == 0, whole batches, ldo %% 64 == 0 (rows_per_batch=%d, ldo=%d)", d->rows_per_batch, d->ldo);
@@ -972,7 +972,7 @@ extern "C" int ffn_igemm(void* stream, int dtype, const ffn_igemm_desc* d) {
     }
     if (d->flags & FFN_IG_OUT_TRANSPOSED) {
         REQUIRE(d->ldo % 4 == 0, "igemm: transposed ldo=%d must be a multiple of 4", d->ldo);
-        REQUIRE(!(d->flags & (FFN_IG_GEGLU | FFN_IG_OUT_F32 | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU)) && !d->residual && !d->rowbias,
+        REQUIRE(!(d->flags & (FFN_IG_GEGLU | FFN_IG_OUT_F32 | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU)) && !d->residual && !d->rowbias,
                 "igemm: transposed output supports bias only");
     } else {
         REQUIRE(d->N % 4 == 0 && d->ldo % 4 == 0, "igemm: N=%d and ldo=%d must be multiples of 4", d->N, d->ldo);
@@ -987,12 +987,12 @@ extern "C" int ffn_igemm(void* stream, int dtype, const ffn_igemm_desc* d) {
         }
         if (d->flags & FFN_IG_GEGLU) {
             REQUIRE(d->N % 64 == 0, "igemm: GEGLU needs N %% 64 == 0 (N=%d)", d->N);
-            REQUIRE(!d->residual && !d->rowbias && !(d->flags & (FFN_IG_OUT_F32 | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU)), "igemm: GEGLU epilogue is exclusive");
+            REQUIRE(!d->residual && !d->rowbias && !(d->flags & (FFN_IG_OUT_F32 | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU)), "igemm: GEGLU epilogue is exclusive");
         }
     }
     {
-        const int act = d->flags & (FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU);
-        REQUIRE((act & (act - 1)) == 0, "igemm: SILU / GELU / RELU are mutually exclusive");
+        const int act = d->flags & (FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU);
+        REQUIRE((act & (act - 1)) == 0, "igemm: SILU / GELU / QGELU / RELU are mutually exclusive");
     }
     if (d->ws) REQUIRE(aligned16(d->ws) && d->ws_bytes >= 0, "igemm: workspace must be 16-byte aligned");
     REQUIRE(d->splitk >= 0, "igemm: splitk must be >= 0");
@@ -1035,8 +1035,12 @@ static_assert(attn_kernel_lds(4, 160, 1, 32) <= 160 * 1024 && attn_kernel_lds(2,
 typedef void (*attn_x3w_t)(ffn_attn_desc);
 extern "C" __attribute__((visibility("hidden"))) attn_x3w_t fx3w_kernel(int masks);
 extern "C" __attribute__((visibility("hidden"))) int fx3w_lds_bytes(void);
+// attn_causal_kernel and embed_tokens_kernel live in a third one (attn_causal.hip)
+extern "C" __attribute__((visibility("hidden"))) attn_x3w_t fcausal_kernel(int dtype);
+extern "C" __attribute__((visibility("hidden"))) void fembed_launch(hipStream_t s, int bf16_out, const int* ids, const float* table, const float* pos, void* out,
+                                                                    long M, int S, int C, int V);
 
-enum AttnKind { ATT_KERNEL, ATT_PP, ATT_X, ATT_X_MP, ATT_X3, ATT_X3P, ATT_X3W, ATT_XX3 };
+enum AttnKind { ATT_KERNEL, ATT_PP, ATT_X, ATT_X_MP, ATT_X3, ATT_X3P, ATT_X3W, ATT_XX3, ATT_CAUSAL_K };
 struct AttnPlan {
     AttnKind kind;
     bool f32;           // ATT_KERNEL: fp32 (else bf16) operands
@@ -1055,14 +1059,19 @@ struct AttnPlan {
 //   FFN_BF16: xattn_kernel / xattn_mp_kernel (attention_x.h) for short unmasked key sequences; attn_pp_kernel (attention_pp.h) on the
 //     ping-pong preconditions; else attn_kernel (attention.h).
 //   FFN_F32, and FFN_BF16X3 with larger heads: the exact fp32 attn_kernel.
+//   Any dtype, an active entry carrying FFN_ATT_CAUSAL: attn_causal_kernel (attention_causal.h) under the flag's preconditions, FFN_EINVAL outside them; a
+//     descriptor without the flag never reaches that branch.
 // FFN_EINVAL: kv_pair for a launch that does not run attn_x3w_kernel; FFN_ENOSYS: head dim beyond 160.
 static int attn_plan(int dtype, const ffn_attn_desc& d, AttnPlan* p) {
     bool masks = false, uniform = false, xok = true, multi = d.npass != 1;
+    bool causal = false, causal_ok = true;
     int maxq = 0, maxkv = 0;
     for (int pi = 0; pi < d.npass; ++pi)
         for (int b = 0; b < d.Bo; ++b) {
             const ffn_attn_entry& e = d.e[pi * FFN_ATT_MAXB + b];
             if (e.w_const == 0.f && e.w_slope == 0.f) { multi = true; continue; }
+            causal |= (e.flags & FFN_ATT_CAUSAL) != 0;
+            causal_ok &= (e.flags & FFN_ATT_CAUSAL) && !e.kmask && !e.qsel && !e.wq && e.w_slope == 0.f;
             masks |= e.kmask != nullptr;
             uniform |= e.kmask != nullptr && (e.flags & (FFN_ATT_UNIFORM_SEL1 | FFN_ATT_UNIFORM_SEL0));
             xok &= !e.kmask && !e.qsel && (e.w_slope == 0.f || d.w_dev);      // (flags only qualify a key mask)
@@ -1081,6 +1090,15 @@ static int attn_plan(int dtype, const ffn_attn_desc& d, AttnPlan* p) {
         return need <= 2 ? 2 : (need <= 5 ? 5 : 6);
     };
     *p = AttnPlan{};
+    if (causal) {
+        REQUIRE(causal_ok && d.npass == 1 && d.S == d.Sk && d.Sk <= 96 && d.D == 64 && !d.kv_pair && d.scale > 0.f,
+                "attn: FFN_ATT_CAUSAL needs S == Sk <= 96, D = 64, one pass, kv_pair = 0, scale > 0 and on every active entry the flag and no kmask / qsel / wq / "
+                "w_slope (S=%d, Sk=%d, D=%d, npass=%d, kv_pair=%d)", d.S, d.Sk, d.D, d.npass, d.kv_pair);
+        p->kind = ATT_CAUSAL_K;
+        p->grid = dim3(d.Bo * d.heads);                        // one workgroup per (row, head), one wave per 16 queries
+        p->block = dim3(64 * ((d.S + 15) / 16));
+        return FFN_OK;
+    }
     p->masks = masks;
     p->grid = dim3(((d.S + 255) / 256) * d.heads * d.Bo);      // the 256-query workgroups of the ping-pong and split-bf16 kernels
     p->block = dim3(512);
@@ -1174,6 +1192,7 @@ extern "C" int ffn_attn_kernel_name(int dtype, const ffn_attn_desc* d, char* buf
     case ATT_X3P: snprintf(buf, len, "void attn_x3p_kernel<%s>(ffn_attn_desc)", m); break;
     case ATT_X3W: snprintf(buf, len, "void attn_x3w_kernel<%s>(ffn_attn_desc)", m); break;
     case ATT_XX3: snprintf(buf, len, "void xattn_x3_kernel<%d, %d>(ffn_attn_desc, int, int)", p.nkf, p.nw); break;
+    case ATT_CAUSAL_K: snprintf(buf, len, "void attn_causal_kernel<%s, %s>(ffn_attn_desc)", dtype == FFN_BF16 ? "bf16" : "float", dtype == FFN_BF16X3 ? "true" : "false"); break;
     }
     return FFN_OK;
 }
@@ -1233,6 +1252,7 @@ extern "C" int ffn_attn(void* stream, int dtype, const ffn_attn_desc* d) {
     case ATT_X3: return p.masks ? attn_launch(p, attn_x3_kernel<true>, s, *d) : attn_launch(p, attn_x3_kernel<false>, s, *d);
     case ATT_X3P: return p.masks ? attn_launch(p, attn_x3p_kernel<true>, s, *d) : attn_launch(p, attn_x3p_kernel<false>, s, *d);
     case ATT_X3W: return attn_launch(p, fx3w_kernel(p.masks), s, *d);
+    case ATT_CAUSAL_K: return attn_launch(p, fcausal_kernel(dtype), s, *d);
     case ATT_XX3:
         if (p.nw == 8)
             return p.nkf == 2 ? attn_launch(p, xattn_x3_kernel<2, 8>, s, *d, wpp, bpw)
@@ -1241,6 +1261,15 @@ extern "C" int ffn_attn(void* stream, int dtype, const ffn_attn_desc* d) {
              : p.nkf == 5 ? attn_launch(p, xattn_x3_kernel<5, 4>, s, *d, wpp, bpw) : attn_launch(p, xattn_x3_kernel<6, 4>, s, *d, wpp, bpw);
     }
     return fail(FFN_EINVAL, "attn: no kernel planned");
+}
+
+// ---- token + position embedding of the text tower ------------------------------------------------------------------------
+extern "C" int ffn_embed_tokens(void* stream, int dtype, const int* ids, const float* table, const float* pos, void* out, long M, int S, int C, int V) {
+    REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16 || dtype == FFN_BF16X3, "embed_tokens: bad dtype %d", dtype);
+    REQUIRE(ids && table && pos && out && aligned16(table) && aligned16(pos) && aligned16(out), "embed_tokens: null / unaligned pointer");
+    REQUIRE(M > 0 && S > 0 && V > 0 && C > 0 && C % 4 == 0 && M < (1l << 31), "embed_tokens: bad shape M=%ld S=%d C=%d V=%d (C %% 4 == 0)", M, S, C, V);
+    fembed_launch(reinterpret_cast<hipStream_t>(stream), dtype == FFN_BF16, ids, table, pos, out, M, S, C, V);
+    return check_launch("embed_tokens");
 }
 
 // ---- elementwise / resampling helpers of the depth front end ----------------------------------------------------------

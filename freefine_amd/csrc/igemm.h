@@ -23,12 +23,13 @@
 
 enum { AMODE_DENSE = 0, AMODE_CONV3 = 1 };
 enum { IG_OUT_SILU = FFN_IG_OUT_SILU, IG_OUT_F32 = FFN_IG_OUT_F32, IG_GEGLU = FFN_IG_GEGLU, IG_OUT_TRANSPOSED = FFN_IG_OUT_TRANSPOSED, IG_OUT_PAIR = FFN_IG_OUT_PAIR,
-       IG_OUT_GELU = FFN_IG_OUT_GELU, IG_OUT_RELU = FFN_IG_OUT_RELU, IG_OUT_KV64 = FFN_IG_OUT_KV64 };
+       IG_OUT_GELU = FFN_IG_OUT_GELU, IG_OUT_RELU = FFN_IG_OUT_RELU, IG_OUT_KV64 = FFN_IG_OUT_KV64, IG_OUT_QGELU = FFN_IG_OUT_QGELU };
 // the plain epilogue's activation (flags are launch-uniform)
 __device__ __forceinline__ float ig_activation(float x, int flags) {
     if (flags & IG_OUT_SILU) return silu_exact(x);
     if (flags & IG_OUT_GELU) return gelu_erf(x);
     if (flags & IG_OUT_RELU) return fmaxf(x, 0.f);
+    if (flags & IG_OUT_QGELU) return x / (1.0f + expf(-1.702f * x));      // x * sigmoid(1.702 x): CLIP ViT-L's quick_gelu
     return x;
 }
 // four fp32 values, columns c .. c + 3 (c % 4 == 0) of a row of C -> the bf16 pair form of that row (common.h pair_pos), 8 bytes each
@@ -66,7 +67,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc
     float* __restrict__ outF = reinterpret_cast<float*>(p.out);
     const T* __restrict__ res = reinterpret_cast<const T*>(p.residual);
     const bool out_f32 = p.flags & IG_OUT_F32;
-    const bool out_act = p.flags & (IG_OUT_SILU | IG_OUT_GELU | IG_OUT_RELU);
+    const bool out_act = p.flags & (IG_OUT_SILU | IG_OUT_GELU | IG_OUT_RELU | IG_OUT_QGELU);
 
     if (SWAP && gridDim.y > 1) {
         // split-K partial: raw fp32 accumulators to slab blockIdx.y of the workspace

@@ -337,7 +337,7 @@ def _workspace(device):
     return ws
 
 def linear(x, w, bias=None, *, K=None, out=None, residual=None, rowbias=None, rows_per_batch=None, silu=False,
-           geglu=False, out_f32=False, transposed_ld=None, alpha=1.0, splitk=0, out_pair=False, gelu=False, relu=False, kv64_from=None):
+           geglu=False, out_f32=False, transposed_ld=None, alpha=1.0, splitk=0, out_pair=False, gelu=False, relu=False, kv64_from=None, qgelu=False):
     """out = x @ w[:, :K]^T (+bias ...).  x: [..., K] contiguous rows (M = prod of leading dims).
     kv64_from (split-bf16 only): the projection writes the attention kernels' pre-split K / V^T images itself (FFN_IG_OUT_KV64): row-major output --
     columns >= kv64_from of every row as [hi(64) | lo(64)] blocks per head in the bytes of their fp32 values; transposed output (any value, use 0) --
@@ -372,6 +372,8 @@ def linear(x, w, bias=None, *, K=None, out=None, residual=None, rowbias=None, ro
         flags |= L.IG_OUT_GELU
     if relu:
         flags |= L.IG_OUT_RELU
+    if qgelu:                                       # x * sigmoid(1.702 x): CLIP ViT-L's MLP
+        flags |= L.IG_OUT_QGELU
     if geglu:
         flags |= L.IG_GEGLU
         n_out = N // 2
@@ -398,7 +400,7 @@ def linear(x, w, bias=None, *, K=None, out=None, residual=None, rowbias=None, ro
     d.ldr = residual.shape[-1] if residual is not None else 0
     d.out = out.data_ptr()
     if kv64_from is not None:
-        assert x3 and residual is None and rowbias is None and not (silu or gelu or relu or geglu or out_pair)
+        assert x3 and residual is None and rowbias is None and not (silu or gelu or relu or qgelu or geglu or out_pair)
         flags |= L.IG_OUT_KV64
         d.kv64_from = int(kv64_from)
         splitk = 1
@@ -564,12 +566,13 @@ def attn_row_split(Bo, wg_per_row, maxb, cus):
     return best_n
 
 
-def attention(q, k, vt, heads, scale, passes=None, *, Sk=None, out=None, w_dev=None, Bo=None, C=None, x3=False, out_pair=False, kv_images=False):
+def attention(q, k, vt, heads, scale, passes=None, *, Sk=None, out=None, w_dev=None, Bo=None, C=None, x3=False, out_pair=False, kv_images=False, causal=False):
     """q: [Bq,S,C]; k: [Bk,Sk,C]; vt: [Bk,C,ldvt] (V transposed).  passes: list (per pass) of lists (per output
     row) of AttnEntrySpec or None (= skipped).  passes=None -> plain attention, row b uses its own K/V.
     More than FFN_ATT_MAXB output rows are issued as several launches over row ranges (entries name absolute Q/KV rows).
     kv_images (split-bf16 self attention): k / vt already ARE the pre-split images (written by their projections with kv64_from: fp32-typed tensors of
-    the shapes above whose bytes hold [hi(64) | lo(64)] blocks); the launches run with kv_pair = 1 and no ffn_attn_presplit pass."""
+    the shapes above whose bytes hold [hi(64) | lo(64)] blocks); the launches run with kv_pair = 1 and no ffn_attn_presplit pass.
+    causal: every term carries FFN_ATT_CAUSAL (key k allowed for query q iff k <= q; S == Sk <= 96, head dim 64, one pass of plain terms)."""
     lib = L.load()
     Bq, S, _ = q.shape
     Cq = C if C is not None else q.shape[2]          # q / k may be column views of a wider [B,S,ld] buffer
@@ -577,6 +580,9 @@ def attention(q, k, vt, heads, scale, passes=None, *, Sk=None, out=None, w_dev=N
     Dh = Cq // heads
     if passes is None:
         passes = [[AttnEntrySpec(b, b) for b in range(Bq)]]
+    if causal:
+        passes = [[None if sp is None else AttnEntrySpec(sp.q_row, sp.kv_row, sp.w_const, sp.w_slope, sp.wq, sp.kmask, sp.qsel, sp.flags | L.ATT_CAUSAL, sp.hr_row)
+                   for sp in rows] for rows in passes]
     Bo = Bo if Bo is not None else len(passes[0])
     out_pair = bool(out_pair and x3 and q.dtype == torch.float32 and Dh <= 64 and out is None and Cq % 8 == 0)
     if out_pair:                                     # the result as pair rows for the to_out projection's split-bf16 GEMM
@@ -902,6 +908,24 @@ def resize_bilinear(x, B, Hin, Win, Hout, Wout, relu=False):
     L.check(_timed("resize_bilinear_kernel", 0.0, (x.numel() + out.numel()) * x.element_size(),
                    lambda: lib.ffn_resize_bilinear(_stream(), _dt(x), x.data_ptr(), out.data_ptr(), B, Hin, Win, Hout, Wout, C_, 1 if relu else 0)),
             "ffn_resize_bilinear")
+    return out
+
+
+def embed_tokens(ids, table, pos, dtype, out=None):
+    """ids int32 [N, S] (device), table fp32 [V, C], pos fp32 [>= S, C] -> [N, S, C] of `dtype`: table[ids] + pos, added in fp32 (ffn_embed_tokens).
+    The caller has checked 0 <= id < V on the host."""
+    lib = L.load()
+    assert ids.dtype == torch.int32 and ids.is_contiguous() and table.dtype == pos.dtype == torch.float32 and table.is_contiguous() and pos.is_contiguous()
+    N, S = ids.shape
+    V, C = table.shape
+    assert pos.shape[0] >= S and pos.shape[1] == C
+    if out is None:
+        out = torch.empty(N, S, C, dtype=dtype, device=ids.device)
+    call = lambda: lib.ffn_embed_tokens(_stream(), _dt(out), ids.data_ptr(), table.data_ptr(), pos.data_ptr(), out.data_ptr(), N * S, S, C, V)
+    if _PROF is None:
+        L.check(call(), "ffn_embed_tokens")
+    else:
+        L.check(_timed(f"embed_tokens_kernel<{_tname(out)}>", 0.0, (4.0 + out.element_size()) * out.numel(), call), "ffn_embed_tokens")
     return out
 
 

@@ -23,7 +23,7 @@ from . import ops
 from .attention import Attention_Modulator
 from .config import UNetConfig, VAEConfig
 from .scheduler import DDIMScheduler
-from .text import ByteTokenizer, SyntheticTextEncoder
+from .text import ByteTokenizer, NativeTextSpec, SyntheticTextEncoder
 from .unet import HipUNet
 from .vae import HipVAE
 from .weights import load_safetensors_dir, normalize_state_dict, synthetic_state, unet_param_shapes, vae_param_shapes, validate_state_dict
@@ -81,7 +81,7 @@ class FreeFinePipeline:
     # construction (freefine_batch_infer_2d.py:148-157)
     # ------------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_pretrained(cls, path, torch_dtype=torch.float32, device="cuda:0", seed=0, broadcast=False, x3=False, fp8_conv=False, **kw):
+    def from_pretrained(cls, path, torch_dtype=torch.float32, device="cuda:0", seed=0, broadcast=False, x3=False, fp8_conv=False, native_text=False, **kw):
         """`path` is either a HF-layout Stable-Diffusion folder (unet/, vae/ safetensors + config.json; tokenizer/,
         text_encoder/ loaded through transformers when present) or "synthetic:<unet preset>[:<vae preset>]" for
         seeded random weights of that architecture (no checkpoints exist in the build environment).
@@ -92,12 +92,18 @@ class FreeFinePipeline:
         generates the UNet and VAE weights, every other rank of the default process group receives them over RCCL straight into device
         memory (freefine_amd.dist.broadcast_state; bf16 payload for the matrices in fast mode), so ALL ranks must call it with the same
         arguments ("auto": only when a process group with more than one rank is initialised).  The default (False) is the reference's
-        behaviour: every caller reads the checkpoint itself (freefine_batch_infer_2d.py:149), safe on a subset of ranks."""
-        ucfg, ust, vcfg, vst, tok, enc, sched, dtype = cls.components(path, torch_dtype, device, seed, broadcast)
+        behaviour: every caller reads the checkpoint itself (freefine_batch_infer_2d.py:149), safe on a subset of ranks.
+        `native_text` (checkpoint folders only; default False = transformers' CLIPTextModel as before): the text tower runs on the project's own kernels
+        (freefine_amd.text.HipCLIPTextEncoder, read from text_encoder/ without a transformers model class) in the pipeline's mode -- fp32, split-bf16 or bf16;
+        the tokenizer stays CLIPTokenizer.  Its embeddings are bit-identical per prompt whatever is encoded beside it, so `_encode_text` hands it all
+        missing prompts in one call."""
+        ucfg, ust, vcfg, vst, tok, enc, sched, dtype = cls.components(path, torch_dtype, device, seed, broadcast, native_text=native_text)
+        if isinstance(enc, NativeTextSpec):
+            enc = enc.build(dtype=dtype, device=device, x3=x3)
         return cls.from_state(ucfg, ust, vcfg, vst, tok, enc, sched, dtype, device, x3=x3, fp8_conv=fp8_conv)
 
     @classmethod
-    def components(cls, path, torch_dtype=torch.float32, device="cuda:0", seed=0, broadcast=False):
+    def components(cls, path, torch_dtype=torch.float32, device="cuda:0", seed=0, broadcast=False, native_text=False):
         """what `from_pretrained` hands to `from_state`: configs, host (or, after a broadcast, device-resident) parameter states, tokenizer, text
         encoder, scheduler, storage dtype -- without building the executors, so the whole loading / broadcasting path runs without a GPU."""
         from . import dist as FD
@@ -112,10 +118,12 @@ class FreeFinePipeline:
             if lead:
                 ust = synthetic_state(unet_param_shapes(ucfg), seed)
                 vst = synthetic_state(vae_param_shapes(vcfg), seed + 1)
+            if native_text:
+                raise ValueError("native_text needs a checkpoint folder with text_encoder/ (synthetic: pipelines use the byte-level stand-in encoder)")
             tok, enc = ByteTokenizer(), SyntheticTextEncoder(ucfg.cross_attention_dim)
             sched = DDIMScheduler()
         else:
-            ucfg, ust, vcfg, vst, tok, enc, sched = cls.load_folder(path, shared=shared, lead=lead)
+            ucfg, ust, vcfg, vst, tok, enc, sched = cls.load_folder(path, shared=shared, lead=lead, native_text=native_text)
         if shared:
             if lead:        # the shape tables are defined on normalised names: rename legacy VAE keys before the names travel
                 ust, vst = normalize_state_dict(ust), normalize_state_dict(vst)
@@ -158,7 +166,7 @@ class FreeFinePipeline:
         return out
 
     @classmethod
-    def load_folder(cls, path, shared=False, lead=True):
+    def load_folder(cls, path, shared=False, lead=True, native_text=False):
         """Everything `from_pretrained` reads from a HF-layout Stable-Diffusion folder, on the host: (UNetConfig, unet state, VAEConfig, vae state,
         tokenizer, text encoder, DDIMScheduler).  States are fp32 (fp16 / bf16 shards are up-cast), under current diffusers parameter names (the hub's
         legacy VAE attention names are renamed); with `shared` only the lead rank reads the tensors (the others get None) and the configs travel by
@@ -180,7 +188,8 @@ class FreeFinePipeline:
         sched = DDIMScheduler(**sc)
         from transformers import CLIPTextModel, CLIPTokenizer
         tok = CLIPTokenizer.from_pretrained(os.path.join(path, "tokenizer"))
-        enc = CLIPTextModel.from_pretrained(os.path.join(path, "text_encoder")).eval()
+        # native_text: the checked config + host state of the tower on the project's kernels (from_pretrained builds the executor in its mode)
+        enc = NativeTextSpec(path) if native_text else CLIPTextModel.from_pretrained(os.path.join(path, "text_encoder")).eval()
         if enc.config.hidden_size != ucfg.cross_attention_dim:
             raise ValueError(f"text encoder width {enc.config.hidden_size} != unet cross_attention_dim {ucfg.cross_attention_dim}")
         return ucfg, ust, vcfg, vst, tok, enc, sched

@@ -4,6 +4,8 @@ The reference tokenises with CLIP and calls `self.text_encoder(ids)[0]` (/root/r
 No CLIP weights exist in this environment, so synthetic runs use a deterministic byte-level stand-in with the same
 interface pair (tokenizer(prompts, padding=..., max_length=77, return_tensors="pt").input_ids ; text_encoder(ids)[0]
 -> [N,77,D]).  A real HF tokenizer/text-encoder pair can be plugged into FreeFinePipeline unchanged.
+
+HipCLIPTextEncoder (below) is the same interface on the project's own kernels: transformers' CLIPTextModel arithmetic without a library GEMM.
 """
 from types import SimpleNamespace
 
@@ -73,3 +75,171 @@ def clip_shaped_text_encoder(dim, seed=1234, layers=None):
     for q in enc.parameters():
         q.requires_grad_(False)
     return enc
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the CLIP text tower on the project's own kernels
+# ---------------------------------------------------------------------------------------------------------------------
+_TEXT_DEFAULTS = dict(hidden_act="quick_gelu", layer_norm_eps=1e-5, max_position_embeddings=77)      # transformers' CLIPTextConfig defaults
+_TEXT_FIELDS = ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "max_position_embeddings", "hidden_act",
+                "layer_norm_eps")
+TEXT_MAX_POSITIONS = 96            # the causal attention kernel holds a sequence's keys in six 16-key fragments
+
+
+def text_config(config):
+    """a CLIPTextConfig, or the dict of a checkpoint's text_encoder/config.json -> the fields the tower needs, checked: head dim 64 (the causal attention kernel's),
+    quick_gelu (CLIP ViT-L, SD-1.x) or erf-gelu (OpenCLIP ViT-H, SD-2.1) MLP.  Raises ValueError with the reason otherwise."""
+    get = (lambda k: config.get(k, _TEXT_DEFAULTS.get(k))) if isinstance(config, dict) else (lambda k: getattr(config, k, _TEXT_DEFAULTS.get(k)))
+    cfg = SimpleNamespace(**{k: get(k) for k in _TEXT_FIELDS})
+    missing = [k for k in _TEXT_FIELDS if getattr(cfg, k) is None]
+    if missing:
+        raise ValueError(f"text encoder config: missing {missing}")
+    C, nh = cfg.hidden_size, cfg.num_attention_heads
+    if C % nh != 0 or C // nh != 64:
+        raise ValueError(f"text encoder: head dim {C / nh:g} (hidden_size {C} / {nh} heads); the causal attention kernel is built for head dim 64")
+    if cfg.hidden_act not in ("quick_gelu", "gelu"):
+        raise ValueError(f"text encoder: hidden_act {cfg.hidden_act!r}; the GEMM epilogues carry 'quick_gelu' and 'gelu'")
+    if cfg.intermediate_size % 8 != 0:
+        raise ValueError(f"text encoder: intermediate_size {cfg.intermediate_size} must be a multiple of 8")
+    return cfg
+
+
+def pack_text_state(cfg, state):
+    """CLIPTextModel parameters (names with or without the hub files' `text_model.` prefix; `text_projection` and `position_ids` ignored) -> the fp32 host tensors
+    the tower uploads, in the packing of depth.py: q | k rows of one GEMM, V apart (its GEMM writes V^T).  Missing or mis-shaped parameters raise ValueError."""
+    st = {(k[len("text_model."):] if k.startswith("text_model.") else k): v for k, v in state.items()}
+    C, I = cfg.hidden_size, cfg.intermediate_size
+    want = {"embeddings.token_embedding.weight": (cfg.vocab_size, C), "embeddings.position_embedding.weight": (cfg.max_position_embeddings, C),
+            "final_layer_norm.weight": (C,), "final_layer_norm.bias": (C,)}
+    for i in range(cfg.num_hidden_layers):
+        p = f"encoder.layers.{i}."
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            want[p + f"self_attn.{n}.weight"], want[p + f"self_attn.{n}.bias"] = (C, C), (C,)
+        for n in ("layer_norm1", "layer_norm2"):
+            want[p + n + ".weight"], want[p + n + ".bias"] = (C,), (C,)
+        want[p + "mlp.fc1.weight"], want[p + "mlp.fc1.bias"], want[p + "mlp.fc2.weight"], want[p + "mlp.fc2.bias"] = (I, C), (I,), (C, I), (C,)
+    bad = [k for k, s in want.items() if k not in st or tuple(st[k].shape) != s]
+    if bad:
+        raise ValueError(f"text encoder state: missing or mis-shaped parameters {bad[:4]}{' ...' if len(bad) > 4 else ''}")
+    f = lambda k: st[k].detach().float().cpu().contiguous()
+    out = {"tok": f("embeddings.token_embedding.weight"), "pos": f("embeddings.position_embedding.weight"),
+           "lnf.w": f("final_layer_norm.weight"), "lnf.b": f("final_layer_norm.bias")}
+    for i in range(cfg.num_hidden_layers):
+        p, a = f"encoder.layers.{i}.", f"encoder.layers.{i}.self_attn."
+        out[f"{i}.ln1.w"], out[f"{i}.ln1.b"] = f(p + "layer_norm1.weight"), f(p + "layer_norm1.bias")
+        out[f"{i}.ln2.w"], out[f"{i}.ln2.b"] = f(p + "layer_norm2.weight"), f(p + "layer_norm2.bias")
+        out[f"{i}.qk.w"] = torch.cat([f(a + "q_proj.weight"), f(a + "k_proj.weight")], 0).contiguous()
+        out[f"{i}.qk.b"] = torch.cat([f(a + "q_proj.bias"), f(a + "k_proj.bias")], 0).contiguous()
+        out[f"{i}.v.w"], out[f"{i}.v.b"] = f(a + "v_proj.weight"), f(a + "v_proj.bias")
+        out[f"{i}.o.w"], out[f"{i}.o.b"] = f(a + "out_proj.weight"), f(a + "out_proj.bias")
+        out[f"{i}.fc1.w"], out[f"{i}.fc1.b"] = f(p + "mlp.fc1.weight"), f(p + "mlp.fc1.bias")
+        out[f"{i}.fc2.w"], out[f"{i}.fc2.b"] = f(p + "mlp.fc2.weight"), f(p + "mlp.fc2.bias")
+    return out
+
+
+class NativeTextSpec:
+    """what FreeFinePipeline.components reads from <path>/text_encoder for native_text=True: the checked config and the host state, no executor yet (the
+    pipeline's mode and device are from_pretrained's business) -- so the loading path runs without a GPU"""
+
+    def __init__(self, path):
+        from .weights import load_safetensors_dir
+        cfg, self.state = load_safetensors_dir(path, "text_encoder")
+        self.config = text_config(cfg)
+
+    def build(self, dtype=torch.float32, device="cuda:0", x3=False):
+        return HipCLIPTextEncoder(self.config, self.state, dtype=dtype, device=device, x3=x3)
+
+
+class HipCLIPTextEncoder:
+    """transformers' CLIPTextModel (`self.text_encoder(ids)[0]`, /root/reference/src/demo/model.py:536-567, 842-848) on the HIP kernels, the way depth.py runs its
+    ViT: every Linear an `ffn_igemm` (q | k in one GEMM, V^T from a transposed-output GEMM, residuals and the MLP activation in the epilogues), LayerNorm
+    `ffn_layernorm`, the causal self attention `ffn_attn` with FFN_ATT_CAUSAL, the token + position lookup `ffn_embed_tokens`.
+
+        x = tok[ids] + pos;  per layer: y = LN1(x); q, k, v = Linear(y); a = softmax(q k^T / 8 + causal) v per head; x += out_proj(a);
+        y = LN2(x); x += fc2(act(fc1(y)));  result final_layer_norm(x)                         (no padding mask: the reference passes none)
+
+    dtype float32 = parity mode (exact-fp32 MFMA), float32 with x3 = split-bf16, bfloat16 = fast mode.  The result is fp32 [N, S, C] on the device.
+
+    BIT-IDENTICAL PER PROMPT.  Tile choice and the bf16 tuner key on M, so prompts run in groups of GROUP rows (the last group zero-padded; rows are independent
+    in every op) with split-K off: a prompt's embedding does not depend on what is encoded beside it, and FreeFinePipeline._encode_text can hand all missing
+    prompts over in one call.  M = 77 * GROUP = 308 keeps the 192- and 256-row tiles eligible."""
+    GROUP = 4
+
+    def __init__(self, config, state, dtype=torch.float32, device="cuda:0", x3=False):
+        from . import ops
+        assert dtype in (torch.float32, torch.bfloat16) and not (x3 and dtype != torch.float32)
+        self.config = config if isinstance(config, SimpleNamespace) else text_config(config)
+        self.dtype, self.device, self.x3 = dtype, torch.device(device), bool(x3)
+        self.host = pack_text_state(self.config, state)
+        cfg, dev = self.config, self.device
+        up = lambda k: self.host[k].to(dev)
+        lin = lambda k: (ops.pack_linear(up(k + ".w"), dtype, x3=self.x3), up(k + ".b"))
+        self.tok, self.pos, self.lnf = up("tok"), up("pos"), (up("lnf.w"), up("lnf.b"))
+        self.blocks = []
+        for i in range(cfg.num_hidden_layers):
+            self.blocks.append(SimpleNamespace(ln1=(up(f"{i}.ln1.w"), up(f"{i}.ln1.b")), ln2=(up(f"{i}.ln2.w"), up(f"{i}.ln2.b")), qk=lin(f"{i}.qk"), v=lin(f"{i}.v"),
+                                               o=lin(f"{i}.o"), fc1=lin(f"{i}.fc1"), fc2=lin(f"{i}.fc2")))
+
+    @classmethod
+    def from_torch(cls, module, dtype=torch.float32, device="cuda:0", x3=False):
+        """from a transformers CLIPTextModel (its config and state_dict)"""
+        return cls(module.config, module.state_dict(), dtype=dtype, device=device, x3=x3)
+
+    @classmethod
+    def from_folder(cls, path, dtype=torch.float32, device="cuda:0", x3=False):
+        """from <path>/text_encoder/{config.json, *.safetensors} of a HF-layout Stable-Diffusion folder; no transformers model class is built"""
+        return NativeTextSpec(path).build(dtype=dtype, device=device, x3=x3)
+
+    def to(self, *a, **k):
+        return self
+
+    def _group(self, ids):
+        """ids int32 [GROUP, S] on the device -> final_layer_norm output [GROUP, S, C] in the activation type"""
+        from . import ops
+        cfg, x3 = self.config, self.x3
+        C, nh, eps = cfg.hidden_size, cfg.num_attention_heads, cfg.layer_norm_eps
+        S = ids.shape[1]
+        quick = cfg.hidden_act == "quick_gelu"
+        x = ops.embed_tokens(ids, self.tok, self.pos, self.dtype)
+        ld = (S + 7) // 8 * 8
+        # V^T [P, C, S'] of every layer goes through one buffer: its padding columns (S' > S) are zeroed once and no GEMM writes them
+        vt = torch.zeros(ids.shape[0], C, ld, dtype=self.dtype, device=self.device)
+        for b in self.blocks:
+            y = ops.layernorm(x, *b.ln1, eps=eps, pair=x3)
+            qk = ops.linear(y, b.qk[0], b.qk[1], K=C, splitk=1)                                               # [P, S, 2C]: q | k
+            ops.linear(y, b.v[0], b.v[1], K=C, rows_per_batch=S, transposed_ld=ld, splitk=1, out=vt)
+            a = ops.attention(qk, qk[..., C:], vt, nh, 0.125, None, Sk=S, C=C, x3=x3, out_pair=x3, causal=True)
+            x = ops.linear(a, b.o[0], b.o[1], K=C, residual=x, splitk=1)
+            y = ops.layernorm(x, *b.ln2, eps=eps, pair=x3)
+            h = ops.linear(y, b.fc1[0], b.fc1[1], K=C, gelu=not quick, qgelu=quick, out_pair=x3, splitk=1)
+            x = ops.linear(h, b.fc2[0], b.fc2[1], K=cfg.intermediate_size, residual=x, splitk=1)
+        return ops.layernorm(x, *self.lnf, eps=eps)
+
+    @torch.no_grad()
+    def __call__(self, input_ids, attention_mask=None, **kw):
+        """input_ids [N, S] (S <= 96 and <= max_position_embeddings) -> (last_hidden_state fp32 [N, S, C] on the device,).  Host ids are range-checked before upload;
+        device ids are taken as checked by whoever uploaded them (no synchronisation: the call is capturable; the lookup kernel reads no row outside the table)."""
+        if attention_mask is not None:
+            raise ValueError("HipCLIPTextEncoder takes no attention_mask (the reference passes none: padding tokens attend like any other)")
+        if kw:
+            raise ValueError(f"HipCLIPTextEncoder: unsupported arguments {sorted(kw)}")
+        ids = torch.as_tensor(input_ids)
+        if ids.ndim == 1:
+            ids = ids[None]
+        N, S = ids.shape
+        cfg = self.config
+        if S > TEXT_MAX_POSITIONS or S > cfg.max_position_embeddings:
+            raise ValueError(f"HipCLIPTextEncoder: {S} positions requested (at most {min(TEXT_MAX_POSITIONS, cfg.max_position_embeddings)})")
+        if not ids.is_cuda:
+            if N and (int(ids.min()) < 0 or int(ids.max()) >= cfg.vocab_size):
+                raise ValueError(f"HipCLIPTextEncoder: token ids outside [0, {cfg.vocab_size})")
+        ids = ids.to(self.device, torch.int32)
+        P, outs = self.GROUP, []
+        for g0 in range(0, N, P):
+            grp = ids[g0:g0 + P]
+            n = grp.shape[0]
+            if n < P:
+                grp = torch.cat([grp, torch.zeros(P - n, S, dtype=torch.int32, device=self.device)])
+            outs.append(self._group(grp.contiguous())[:n])
+        out = torch.cat(outs) if outs else torch.empty(0, S, cfg.hidden_size, device=self.device)
+        return (out.float(),)

@@ -63,8 +63,11 @@ enum {
                                        would occupy (columns below kv64_from stay fp32: the q half of the fused q | k projection; kv64_from and N %% 64 == 0).
                                        FFN_IG_OUT_TRANSPOSED: every run of 64 consecutive positions s of a row out[b][n][.] is stored as [hi(64) | lo(64)]
                                        (rows_per_batch %% 64 == 0).  Plain epilogue only (bias allowed), no split-K.  ffn_attn reads them with kv_pair = 1. */
-    FFN_IG_OUT_RELU = 1 << 6        /* out = max(acc + bias, 0) (+ residual): the DPT head's ResidualConvUnit / output convs (depth_anything/blocks.py:68-78,
-                                       dpt.py:93-98).  SILU / GELU / RELU are mutually exclusive and exclude GEGLU and the transposed output */
+    FFN_IG_OUT_RELU = 1 << 6,       /* out = max(acc + bias, 0) (+ residual): the DPT head's ResidualConvUnit / output convs (depth_anything/blocks.py:68-78,
+                                       dpt.py:93-98).  SILU / GELU / QGELU / RELU are mutually exclusive and exclude GEGLU and the transposed output */
+    FFN_IG_OUT_QGELU = 1 << 8       /* out = y * sigmoid(1.702 y), y = acc + bias (+ residual after it): the "quick_gelu" of CLIP ViT-L's MLP (SD-1.x text tower; transformers
+                                       activations.py QuickGELUActivation).  Same rules as FFN_IG_OUT_GELU, all three dtypes; runs on the generic tiles (the ping-pong
+                                       tiles' epilogue does not carry it) */
 };
 typedef struct ffn_igemm_desc {
     const void* A;        /* dense: [M][lda];  conv: NHWC input [B][Hin][Win][Cin] */
@@ -161,7 +164,10 @@ int ffn_igemm_kernel_name(int dtype, const ffn_igemm_desc* d, char* buf, int len
  * builders (src/utils/attention.py:774-1432) plus the plain branch of ca_forward (attention.py:394-404). */
 #define FFN_ATT_MAXP 4
 #define FFN_ATT_MAXB 16
-enum { FFN_ATT_HEAD_RULE = 1, FFN_ATT_UNIFORM_SEL1 = 2, FFN_ATT_UNIFORM_SEL0 = 4 };
+enum { FFN_ATT_HEAD_RULE = 1, FFN_ATT_UNIFORM_SEL1 = 2, FFN_ATT_UNIFORM_SEL0 = 4,
+       FFN_ATT_CAUSAL = 8 /* key k is allowed for query q iff k <= q (the CLIP text tower's self attention).  Accepted when S == Sk <= 96, D == 64, npass == 1,
+                             kv_pair == 0, scale > 0 and every active entry carries the flag and has no kmask / qsel / wq / w_slope; any other descriptor with the
+                             flag set returns FFN_EINVAL and launches nothing.  Runs attn_causal_kernel (attention_causal.h) in all three dtypes; out_pair as usual */ };
 typedef struct ffn_attn_entry {
     int q_row, kv_row;      /* batch rows supplying Q and K/V for this (pass, output row) */
     float w_const, w_slope; /* weight = w_const + w_slope * (*w_dev); both 0 -> entry skipped */
@@ -169,7 +175,8 @@ typedef struct ffn_attn_entry {
     const uint8_t* kmask;   /* per-key byte mask [Sk] or NULL */
     const uint8_t* qsel;    /* per-query selector [S] or NULL (=1): allowed(q,k) = (kmask[k]!=0) == (qsel[q]!=0) */
     int flags;              /* FFN_ATT_HEAD_RULE: mask applies only where (b*heads+head) is even (attention.py:859 vs 761);
-                               FFN_ATT_UNIFORM_SEL1/0: the allowed set for sel=1/0 is empty -> uniform over all keys */
+                               FFN_ATT_UNIFORM_SEL1/0: the allowed set for sel=1/0 is empty -> uniform over all keys;
+                               FFN_ATT_CAUSAL: see above */
     int hr_row;             /* 0: the tiled-head rule uses the OUTPUT row index; k>0: it uses row k-1 (row-deduplicated batches) */
 } ffn_attn_entry;
 typedef struct ffn_attn_desc {
@@ -210,6 +217,8 @@ int ffn_attn(void* stream, int dtype, const ffn_attn_desc* d);
  * split the whole K / V^T in their key loops (16-25 % of the launch).  Reference call sites: the self-attention of the hooked Attention.forward,
  * src/utils/attention.py:394-404, 1043-1091. */
 int ffn_attn_presplit(void* stream, const float* k, const float* vt, void* k_pair, void* vt_pair, int rows, int Sk, int heads, int ldk, int ldvt);
+/* Descriptors whose entries carry FFN_ATT_CAUSAL run attn_causal_kernel (attention_causal.h: one workgroup per (row, head), one wave per 16 queries, key
+ * fragments above the diagonal skipped) whatever the dtype; a descriptor without the flag is planned exactly as before the flag existed. */
 /* padded head dim / query fragments per wave of the instantiation ffn_attn dispatches for head dim D */
 int ffn_attn_variant(int dtype, int D, int* dp, int* qf);
 /* the kernel instantiation ffn_attn launches for this problem, spelled like rocprofv3's kernel trace */
@@ -315,6 +324,11 @@ int ffn_concat(void* stream, int dtype, const void* a, const void* b, void* out,
 int ffn_timestep_embed(void* stream, int dtype, const float* t_dev, const float* freq, void* out, int B, int half, int flip);
 int ffn_transpose(void* stream, int dtype, const void* src, void* dst, int B, int R, int C, int ld_src, int ld_dst);
 int ffn_cast(void* stream, int src_dtype, int dst_dtype, const void* src, void* dst, long n);
+/* Token + position embedding lookup of the CLIP text tower (transformers CLIPTextEmbeddings, reached from the reference's self.text_encoder(ids)[0],
+ * src/demo/model.py:536-567): out[m][:] = table[ids[m]][:] + pos[m % S][:], m < M, added in fp32 and stored in the activation type of `dtype` (FFN_F32 and
+ * FFN_BF16X3: fp32 rows -- a LayerNorm follows, no pair rows; FFN_BF16: bf16 rows).  ids int32 [M] in device memory, 0 <= id < V (the CALLER checks that on
+ * the host before upload; the kernel reads no table row outside [0, V)); table fp32 [V][C], pos fp32 [S][C], C % 4 == 0. */
+int ffn_embed_tokens(void* stream, int dtype, const int* ids, const float* table, const float* pos, void* out, long M, int S, int C, int V);
 int ffn_image_to_nhwc(void* stream, int dtype, const uint8_t* img, void* dst, long npix, int CP);
 int ffn_nhwc_to_image(void* stream, int dtype, const void* src, float* dst, int B, int HW, int ld);
 

@@ -88,7 +88,10 @@ def legacy_vae_names(state):
     return out
 
 
-def write(out, unet="tiny", vae="tiny", dtype="fp32", seed=0, prediction_type="epsilon", scheduler=True, text_width=None, text_layers=2):
+def write(out, unet="tiny", vae="tiny", dtype="fp32", seed=0, prediction_type="epsilon", scheduler=True, text_width=None, text_layers=2, text_heads=None,
+          text_act=None):
+    """text_heads / text_act: head count and MLP activation of the text encoder (defaults: width // 32 heads and the config class's default activation, as
+    always; text_heads = width // 64 gives the head dim 64 freefine_amd.text.HipCLIPTextEncoder runs)"""
     from safetensors.torch import save_file
     from transformers import CLIPTextConfig, CLIPTextModel, CLIPTokenizer
     from freefine_amd.config import UNetConfig, VAEConfig
@@ -118,8 +121,8 @@ def write(out, unet="tiny", vae="tiny", dtype="fp32", seed=0, prediction_type="e
     tok.save_pretrained(os.path.join(out, "tokenizer"))
     width = text_width or ucfg.cross_attention_dim
     tcfg = CLIPTextConfig(vocab_size=len(vocab), hidden_size=width, intermediate_size=2 * width, num_hidden_layers=text_layers,
-                          num_attention_heads=max(1, width // 32), max_position_embeddings=77, bos_token_id=vocab["<|startoftext|>"],
-                          eos_token_id=vocab["<|endoftext|>"], pad_token_id=vocab["<|endoftext|>"])
+                          num_attention_heads=text_heads or max(1, width // 32), max_position_embeddings=77, bos_token_id=vocab["<|startoftext|>"],
+                          eos_token_id=vocab["<|endoftext|>"], pad_token_id=vocab["<|endoftext|>"], **({"hidden_act": text_act} if text_act else {}))
     torch.manual_seed(seed + 2)
     CLIPTextModel(tcfg).eval().save_pretrained(os.path.join(out, "text_encoder"))
     return ucfg, vcfg, ust, vst
