@@ -95,7 +95,6 @@ SYMBOLS = {
     "ffn_igemm_tune_enable": (_i, [_i]),
     "ffn_igemm_num_configs": (_i, []),
     "ffn_igemm_force_config": (_i, [_i]),
-    "ffn_igemm_variant": (_i, [C.POINTER(IgemmDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ffn_igemm_kernel_name": (_i, [_i, C.POINTER(IgemmDesc), C.c_char_p, _i]),
     "ffn_attn_presplit": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "ffn_attn_variant": (_i, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

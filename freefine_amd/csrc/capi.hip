@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <initializer_list>
 #include <mutex>
 #include <unordered_map>
 #include <stdlib.h>
@@ -69,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 2; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens
+extern "C" int ffn_version(void) { return 3; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers)
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -90,14 +91,6 @@ extern "C" int ffn_graph_launch(void* stream, void* graph_exec) {
 }
 
 // ---- igemm -------------------------------------------------------------------------------------------------------
-static void igemm_plan_for(int dtype, const ffn_igemm_desc& d, int* bm, int* bn, int* splitk);
-static int igemm_stages_env() {
-    static const int v = [] {
-        const char* e = getenv("FFN_IGEMM_STAGES");     // 0/unset = heuristic, 1 = register-staged legacy loader, 2..4 = LDS ring depth
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
 static int device_cus() {
     static const int n = [] {
         int dev = 0, v = 0;
@@ -106,110 +99,16 @@ static int device_cus() {
     }();
     return n;
 }
-static bool persist_enabled() {
-    static const bool on = [] { const char* e = getenv("FFN_IGEMM_PERSIST"); return !(e && atoi(e) == 0); }();
-    return on;
-}
-// persist: the 2-stage glds kernels walk several output tiles per workgroup (igemm.h); launch only as many workgroups as are
-// co-resident (LDS / thread limits per CU) and let each stride over the tile list
-template <typename K>
-static int launch_igemm_kernel(K kern, int lds, hipStream_t s, const ffn_igemm_desc& d, int ntiles, int splitk, int threads = 256,
-                               bool persist = false) {
-    int rc = set_lds(kern, lds);
-    if (rc) return rc;
-    int gx = ntiles;
-    if (persist && persist_enabled()) {
-        int per_cu = (160 * 1024) / (lds > 0 ? lds : 1);
-        if (per_cu > 2048 / threads) per_cu = 2048 / threads;
-        if (per_cu < 1) per_cu = 1;
-        const int cap = (device_cus() * per_cu) / (splitk > 0 ? splitk : 1);
-        if (gx > cap && cap >= 8) gx = cap;
-    }
-    LAUNCH(kern, dim3(gx, splitk), dim3(threads), lds, s, d);
-    return check_launch("igemm");
-}
-static int igemm_waves_env() {
-    static const int v = [] {
-        const char* e = getenv("FFN_IGEMM_WAVES");      // 0/unset = heuristic, 4 or 8 waves per workgroup
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-// ring depth and waves per workgroup for a (tile, split) choice.  Measured on MI355X (tools/bench_kernels.py): occupancy beats
-// prefetch depth for these compiler-scheduled loops -- 2 workgroups/CU with a 2-deep ring win over 1 workgroup/CU with a 3-4 deep
-// ring by ~35%; on the 128x128 tile 8 waves (4 waves/SIMD) beat 4 waves by 5-30%, and 16 waves win once the K loop is short.
-static void igemm_exec_cfg(int dtype, const ffn_igemm_desc& d, int bm, int bn, int splitk, int* ns, int* nw) {
-    const int kstage = dtype == FFN_F32 ? 32 : 64;
-    const int nk = ((d.K + kstage - 1) / kstage + splitk - 1) / splitk;    // K stages per workgroup
-    *ns = igemm_stages_env();
-    *nw = igemm_waves_env();
-    if (*ns == 0) *ns = 2;
-    if (*nw == 0) *nw = (bm == 128 && bn == 128 && !d.conv && nk <= 24) ? 16 : 8;
-    if (*ns > 2 && nk < 3) *ns = 2;
-    if (bm == 64) *nw = 4;
-    if (bm == 128 && bn == 64 && *nw > 8) *nw = 8;
-    if (*ns == 1) *nw = 4;
-}
-template <typename T, int BM, int BN, int AMODE, bool SWAP>
-static int launch_igemm(hipStream_t s, const ffn_igemm_desc& d, int splitk) {
-    constexpr int stage = (BM + BN) * 128;
-    const int ntiles = ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
-    int ns, nw;
-    igemm_exec_cfg(sizeof(T) == 4 ? FFN_F32 : FFN_BF16, d, BM, BN, splitk, &ns, &nw);
-    int rc = FFN_OK;
-    bool done = false;
-    if constexpr (BM == 128 && BN == 128) {
-        if (nw == 8 && ns >= 2) {   // 8 waves (2x4) on the 128x128 tile: 2 waves/SIMD from ONE workgroup, so a deep ring fits the LDS
-            if (ns == 2) rc = launch_igemm_kernel(igemm_glds_kernel<T, BM, BN, AMODE, SWAP, 2, 2, 4>, 2 * stage, s, d, ntiles, splitk, 512);
-            else if (ns == 3) rc = launch_igemm_kernel(igemm_glds_kernel<T, BM, BN, AMODE, SWAP, 3, 2, 4>, 3 * stage, s, d, ntiles, splitk, 512);
-            else rc = launch_igemm_kernel(igemm_glds_kernel<T, BM, BN, AMODE, SWAP, 4, 2, 4>, 4 * stage, s, d, ntiles, splitk, 512);
-            done = true;
-        } else if (nw == 16) {   // experiment: 16 waves (4x4), 32x32 per wave
-            rc = launch_igemm_kernel(igemm_glds_kernel<T, BM, BN, AMODE, SWAP, 2, 4, 4>, 2 * stage, s, d, ntiles, splitk, 1024);
-            done = true;
-        }
-    }
-    if constexpr (BM == 128 && BN == 64) {
-        if (nw >= 8) {           // 8 waves (4x2), 32x32 per wave
-            rc = launch_igemm_kernel(igemm_glds_kernel<T, BM, BN, AMODE, SWAP, 2, 4, 2>, 2 * stage, s, d, ntiles, splitk, 512);
-            done = true;
-        }
-    }
-    if (!done) {
-        if (ns == 1) rc = launch_igemm_kernel(igemm_kernel<T, BM, BN, AMODE, SWAP>, 2 * stage, s, d, ntiles, splitk);
-        else if (ns == 3) rc = launch_igemm_kernel(igemm_glds_kernel<T, BM, BN, AMODE, SWAP, 3>, 3 * stage, s, d, ntiles, splitk);
-        else if (ns >= 4) rc = launch_igemm_kernel(igemm_glds_kernel<T, BM, BN, AMODE, SWAP, 4>, 4 * stage, s, d, ntiles, splitk);
-        else rc = launch_igemm_kernel(igemm_glds_kernel<T, BM, BN, AMODE, SWAP, 2>, 2 * stage, s, d, ntiles, splitk);
-    }
-    if (rc || splitk == 1) return rc;
-    const long nq = (long)d.M * (d.N / 4);
-    LAUNCH(igemm_splitk_reduce_kernel<T>, dim3(grid_for(nq)), dim3(256), 0, s, d, splitk);
-    return check_launch("igemm_splitk_reduce");
-}
-static void igemm_plan_for(int dtype, const ffn_igemm_desc& d, int* bm, int* bn, int* splitk);
-template <typename T, int AMODE, bool SWAP>
-static int dispatch_igemm_tile(hipStream_t s, const ffn_igemm_desc& d) {
-    // pick the largest tile that still gives the chip >= ~1 wave of workgroups (256 CUs, 2 workgroups/CU)
-    int bm, bn, sk;
-    igemm_plan_for(sizeof(T) == 4 ? FFN_F32 : FFN_BF16, d, &bm, &bn, &sk);
-    if (bm == 128 && bn == 128) return launch_igemm<T, 128, 128, AMODE, SWAP>(s, d, sk);
-    if (bm == 128) return launch_igemm<T, 128, 64, AMODE, SWAP>(s, d, sk);
-    return launch_igemm<T, 64, 64, AMODE, SWAP>(s, d, sk);
-}
 static bool can_split(const ffn_igemm_desc& d) {
     return d.ws && d.splitk != 1 && !(d.flags & (FFN_IG_GEGLU | FFN_IG_OUT_TRANSPOSED | FFN_IG_OUT_KV64));
 }
-// tile + number of K slices.  Without split-K small-M problems take small tiles to fill the chip; with it they keep the
-// 128x128 tile (operand reuse) and the K loop is cut so that ~2 workgroups per CU exist.
-static void igemm_plan_for(int dtype, const ffn_igemm_desc& d, int* bm, int* bn, int* splitk) {
+// the rule-based tile + number of K slices.  Without split-K small-M problems take small tiles to fill the chip (256 CUs, 2 workgroups/CU);
+// with it they keep the 128x128 tile (operand reuse) and the K loop is cut so that ~2 workgroups per CU exist.
+static void igemm_rule_for(int dtype, const ffn_igemm_desc& d, int* bm, int* bn, int* splitk) {
     const long t128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
     const long t12864 = (long)((d.M + 127) / 128) * ((d.N + 63) / 64);
     *splitk = 1;
-    static const char* tile_env = getenv("FFN_IGEMM_TILE");   // experiment: force 128x64 / 64x64 for dense problems
-    if (tile_env && !d.conv && !(d.flags & FFN_IG_GEGLU)) {
-        *bm = atoi(tile_env) >= 128 ? 128 : 64;
-        *bn = 64;
-    } else if (!d.conv && !(d.flags & FFN_IG_GEGLU) && d.M >= 128 && (!can_split(d) || t12864 >= 128)) {
+    if (!d.conv && !(d.flags & FFN_IG_GEGLU) && d.M >= 128 && (!can_split(d) || t12864 >= 128)) {
         *bm = 128; *bn = 64;      // dense Linear layers (short K, memory/latency bound): measured 5-25% faster than 128x128
     } else if (d.N > 64 && (t128 >= 256 || (can_split(d) && d.M > 512 && d.N >= 128))) {
         *bm = 128; *bn = 128;     // measured (tools/bench_kernels.py): from M = 1024 up, 128x128 + split-K beats 128x64 without it
@@ -229,16 +128,6 @@ static void igemm_plan_for(int dtype, const ffn_igemm_desc& d, int* bm, int* bn,
         *splitk = s;
     }
 }
-static void igemm_tile_for(const ffn_igemm_desc& d, int* bm, int* bn) {
-    int s;
-    igemm_plan_for(FFN_BF16, d, bm, bn, &s);
-}
-extern "C" int ffn_igemm_variant(const ffn_igemm_desc* d, int* bm, int* bn) {
-    REQUIRE(d && bm && bn, "igemm_variant: null argument");
-    igemm_tile_for(*d, bm, bn);
-    return FFN_OK;
-}
-
 
 // ---- bf16 tile configurations and first-use autotuning ------------------------------------------------------------------
 // The SD shapes span M = 4 ... 4M rows and N = 4 ... 10240 columns; which (tile, K-split) wins depends on how the tile count
@@ -322,144 +211,96 @@ static int halo_bytes_for(const ffn_igemm_desc& d, int bm) {
 }
 // X3 (split-bf16, FFN_BF16X3) problems run the generic 64x64 / 128x64 / 128x128 tiles (recomputing loader) and the ping-pong tiles
 static bool x3_cfg(int cfg) { return cfg == CFG_64x64 || cfg == CFG_128x64 || cfg == CFG_128x128_8 || is_pp_cfg(cfg); }
-template <int AMODE, bool X3 = false, bool F8 = false>
-static int launch_bf16_cfg(hipStream_t s, const ffn_igemm_desc& d, IgChoice ch) {
-    const IgCfgInfo& c = kCfg[ch.cfg];
-    if ((X3 || F8) && !x3_cfg(ch.cfg)) return fail(FFN_EINVAL, "igemm: configuration %d is not built for split-bf16 / fp8 problems", ch.cfg);
-    const int ntiles = ((d.M + c.bm - 1) / c.bm) * ((d.N + c.bn - 1) / c.bn);
-    const int lds = 2 * (c.bm + c.bn) * 128, threads = 64 * c.nwm * c.nwn;
-    int rc = FFN_OK;
-    // FASTK kernels (streaming loader) need every 128-byte K stage inside K / inside one conv tap
-    // the streaming loader's zero-page pointers (N-tail columns, rows past M, conv padding) walk 128 B per K stage over the WHOLE K
-    // range of the launch: K * 2 bytes must stay inside the 64 KiB zero page
-    const bool fastk = (d.conv ? d.Cin % 64 == 0 : d.K % 64 == 0) && (long)d.K * 2 + 256 <= (long)sizeof(g_zero_page);
-#define FFN_CFG_CASE(ID, BM_, BN_, WM_, WN_)                                                                                               \
-    case ID:                                                                                                                        \
-        if constexpr (X3) {                                                                                                         \
-            if constexpr (ID == CFG_64x64 || ID == CFG_128x64 || ID == CFG_128x128_8)                                               \
-                rc = launch_igemm_kernel(igemm_glds_kernel<bf16, BM_, BN_, AMODE, true, 2, WM_, WN_, false, true>, lds, s, d, ntiles, ch.splitk, threads, true); \
-        } else if constexpr (F8) {                                                                                                  \
-            if constexpr (AMODE == AMODE_CONV3 && (ID == CFG_64x64 || ID == CFG_128x64 || ID == CFG_128x128_8))                     \
-                rc = launch_igemm_kernel(igemm_glds_kernel<bf16, BM_, BN_, AMODE, true, 2, WM_, WN_, false, false, true>, lds, s, d, ntiles, ch.splitk, threads, true); \
-        } else {                                                                                                                    \
-            rc = fastk ? launch_igemm_kernel(igemm_glds_kernel<bf16, BM_, BN_, AMODE, true, 2, WM_, WN_, true>, lds, s, d, ntiles, ch.splitk, threads, true)  \
-                       : launch_igemm_kernel(igemm_glds_kernel<bf16, BM_, BN_, AMODE, true, 2, WM_, WN_, false>, lds, s, d, ntiles, ch.splitk, threads, true); \
-        }                                                                                                                           \
-        break;
-    switch (ch.cfg) {
-        FFN_CFG_CASE(CFG_64x64, 64, 64, 2, 2)
-        FFN_CFG_CASE(CFG_128x64, 128, 64, 4, 2)
-        FFN_CFG_CASE(CFG_128x128_8, 128, 128, 2, 4)
-        FFN_CFG_CASE(CFG_128x128_16, 128, 128, 4, 4)
-        FFN_CFG_CASE(CFG_256x128, 256, 128, 4, 4)
-        FFN_CFG_CASE(CFG_256x256, 256, 256, 4, 4)
-        FFN_CFG_CASE(CFG_128x320, 128, 320, 4, 4)
-        FFN_CFG_CASE(CFG_128x160, 128, 160, 4, 2)
-        FFN_CFG_CASE(CFG_192x320, 192, 320, 3, 4)      // 12 waves: 168 registers per wave (spills at 16 waves x 128)
-        case CFG_PP_256x320:
-        case CFG_PP_256x256:
-        case CFG_PP_192x320:
-        case CFG_PP_192x256:
-        case CFG_PP_256x128: {
-            if (!pp_ok(d, c.bm, c.bn, ch.splitk)) return fail(FFN_EINVAL, "igemm: ping-pong kernel not applicable");
-            const int pplds = 2 * (c.bm + c.bn) * 128 + 12288;
-            const int nt = ((d.M + c.bm - 1) / c.bm) * (d.N / c.bn) * ch.splitk;
-            const int grid = nt < device_cus() ? nt : device_cus();
-            (void)hipGetLastError();
-#define FFN_PP_LAUNCH(BM_, BN_, RES_, GEGLU_)                                              \
-    do {                                                                                   \
-        auto kern = igemm_pp_kernel<BM_, BN_, AMODE, RES_, (GEGLU_) && !F8, false, false, X3, F8>;      \
-        if ((rc = set_lds(kern, pplds))) return rc;                                        \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), pplds, s, d, 1);                   \
-    } while (0)
-#define FFN_PP_TILE(BM_)                                                                   \
-    do {                                                                                   \
-        if (c.bn == 320) {                                                                 \
-            if (d.residual) FFN_PP_LAUNCH(BM_, 320, true, false);                          \
-            else FFN_PP_LAUNCH(BM_, 320, false, false);                                    \
-        } else {                                                                           \
-            if constexpr (AMODE == AMODE_DENSE) {                                          \
-                if (d.flags & FFN_IG_GEGLU) FFN_PP_LAUNCH(BM_, 256, false, true);          \
-                else if (d.residual) FFN_PP_LAUNCH(BM_, 256, true, false);                 \
-                else FFN_PP_LAUNCH(BM_, 256, false, false);                                \
-            } else {                                                                       \
-                if (d.residual) FFN_PP_LAUNCH(BM_, 256, true, false);                      \
-                else FFN_PP_LAUNCH(BM_, 256, false, false);                                \
-            }                                                                              \
-        }                                                                                  \
-    } while (0)
-#define FFN_PP_SPLIT(BM_, BN_)                                                             \
-    do {                                                                                   \
-        auto kern = igemm_pp_kernel<BM_, BN_, AMODE, false, false, true, false, X3, F8>;   \
-        if ((rc = set_lds(kern, pplds))) return rc;                                        \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), pplds, s, d, ch.splitk);           \
-    } while (0)
-            if (c.bn == 128) {                 // (pp_ok: split-bf16 3x3 convolution, unsplit)
-                if constexpr (X3 && AMODE == AMODE_CONV3) {
-                    if (d.residual) FFN_PP_LAUNCH(256, 128, true, false);
-                    else FFN_PP_LAUNCH(256, 128, false, false);
-                    return check_launch("igemm(ping-pong, 256 x 128)");
-                } else {
-                    return fail(FFN_EINVAL, "igemm: the 256 x 128 ping-pong tile is built for split-bf16 3x3 convolutions");
-                }
-            }
-            if (ch.splitk > 1) {
-                if (c.bm == 256 && c.bn == 320) FFN_PP_SPLIT(256, 320);
-                else if (c.bm == 256) FFN_PP_SPLIT(256, 256);
-                else if (c.bn == 320) FFN_PP_SPLIT(192, 320);
-                else FFN_PP_SPLIT(192, 256);
-                if ((rc = check_launch("igemm(ping-pong, split-K)"))) return rc;
-                const long nq = (long)d.M * (d.N / 4);
-                if constexpr (X3) LAUNCH(igemm_splitk_reduce_kernel<float>, dim3(grid_for(nq)), dim3(256), 0, s, d, ch.splitk);
-                else LAUNCH(igemm_splitk_reduce_kernel<bf16>, dim3(grid_for(nq)), dim3(256), 0, s, d, ch.splitk);
-                return check_launch("igemm_splitk_reduce");
-            }
-            if (c.bm == 256) FFN_PP_TILE(256);
-            else FFN_PP_TILE(192);
-#undef FFN_PP_SPLIT
-#undef FFN_PP_TILE
-#undef FFN_PP_LAUNCH
-            return check_launch("igemm(ping-pong)");
-        }
-        case CFG_H_128x320:
-        case CFG_H_256x128:
-        case CFG_H_256x256:
-        case CFG_H_128x128:
-            if constexpr (AMODE == AMODE_CONV3 && !X3 && !F8) {
-                const int hb = halo_bytes_for(d, c.bm);
-                if (hb <= 0 || ch.splitk != 1) return fail(FFN_EINVAL, "igemm: halo kernel not applicable");
-                const int hlds = 2 * hb + 2 * c.bn * 128;
-                const int nt = (d.M / c.bm) * ((d.N + c.bn - 1) / c.bn);
-                (void)hipGetLastError();
-                if (ch.cfg == CFG_H_128x320) {
-                    auto kern = igemm_halo_kernel<bf16, 128, 320, 4, 4>;
-                    if ((rc = set_lds(kern, hlds))) return rc;
-                    hipLaunchKernelGGL(kern, dim3(nt), dim3(threads), hlds, s, d, hb);
-                } else if (ch.cfg == CFG_H_256x128) {
-                    auto kern = igemm_halo_kernel<bf16, 256, 128, 4, 4>;
-                    if ((rc = set_lds(kern, hlds))) return rc;
-                    hipLaunchKernelGGL(kern, dim3(nt), dim3(threads), hlds, s, d, hb);
-                } else if (ch.cfg == CFG_H_256x256) {
-                    auto kern = igemm_halo_kernel<bf16, 256, 256, 4, 4>;
-                    if ((rc = set_lds(kern, hlds))) return rc;
-                    hipLaunchKernelGGL(kern, dim3(nt), dim3(threads), hlds, s, d, hb);
-                } else {
-                    auto kern = igemm_halo_kernel<bf16, 128, 128, 4, 4>;
-                    if ((rc = set_lds(kern, hlds))) return rc;
-                    hipLaunchKernelGGL(kern, dim3(nt), dim3(threads), hlds, s, d, hb);
-                }
-                return check_launch("igemm(halo)");
-            } else {
-                return fail(FFN_EINVAL, "igemm: halo configurations are for 3x3 convolutions");
-            }
-        default: return fail(FFN_EINVAL, "igemm: bad configuration %d", ch.cfg);
+// the library's private view of a split-bf16 problem: the kernels and the tile / split-K logic see the VIRTUAL contraction 3K
+static ffn_igemm_desc x3_view(const ffn_igemm_desc& d) {
+    ffn_igemm_desc v = d;
+    v.x3 = d.x3 == 2 ? 2 : 1;          // operand layout: 1 = planes, 2 = 128-byte blocks [hi(32) | lo(32)] (include/freefine_hip.h)
+    v.f8 = 0;
+    v.K = 3 * d.K;
+    v.flags |= FFN_IG_OUT_F32;
+    return v;
+}
+// fp8 problems: the kernels and every tile / split-K decision see a bf16-SHAPED view (two e4m3 bytes = one "element")
+static ffn_igemm_desc f8_view(const ffn_igemm_desc& d) {
+    ffn_igemm_desc v = d;
+    v.f8 = 1;
+    v.x3 = 0;
+    v.K = d.K / 2;
+    v.Cin = d.Cin / 2;
+    v.Kpad = d.Kpad / 2;
+    v.lda = d.lda / 2;
+    return v;
+}
+static ffn_igemm_desc igemm_view(int dtype, const ffn_igemm_desc& d) {
+    if (dtype == FFN_BF16X3) return x3_view(d);
+    if (dtype == FFN_FP8) return f8_view(d);
+    ffn_igemm_desc v = d;
+    v.x3 = v.f8 = 0;
+    return v;
+}
+// the ping-pong tile height for bn-column tiles: of `heights`, among those the kernel takes (transposed form: M >= h is all that is left to ask) and
+// whose tiles fill at least min_fill4 quarters of the chip, the one whose tile count wastes the least of the last round of workgroups; 0 = none
+static int pp_tile_height(const ffn_igemm_desc& d, int bn, std::initializer_list<int> heights, int min_fill4, bool trans = false) {
+    long best = -1;
+    int bh = 0;
+    for (int h : heights) {
+        if (trans ? d.M < h : !pp_ok(d, h, bn)) continue;
+        const long tiles = (long)((d.M + h - 1) / h) * (d.N / bn);
+        if (tiles * 4 < (long)device_cus() * min_fill4) continue;
+        const long cost = ((tiles + device_cus() - 1) / device_cus()) * h;
+        if (best < 0 || cost < best) { best = cost; bh = h; }
     }
-#undef FFN_CFG_CASE
-    if (rc || ch.splitk == 1) return rc;
-    const long nq = (long)d.M * (d.N / 4);
-    if constexpr (X3) LAUNCH(igemm_splitk_reduce_kernel<float>, dim3(grid_for(nq)), dim3(256), 0, s, d, ch.splitk);
-    else LAUNCH(igemm_splitk_reduce_kernel<bf16>, dim3(grid_for(nq)), dim3(256), 0, s, d, ch.splitk);
-    return check_launch("igemm_splitk_reduce");
+    return bh;
+}
+static int pp_cfg(int bm, int bn) {
+    for (int cfg = CFG_PP_256x320; cfg <= CFG_PP_256x128; ++cfg)
+        if (kCfg[cfg].bm == bm && kCfg[cfg].bn == bn) return cfg;
+    return -1;
+}
+// 2x2 sub-pixel convolutions exist in the ping-pong kernel only: the first of its tiles that applies, wide and tall first
+static bool conv2_tile(const ffn_igemm_desc& d, int* bm, int* bn) {
+    for (int n : {320, 256})
+        for (int h : {256, 192})
+            if (pp_tile_height(d, n, {h}, 0)) { *bm = h; *bn = n; return true; }
+    return false;
+}
+// transposed-output (V^T) launches on the ping-pong kernel: deterministic tile choice (no tuning)
+static bool pp_trans_tile(const ffn_igemm_desc& d, int* bm, int* bn) {
+    const long lim = (1l << 31) - 4096;
+    *bn = d.N % 320 == 0 ? 320 : (d.N % 256 == 0 ? 256 : 0);
+    if (!*bn || d.alpha != 1.0f || d.rows_per_batch % 16 != 0 || d.M % 4 != 0) return false;
+    if (d.x3) {         // split-bf16: blocked operands, K tiles of 32 real elements (d.K = the virtual 3 K), fp32 V^T
+        if (d.x3 != 2 || d.K % 96 != 0 || d.K < 192 || d.a_lo != 32) return false;
+    } else if (d.K % 64 != 0 || d.K < 128) return false;
+    if ((long)(d.M + 256) * d.lda * 2 >= lim || (long)d.N * d.Kpad * 2 >= lim) return false;
+    if ((long)((d.M + d.rows_per_batch - 1) / d.rows_per_batch) * d.N * d.ldo * (d.x3 ? 4 : 2) >= lim) return false;
+    return (*bm = pp_tile_height(d, *bn, {256, 192}, 0, true)) != 0;
+}
+// igemm_rule_for as a configuration.  Waves per workgroup, measured on MI355X (tools/bench_kernels.py): occupancy beats prefetch depth for these
+// compiler-scheduled loops -- 2 workgroups/CU with a 2-deep ring win over 1 workgroup/CU with a 3-4 deep ring by ~35%; on the 128x128 tile 8 waves
+// (4 waves/SIMD) beat 4 waves by 5-30%, and 16 waves win once the K loop is short (split-bf16 / fp8: no 16-wave instantiation)
+static IgChoice rule_choice(int dtype, const ffn_igemm_desc& d) {
+    int bm, bn, sk;
+    igemm_rule_for(dtype, d, &bm, &bn, &sk);
+    const int kstage = dtype == FFN_F32 ? 32 : 64;
+    const int nk = ((d.K + kstage - 1) / kstage + sk - 1) / sk;    // K stages per workgroup
+    int cfg = CFG_64x64;
+    if (bm == 128 && bn == 64) cfg = CFG_128x64;
+    if (bm == 128 && bn == 128) cfg = (!d.conv && nk <= 24 && !d.x3 && !d.f8) ? CFG_128x128_16 : CFG_128x128_8;
+    return IgChoice{cfg, sk};
+}
+// the deterministic rule-based choice of the tuned family (bf16 / split-bf16 / fp8 problems, row-major output)
+static IgChoice heuristic_choice(const ffn_igemm_desc& d) {
+    int bm, bn;
+    if (d.conv == 2 && conv2_tile(d, &bm, &bn)) return IgChoice{pp_cfg(bm, bn), 1};      // (igemm_validate has checked that a tile applies)
+    // the ping-pong tile first, where its unsplit form applies and its tiles fill at least 3/4 of the chip.  Without this, every launch that
+    // cannot be tuned (FFN_IGEMM_TUNE=0, stream capture before a shape was seen, out aliasing residual) fell back to the 2-stage kernels
+    if (d.splitk <= 1) {
+        for (int n : {320, 256})
+            if ((bm = pp_tile_height(d, n, {256, 192}, 3))) return IgChoice{pp_cfg(bm, n), 1};
+        if (pp_tile_height(d, 128, {256}, 3)) return IgChoice{CFG_PP_256x128, 1};
+    }
+    return rule_choice(FFN_BF16, d);
 }
 
 struct TuneKey {
@@ -497,40 +338,7 @@ static bool tune_enabled() {
     static const bool on = [] { const char* e = getenv("FFN_IGEMM_TUNE"); return !(e && atoi(e) == 0); }();
     return on && g_tune_runtime;
 }
-// the deterministic rule-based choice (also what f32 parity mode uses): igemm_plan_for + igemm_exec_cfg mapped to a configuration
-static IgChoice heuristic_choice(const ffn_igemm_desc& d) {
-    if (d.conv == 2) {      // 2x2 sub-pixel convolutions exist in the ping-pong kernel only (ffn_igemm has checked that one of its tiles applies)
-        for (int bn : {320, 256})
-            for (int h : {256, 192})
-                if (d.N % bn == 0 && pp_ok(d, h, bn)) return IgChoice{bn == 320 ? (h == 256 ? CFG_PP_256x320 : CFG_PP_192x320) : (h == 256 ? CFG_PP_256x256 : CFG_PP_192x256), 1};
-    }
-    // the ping-pong tile first, where its unsplit form applies and its tiles fill at least 3/4 of the chip: tile height = the one whose
-    // tile count wastes the least of the last round of workgroups (the rule pp_trans_tile uses).  Without this, every launch that
-    // cannot be tuned (FFN_IGEMM_TUNE=0, stream capture before a shape was seen, out aliasing residual) fell back to the 2-stage kernels
-    if (d.splitk <= 1) {
-        for (int bn : {320, 256}) {
-            if (d.N % bn != 0) continue;
-            long best = -1;
-            int bh = 0;
-            for (int h : {256, 192}) {
-                if (!pp_ok(d, h, bn)) continue;
-                const long tiles = (long)((d.M + h - 1) / h) * (d.N / bn);
-                if (tiles * 4 < (long)device_cus() * 3) continue;
-                const long cost = ((tiles + device_cus() - 1) / device_cus()) * h;
-                if (best < 0 || cost < best) { best = cost; bh = h; }
-            }
-            if (best >= 0) return IgChoice{bn == 320 ? (bh == 256 ? CFG_PP_256x320 : CFG_PP_192x320) : (bh == 256 ? CFG_PP_256x256 : CFG_PP_192x256), 1};
-        }
-        if (d.N % 128 == 0 && pp_ok(d, 256, 128) && (long)((d.M + 255) / 256) * (d.N / 128) * 4 >= (long)device_cus() * 3) return IgChoice{CFG_PP_256x128, 1};
-    }
-    int bm, bn, sk, ns, nw;
-    igemm_plan_for(FFN_BF16, d, &bm, &bn, &sk);
-    igemm_exec_cfg(FFN_BF16, d, bm, bn, sk, &ns, &nw);
-    int cfg = CFG_64x64;
-    if (bm == 128 && bn == 64) cfg = CFG_128x64;
-    if (bm == 128 && bn == 128) cfg = (nw == 16 && !d.x3 && !d.f8) ? CFG_128x128_16 : CFG_128x128_8;
-    return IgChoice{cfg, sk};
-}
+static constexpr int kPpSplitBelow = 160;      // ping-pong configurations: unsplit tile counts below this get split-K candidates
 static int candidates_for(const ffn_igemm_desc& d, IgChoice* out, int cap) {
     int n = 0;
     const IgChoice h = heuristic_choice(d);
@@ -553,8 +361,7 @@ static int candidates_for(const ffn_igemm_desc& d, IgChoice* out, int cap) {
             // output tiles alone leave most of the chip idle
             const long pt = (long)((d.M + c.bm - 1) / c.bm) * (d.N / (c.bn > 0 ? c.bn : 1));
             if (d.splitk <= 1 && pp_ok(d, c.bm, c.bn) && n < cap) out[n++] = IgChoice{cfg, 1};
-            static const int split_below = [] { const char* e = getenv("FFN_PP_SPLIT_BELOW"); return e ? atoi(e) : 160; }();      // unsplit tile counts below this get split-K candidates
-            if (cfg != CFG_PP_256x128 && d.splitk != 1 && pt > 0 && pt < split_below && d.N % c.bn == 0) {
+            if (cfg != CFG_PP_256x128 && d.splitk != 1 && pt > 0 && pt < kPpSplitBelow && d.N % c.bn == 0) {
                 const int nkt = d.x3 ? d.K / 96 : d.K / 64;
                 int added = 0;
                 for (int sgo = (int)((384 + pt - 1) / pt); sgo >= 2 && added < 2; --sgo) {
@@ -601,53 +408,233 @@ extern "C" int ffn_igemm_force_config(int cfg) {
     g_force_cfg = (cfg >= 0 && cfg < CFG_COUNT) ? cfg : -1;
     return prev;
 }
-template <int AMODE, bool X3 = false, bool F8 = false>
-static int tuned_bf16(hipStream_t s, const ffn_igemm_desc& d) {
+// the configuration of a tuned-family problem where no timing is needed to know it: the forced one (the first candidate on it, else -- not valid
+// for this problem -- the rule's), then the table's.  false: neither (ffn_igemm tunes or takes heuristic_choice, ffn_igemm_kernel_name the latter)
+static bool known_choice(const ffn_igemm_desc& d, IgChoice* ch) {
+    IgChoice cand[40];
     if (g_force_cfg >= 0) {
-        IgChoice cand[40];
-        const int nc = candidates_for(d, cand, 40);
-        for (int i = 0; i < nc; ++i)
-            if (cand[i].cfg == g_force_cfg) return launch_bf16_cfg<AMODE, X3, F8>(s, d, cand[i]);
-        return launch_bf16_cfg<AMODE, X3, F8>(s, d, heuristic_choice(d));     // not valid for this problem
+        *ch = heuristic_choice(d);
+        for (int i = candidates_for(d, cand, 40) - 1; i >= 0; --i)
+            if (cand[i].cfg == g_force_cfg) *ch = cand[i];
+        return true;
     }
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cap);
-    const bool aliased = d.residual == d.out;        // repeated launches would accumulate: never time such a call
-    const TuneKey key = tune_key(d);
-    {
-        std::lock_guard<std::mutex> lk(g_tune_mu);
-        auto it = g_tuned.find(key);
-        if (it != g_tuned.end()) {
-            if (!it->second.validated) {
-                // an entry that came in as data (a tune file, another rank's table): launch it only if this build would have
-                // offered exactly that (configuration, K split) for THIS problem -- workspace capacity, split legality, tile
-                // applicability are all decided in candidates_for; anything else is dropped and the problem is tuned afresh
-                IgChoice cand[40];
-                const int nc = candidates_for(d, cand, 40);
-                bool ok = false;
-                for (int i = 0; i < nc; ++i) ok |= cand[i].cfg == it->second.ch.cfg && cand[i].splitk == it->second.ch.splitk;
-                if (ok) it->second.validated = true;
-                else g_tuned.erase(it), it = g_tuned.end();
-            }
-            if (it != g_tuned.end()) return launch_bf16_cfg<AMODE, X3, F8>(s, d, it->second.ch);
+    std::lock_guard<std::mutex> lk(g_tune_mu);
+    auto it = g_tuned.find(tune_key(d));
+    if (it == g_tuned.end()) return false;
+    if (!it->second.validated) {
+        // an entry that came in as data (a tune file, another rank's table): launch it only if this build would have
+        // offered exactly that (configuration, K split) for THIS problem -- workspace capacity, split legality, tile
+        // applicability are all decided in candidates_for; anything else is dropped and the problem is tuned afresh
+        const int nc = candidates_for(d, cand, 40);
+        bool ok = false;
+        for (int i = 0; i < nc; ++i) ok |= cand[i].cfg == it->second.ch.cfg && cand[i].splitk == it->second.ch.splitk;
+        if (!ok) return g_tuned.erase(it), false;
+        it->second.validated = true;
+    }
+    *ch = it->second.ch;
+    return true;
+}
+
+enum IgKind { IG_RING, IG_HALO, IG_PP, IG_PP_TRANS };
+struct IgemmPlan {
+    IgKind kind;
+    bool f32;                          // fp32 (else bf16: what split-bf16 and fp8 operands ride on, too) elements
+    int bm, bn, amode, nwm, nwn;       // tile, AMODE_*, wave grid (IG_RING: the ring depth NS is 2)
+    bool swap, fastk, x3, f8;
+    bool res, geglu, split;            // IG_PP: the instantiation's epilogue form
+    int splitk, halo_bytes, lds;
+    bool reduce_f32;                   // splitk > 1: igemm_splitk_reduce_kernel<float> (else <bf16>) finishes
+    dim3 grid, block;
+};
+// The one statement of which kernel ffn_igemm launches for a (validated, viewed: igemm_view) descriptor: igemm_run launches from it,
+// ffn_igemm_kernel_name spells it.
+//   The rule-based family (ch = nullptr): FFN_F32, and every transposed output (V^T for ffn_attn).  igemm_pp_kernel's transposed form where
+//     pp_trans_tile finds a tile (bf16 / split-bf16 elements); else igemm_glds_kernel on rule_choice's tile, K split and waves (the split-bf16
+//     V^T: 4 waves on every tile).
+//   The tuned family (bf16 / split-bf16 / fp8 elements, row-major output): the configuration `ch` -- forced, from the table, timed or
+//     heuristic_choice's -- on igemm_glds_kernel (walking its tiles from a co-resident grid), igemm_halo_kernel or igemm_pp_kernel.
+// FFN_EINVAL: a configuration that does not apply to the problem (candidates_for offers none such).
+static int igemm_plan(int dtype, const ffn_igemm_desc& d, const IgChoice* ch, IgemmPlan* p) {
+    *p = IgemmPlan{};
+    p->f32 = dtype == FFN_F32;
+    p->x3 = d.x3 != 0;
+    p->f8 = d.f8 != 0;
+    p->amode = d.conv ? AMODE_CONV3 : AMODE_DENSE;
+    p->swap = !(d.flags & FFN_IG_OUT_TRANSPOSED);
+    p->reduce_f32 = p->f32 || p->x3;
+    p->splitk = 1;
+    p->block = dim3(512);
+    const bool tuned = ch != nullptr;
+    IgChoice rule;
+    if (!tuned && !p->f32 && pp_trans_tile(d, &p->bm, &p->bn)) {
+        p->kind = IG_PP_TRANS;
+    } else {
+        if (!tuned) ch = &(rule = rule_choice(p->f32 ? FFN_F32 : FFN_BF16, d));
+        REQUIRE(ch->cfg >= 0 && ch->cfg < CFG_COUNT, "igemm: bad configuration %d", ch->cfg);
+        REQUIRE(!(p->x3 || p->f8) || x3_cfg(ch->cfg), "igemm: configuration %d is not built for split-bf16 / fp8 problems", ch->cfg);
+        const IgCfgInfo& c = kCfg[ch->cfg];
+        p->kind = is_halo_cfg(ch->cfg) ? IG_HALO : (is_pp_cfg(ch->cfg) ? IG_PP : IG_RING);
+        p->bm = c.bm; p->bn = c.bn; p->nwm = c.nwm; p->nwn = c.nwn;
+        p->splitk = ch->splitk;
+        p->block = dim3(64 * c.nwm * c.nwn);
+        if (!tuned && p->x3) p->nwm = p->nwn = 2, p->block = dim3(256);
+    }
+    const int ntm = (d.M + p->bm - 1) / p->bm, ntn = (d.N + p->bn - 1) / p->bn;
+    switch (p->kind) {
+    case IG_RING: {
+        // FASTK kernels (streaming loader) need every 128-byte K stage inside K / inside one conv tap
+        // the streaming loader's zero-page pointers (N-tail columns, rows past M, conv padding) walk 128 B per K stage over the WHOLE K
+        // range of the launch: K * 2 bytes must stay inside the 64 KiB zero page
+        p->fastk = tuned && !p->x3 && !p->f8 && (d.conv ? d.Cin % 64 == 0 : d.K % 64 == 0) && (long)d.K * 2 + 256 <= (long)sizeof(g_zero_page);
+        p->lds = 2 * (p->bm + p->bn) * 128;
+        int gx = ntm * ntn;
+        if (tuned || p->x3) {
+            // these instantiations walk several output tiles per workgroup (igemm.h): launch only as many workgroups as are co-resident
+            // (LDS / thread limits per CU) and let each stride over the tile list
+            int per_cu = (160 * 1024) / p->lds;
+            if (per_cu > 2048 / (int)p->block.x) per_cu = 2048 / (int)p->block.x;
+            const int cap = (device_cus() * per_cu) / p->splitk;
+            if (gx > cap && cap >= 8) gx = cap;
+        }
+        p->grid = dim3(gx, p->splitk);
+        break;
+    }
+    case IG_HALO:
+        p->halo_bytes = halo_bytes_for(d, p->bm);
+        REQUIRE(p->halo_bytes > 0 && p->splitk == 1 && !p->x3 && !p->f8, "igemm: halo kernel not applicable");
+        p->lds = 2 * p->halo_bytes + 2 * p->bn * 128;
+        p->grid = dim3((d.M / p->bm) * ntn);
+        break;
+    case IG_PP:
+        REQUIRE(pp_ok(d, p->bm, p->bn, p->splitk), "igemm: ping-pong kernel not applicable");
+        p->split = p->splitk > 1;
+        p->res = !p->split && d.residual;
+        p->geglu = !p->split && !d.conv && (d.flags & FFN_IG_GEGLU);
+        [[fallthrough]];
+    case IG_PP_TRANS: {
+        p->lds = 2 * (p->bm + p->bn) * 128 + 12288;
+        const int nt = ntm * (d.N / p->bn) * p->splitk;
+        p->grid = dim3(nt < device_cus() ? nt : device_cus());
+        break;
+    }
+    }
+    return FFN_OK;
+}
+template <typename K, typename... A>
+static int igemm_launch(const IgemmPlan& p, K kern, hipStream_t s, A... args) {
+    static const char* const what[] = {"igemm", "igemm(halo)", "igemm(ping-pong)", "igemm(ping-pong, transposed)"};
+    if (int rc = set_lds(kern, p.lds)) return rc;
+    LAUNCH(kern, p.grid, p.block, p.lds, s, args...);
+    return check_launch(what[p.kind]);
+}
+// the instantiations of igemm_glds_kernel: the 4-wave tiles of the split-bf16 V^T; else the three tiles every element type has, the 16-wave
+// 128x128 tile and -- bf16 operands, row-major output -- the wide tiles of the tuned family
+template <typename T, int AMODE, bool SWAP, bool FASTK = false, bool X3 = false, bool F8 = false>
+static int launch_ring(const IgemmPlan& p, hipStream_t s, const ffn_igemm_desc& d) {
+#define FFN_RING(BM_, BN_, WM_, WN_) \
+    if (p.bm == BM_ && p.bn == BN_ && p.nwm == WM_ && p.nwn == WN_) return igemm_launch(p, igemm_glds_kernel<T, BM_, BN_, AMODE, SWAP, 2, WM_, WN_, FASTK, X3, F8>, s, d)
+    if constexpr (X3 && !SWAP) {
+        FFN_RING(64, 64, 2, 2);
+        FFN_RING(128, 64, 2, 2);
+        FFN_RING(128, 128, 2, 2);
+    } else {
+        FFN_RING(64, 64, 2, 2);
+        FFN_RING(128, 64, 4, 2);
+        FFN_RING(128, 128, 2, 4);
+        if constexpr (!X3 && !F8) FFN_RING(128, 128, 4, 4);
+        if constexpr (sizeof(T) == 2 && SWAP && !X3 && !F8) {
+            FFN_RING(256, 128, 4, 4);
+            FFN_RING(256, 256, 4, 4);
+            FFN_RING(128, 320, 4, 4);
+            FFN_RING(128, 160, 4, 2);
+            FFN_RING(192, 320, 3, 4);      // 12 waves: 168 registers per wave (spills at 16 waves x 128)
         }
     }
-    if (!tune_enabled() || cap != hipStreamCaptureStatusNone || aliased) return launch_bf16_cfg<AMODE, X3, F8>(s, d, heuristic_choice(d));
+#undef FFN_RING
+    return fail(FFN_EINVAL, "igemm: no %d x %d tile on %d x %d waves for this problem", p.bm, p.bn, p.nwm, p.nwn);
+}
+// the instantiations of igemm_pp_kernel: per tile the plain / residual / split-K forms; dense A also the transposed form and, 256 columns wide,
+// GEGLU; the 256x128 tile for split-bf16 3x3 convolutions, plain / residual (pp_ok)
+template <int AMODE, bool X3 = false, bool F8 = false>
+static int launch_pp(const IgemmPlan& p, hipStream_t s, const ffn_igemm_desc& d) {
+    const bool trans = p.kind == IG_PP_TRANS;
+#define FFN_PP(BM_, BN_, RES_, GEGLU_, SPLIT_, TRANS_)                                                                       \
+    if (p.bm == BM_ && p.bn == BN_ && p.res == RES_ && p.geglu == GEGLU_ && p.split == SPLIT_ && trans == TRANS_) \
+        return igemm_launch(p, igemm_pp_kernel<BM_, BN_, AMODE, RES_, GEGLU_, SPLIT_, TRANS_, X3, F8>, s, d, p.splitk)
+#define FFN_PP_TILE(BM_, BN_)                                                                   \
+    FFN_PP(BM_, BN_, false, false, false, false);                                               \
+    FFN_PP(BM_, BN_, true, false, false, false);                                                \
+    FFN_PP(BM_, BN_, false, false, true, false);                                                \
+    if constexpr (AMODE == AMODE_DENSE && !F8) {                                                \
+        FFN_PP(BM_, BN_, false, false, false, true);                                            \
+        if constexpr (BN_ == 256) FFN_PP(BM_, BN_, false, true, false, false);                  \
+    }
+    FFN_PP_TILE(256, 320)
+    FFN_PP_TILE(256, 256)
+    FFN_PP_TILE(192, 320)
+    FFN_PP_TILE(192, 256)
+    if constexpr (X3 && AMODE == AMODE_CONV3) {
+        FFN_PP(256, 128, false, false, false, false);
+        FFN_PP(256, 128, true, false, false, false);
+    }
+#undef FFN_PP_TILE
+#undef FFN_PP
+    return fail(FFN_EINVAL, "igemm: no %d x %d ping-pong tile of this form", p.bm, p.bn);
+}
+// plan and launch: the rule-based family (ch = nullptr) or configuration `ch` of the tuned family; the split-K reduce behind either
+static int igemm_run(hipStream_t s, int dtype, const ffn_igemm_desc& d, const IgChoice* ch) {
+    IgemmPlan p;
+    int rc = igemm_plan(dtype, d, ch, &p);
+    if (rc) return rc;
+    const bool conv = p.amode == AMODE_CONV3;
+    switch (p.kind) {
+    case IG_RING:
+        if (p.f32) rc = conv ? launch_ring<float, AMODE_CONV3, true>(p, s, d) : (p.swap ? launch_ring<float, AMODE_DENSE, true>(p, s, d) : launch_ring<float, AMODE_DENSE, false>(p, s, d));
+        else if (!p.swap) rc = p.x3 ? launch_ring<bf16, AMODE_DENSE, false, false, true>(p, s, d) : launch_ring<bf16, AMODE_DENSE, false>(p, s, d);
+        else if (p.x3) rc = conv ? launch_ring<bf16, AMODE_CONV3, true, false, true>(p, s, d) : launch_ring<bf16, AMODE_DENSE, true, false, true>(p, s, d);
+        else if (p.f8) rc = launch_ring<bf16, AMODE_CONV3, true, false, false, true>(p, s, d);
+        else if (p.fastk) rc = conv ? launch_ring<bf16, AMODE_CONV3, true, true>(p, s, d) : launch_ring<bf16, AMODE_DENSE, true, true>(p, s, d);
+        else rc = conv ? launch_ring<bf16, AMODE_CONV3, true>(p, s, d) : launch_ring<bf16, AMODE_DENSE, true>(p, s, d);
+        break;
+    case IG_HALO:
+#define FFN_HALO(BM_, BN_) \
+    if (p.bm == BM_ && p.bn == BN_) rc = igemm_launch(p, igemm_halo_kernel<bf16, BM_, BN_, 4, 4>, s, d, p.halo_bytes)
+        FFN_HALO(128, 320);
+        FFN_HALO(256, 128);
+        FFN_HALO(256, 256);
+        FFN_HALO(128, 128);
+#undef FFN_HALO
+        break;
+    case IG_PP:
+    case IG_PP_TRANS:
+        if (p.x3) rc = conv ? launch_pp<AMODE_CONV3, true>(p, s, d) : launch_pp<AMODE_DENSE, true>(p, s, d);
+        else if (p.f8) rc = launch_pp<AMODE_CONV3, false, true>(p, s, d);
+        else rc = conv ? launch_pp<AMODE_CONV3>(p, s, d) : launch_pp<AMODE_DENSE>(p, s, d);
+        break;
+    }
+    if (rc || p.splitk == 1) return rc;
+    const dim3 grid(grid_for((long)d.M * (d.N / 4)));
+    if (p.reduce_f32) LAUNCH(igemm_splitk_reduce_kernel<float>, grid, dim3(256), 0, s, d, p.splitk);
+    else LAUNCH(igemm_splitk_reduce_kernel<bf16>, grid, dim3(256), 0, s, d, p.splitk);
+    return check_launch("igemm_splitk_reduce");
+}
+// first use of a problem shape outside stream capture: time its candidates on the caller's stream with the caller's buffers, cache the winner
+static int igemm_tune_now(hipStream_t s, int dtype, const ffn_igemm_desc& d) {
     std::lock_guard<std::mutex> lk(g_tune_mu);       // one tuning at a time
     IgChoice cand[40];
     const int nc = candidates_for(d, cand, 40);
     hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return launch_bf16_cfg<AMODE, X3, F8>(s, d, cand[0]);
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return igemm_run(s, dtype, d, &cand[0]);
     IgChoice best = cand[0];
     float best_ms = 1e30f;
     const int reps = 3;
     for (int i = 0; i < nc; ++i) {
-        int rc = launch_bf16_cfg<AMODE, X3, F8>(s, d, cand[i]);      // warm (LDS opt-in, code load)
+        int rc = igemm_run(s, dtype, d, &cand[i]);      // warm (LDS opt-in, code load)
         if (rc) continue;
         float ms = 1e30f;
         for (int round = 0; round < 2 && !rc; ++round) {       // min of two timed groups: one noisy group must not pick the configuration
             (void)hipEventRecord(e0, s);
-            for (int r = 0; r < reps && !rc; ++r) rc = launch_bf16_cfg<AMODE, X3, F8>(s, d, cand[i]);
+            for (int r = 0; r < reps && !rc; ++r) rc = igemm_run(s, dtype, d, &cand[i]);
             (void)hipEventRecord(e1, s);
             if (rc || hipEventSynchronize(e1) != hipSuccess) { rc = rc ? rc : FFN_EHIP; break; }
             float t = 0.f;
@@ -659,12 +646,12 @@ static int tuned_bf16(hipStream_t s, const ffn_igemm_desc& d) {
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    g_tuned[key] = TunedEntry{best, true};
+    g_tuned[tune_key(d)] = TunedEntry{best, true};
     static const bool verbose = getenv("FFN_IGEMM_TUNE_VERBOSE") != nullptr;
     if (verbose)
         fprintf(stderr, "[ffn tune] %s M=%d N=%d K=%d flags=%d -> %dx%d split %d (%.1f us, %d candidates)\n", d.conv ? "conv" : "dense", d.M, d.N,
                 d.K, d.flags, kCfg[best.cfg].bm, kCfg[best.cfg].bn, best.splitk, best_ms * 1e3f / reps, nc);
-    return launch_bf16_cfg<AMODE, X3, F8>(s, d, best);       // the output now holds the winner's result
+    return igemm_run(s, dtype, d, &best);       // the output now holds the winner's result
 }
 // ---- the tuned table as data: export / import (persist it across processes, broadcast rank 0's table so that every rank of a
 // sharded run launches the same configurations -- bf16 results then are bit-identical across ranks)
@@ -717,167 +704,112 @@ extern "C" int ffn_igemm_tune_import(const int* buf, int n_entries) {
     }
     return n;
 }
-static bool tuned_lookup(const ffn_igemm_desc& d, IgChoice* ch) {
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    auto it = g_tuned.find(tune_key(d));
-    if (it == g_tuned.end()) return false;
-    *ch = it->second.ch;
-    return true;
-}
-
-static bool pp_trans_tile(const ffn_igemm_desc& d, int* bm, int* bn);
-static ffn_igemm_desc x3_view(const ffn_igemm_desc& d);
-static ffn_igemm_desc f8_view(const ffn_igemm_desc& d);
-extern "C" int ffn_igemm_kernel_name(int dtype, const ffn_igemm_desc* d0, char* buf, int len) {
-    REQUIRE(d0 && buf && len > 0, "igemm_kernel_name: null argument");
-    int bm, bn, sk, ns, nw;
-    IgChoice ch;
-    const bool x3 = dtype == FFN_BF16X3, f8 = dtype == FFN_FP8;
-    const ffn_igemm_desc dd = x3 ? x3_view(*d0) : (f8 ? f8_view(*d0) : *d0);
-    const ffn_igemm_desc* d = &dd;
-    if (x3 && (d->flags & FFN_IG_OUT_TRANSPOSED)) {
-        if (!d->conv && pp_trans_tile(*d, &bm, &bn)) {
-            snprintf(buf, len, "void igemm_pp_kernel<%d, %d, 0, false, false, false, true, true, false>(ffn_igemm_desc, int)", bm, bn);
-            return FFN_OK;
-        }
-        igemm_plan_for(FFN_BF16, *d, &bm, &bn, &sk);
-        snprintf(buf, len, "void igemm_glds_kernel<bf16, %d, %d, 0, false, 2, 2, 2, false, true, false>(ffn_igemm_desc)", bm, bn);
+// shape and flag checks of a descriptor (no buffer is looked at: ffn_igemm_kernel_name asks too)
+static int igemm_validate(int dtype, const ffn_igemm_desc& d) {
+    REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16 || dtype == FFN_BF16X3 || dtype == FFN_FP8, "igemm: bad dtype %d", dtype);
+    if (dtype == FFN_FP8) {
+        REQUIRE(d.conv && d.Cin > 0 && d.Cin % 16 == 0 && d.K == 9 * d.Cin && d.Kpad >= d.K && d.Kpad % 16 == 0 && d.lda == d.Cin,
+                "igemm(fp8): 3x3 convolutions with Cin %% 16 == 0 only (Cin=%d, K=%d, Kpad=%d, lda=%d)", d.Cin, d.K, d.Kpad, d.lda);
+        REQUIRE(d.M > 0 && d.N > 0 && d.N % 4 == 0 && d.ldo % 4 == 0 && d.rows_per_batch > 0 && d.M % (d.Hout * d.Wout) == 0, "igemm(fp8): bad shape");
+        REQUIRE(!(d.flags & (FFN_IG_GEGLU | FFN_IG_OUT_TRANSPOSED | FFN_IG_OUT_PAIR | FFN_IG_OUT_F32)), "igemm(fp8): plain / SiLU / residual epilogues only");
+        REQUIRE(d.stride == 1 || d.stride == 2, "igemm(fp8): stride %d", d.stride);
+        int ex = 0;
+        REQUIRE(d.alpha > 0.f && frexpf(d.alpha, &ex) == 0.5f, "igemm(fp8): alpha must be a power of two (the un-scaling of two power-of-two operand scales)");
+        if (d.residual) REQUIRE(d.ldr % 4 == 0, "igemm(fp8): ldr=%d must be a multiple of 4", d.ldr);
         return FFN_OK;
     }
-    if ((dtype == FFN_BF16 || x3 || f8) && !(d->flags & FFN_IG_OUT_TRANSPOSED)) {      // the tuned (or, untuned, rule-based) bf16 configuration
-        if (!tuned_lookup(*d, &ch)) ch = heuristic_choice(*d);
-        const IgCfgInfo& c = kCfg[ch.cfg];
-        if (is_halo_cfg(ch.cfg)) {
-            snprintf(buf, len, "void igemm_halo_kernel<bf16, %d, %d, %d, %d>(ffn_igemm_desc, int)", c.bm, c.bn, c.nwm, c.nwn);
-            return FFN_OK;
+    const int epc = dtype == FFN_F32 ? 4 : 8;
+    const int kmul = dtype == FFN_BF16X3 ? (d.x3 == 2 ? 2 : 3) : 1;       // W row: [hi | lo | hi] planes (3 K) or [hi(32) | lo(32)] blocks (2 K)
+    REQUIRE(d.M > 0 && d.N > 0 && d.K > 0, "igemm: empty problem M=%d N=%d K=%d", d.M, d.N, d.K);
+    REQUIRE(d.Kpad >= kmul * d.K && d.Kpad % epc == 0, "igemm: Kpad=%d (row stride of W) must be >= %d x K=%d and a multiple of %d", d.Kpad, kmul, d.K, epc);
+    if (dtype == FFN_BF16X3) {
+        const int plane = d.conv ? d.Cin : d.K;
+        if (d.x3 == 2) {
+            REQUIRE(plane % 32 == 0 && d.a_lo == 32 && d.lda >= 2 * plane, "igemm: blocked split-bf16 operands need K (conv: Cin) %% 32 == 0, a_lo = 32, lda >= 2 x that (%d, a_lo=%d, lda=%d)", plane, d.a_lo, d.lda);
+        } else {
+            REQUIRE(d.a_lo % 8 == 0 && d.a_lo >= plane && d.a_lo + plane <= d.lda, "igemm: split-bf16 A needs planes of %d elements: a_lo=%d, lda=%d", plane, d.a_lo, d.lda);
         }
-        if (is_pp_cfg(ch.cfg)) {
-            const bool split = ch.splitk > 1;
-            snprintf(buf, len, "void igemm_pp_kernel<%d, %d, %d, %s, %s, %s, false, %s, %s>(ffn_igemm_desc, int)", c.bm, c.bn, d->conv ? 1 : 0,
-                     (!split && d->residual) ? "true" : "false", (!split && (d->flags & FFN_IG_GEGLU)) ? "true" : "false", split ? "true" : "false",
-                     x3 ? "true" : "false", f8 ? "true" : "false");
-            return FFN_OK;
+        REQUIRE(d.lda % 8 == 0, "igemm: lda=%d must be a multiple of 8", d.lda);
+        REQUIRE(d.alpha == 1.0f, "igemm: split-bf16 problems take alpha = 1");
+    }
+    REQUIRE(d.K % epc == 0, "igemm: K=%d must be a multiple of %d", d.K, epc);
+    REQUIRE(d.rows_per_batch > 0, "igemm: rows_per_batch must be > 0");
+    if (d.conv) {
+        REQUIRE(d.Cin % epc == 0, "igemm: Cin=%d must be a multiple of %d", d.Cin, epc);
+        if (d.conv == 2) {
+            REQUIRE((dtype == FFN_BF16 || dtype == FFN_BF16X3) && d.K == 4 * d.Cin && d.stride == 1 && d.upsample == 0 && d.pad >= 0 && d.pad <= 3 && d.splitk <= 1,
+                    "igemm: 2x2 convolution needs FFN_BF16 / FFN_BF16X3, K = 4*Cin, stride 1, no upsample, pad in 0..3, no forced split");
+            int bm, bn;
+            REQUIRE(conv2_tile(igemm_view(dtype, d), &bm, &bn), "igemm: 2x2 convolution M=%d N=%d Cin=%d fits no ping-pong tile (Cin %% 64 (split-bf16: 32), N %% 256 / 320, M >= 192)", d.M, d.N, d.Cin);
+        } else {
+            REQUIRE(d.conv == 1, "igemm: conv=%d", d.conv);
+            REQUIRE(d.K == 9 * d.Cin, "igemm: conv K=%d != 9*Cin=%d", d.K, 9 * d.Cin);
         }
-        const bool fastk = !x3 && !f8 && (d->conv ? d->Cin % 64 == 0 : d->K % 64 == 0) && (long)d->K * 2 + 256 <= (long)sizeof(g_zero_page);
-        snprintf(buf, len, "void igemm_glds_kernel<bf16, %d, %d, %d, true, 2, %d, %d, %s, %s, %s>(ffn_igemm_desc)", c.bm, c.bn, d->conv ? 1 : 0, c.nwm, c.nwn,
-                 fastk ? "true" : "false", x3 ? "true" : "false", f8 ? "true" : "false");
-        return FFN_OK;
+        REQUIRE(d.stride == 1 || d.stride == 2, "igemm: stride %d", d.stride);
+        REQUIRE(d.upsample == 0 || d.upsample == 1, "igemm: upsample %d", d.upsample);
+        REQUIRE(d.M % (d.Hout * d.Wout) == 0, "igemm: M=%d not a multiple of Hout*Wout", d.M);
+    } else {
+        REQUIRE(d.lda % epc == 0, "igemm: lda=%d must be a multiple of %d", d.lda, epc);
     }
-    if (dtype == FFN_BF16 && (d->flags & FFN_IG_OUT_TRANSPOSED) && !d->conv && pp_trans_tile(*d, &bm, &bn)) {
-        snprintf(buf, len, "void igemm_pp_kernel<%d, %d, 0, false, false, false, true, false, false>(ffn_igemm_desc, int)", bm, bn);
-        return FFN_OK;
+    if (d.flags & FFN_IG_OUT_KV64) {
+        REQUIRE(dtype == FFN_BF16X3 && !d.conv && !d.residual && !d.rowbias && d.splitk <= 1 &&
+                    !(d.flags & (FFN_IG_GEGLU | FFN_IG_OUT_PAIR | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU)),
+                "igemm: FFN_IG_OUT_KV64 needs FFN_BF16X3, dense A, the plain epilogue and no forced split-K");
+        if (d.flags & FFN_IG_OUT_TRANSPOSED) REQUIRE(d.rows_per_batch % 64 == 0 && d.M % d.rows_per_batch == 0 && d.ldo >= d.rows_per_batch && d.ldo % 64 == 0,
+                                                     "igemm: KV64 transposed output needs rows_per_batch %% 64 == 0, whole batches, ldo %% 64 == 0 (rows_per_batch=%d, ldo=%d)", d.rows_per_batch, d.ldo);
+        else REQUIRE(d.kv64_from >= 0 && d.kv64_from < d.N && d.kv64_from % 64 == 0 && d.N % 64 == 0 && d.ldo % 4 == 0,
+                     "igemm: KV64 output needs kv64_from and N %% 64 == 0 (kv64_from=%d, N=%d)", d.kv64_from, d.N);
     }
-    igemm_plan_for(dtype, *d, &bm, &bn, &sk);
-    igemm_exec_cfg(dtype, *d, bm, bn, sk, &ns, &nw);
-    const char* t = dtype == FFN_F32 ? "float" : "bf16";
-    const char* swap = (d->flags & FFN_IG_OUT_TRANSPOSED) ? "false" : "true";
-    if (ns == 1) snprintf(buf, len, "void igemm_kernel<%s, %d, %d, %d, %s>(ffn_igemm_desc)", t, bm, bn, d->conv ? 1 : 0, swap);
-    else {
-        const int nwm = nw == 16 ? 4 : (nw == 8 ? (bn == 64 ? 4 : 2) : 2), nwn = nw / nwm;
-        snprintf(buf, len, "void igemm_glds_kernel<%s, %d, %d, %d, %s, %d, %d, %d, false, false, false>(ffn_igemm_desc)", t, bm, bn, d->conv ? 1 : 0, swap, ns, nwm, nwn);
+    if (d.flags & FFN_IG_OUT_TRANSPOSED) {
+        REQUIRE(!d.conv, "igemm: transposed output is only supported for dense A");
+        REQUIRE(d.ldo % 4 == 0, "igemm: transposed ldo=%d must be a multiple of 4", d.ldo);
+        REQUIRE(!(d.flags & (FFN_IG_GEGLU | FFN_IG_OUT_F32 | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU)) && !d.residual && !d.rowbias,
+                "igemm: transposed output supports bias only");
+    } else {
+        REQUIRE(d.N % 4 == 0 && d.ldo % 4 == 0, "igemm: N=%d and ldo=%d must be multiples of 4", d.N, d.ldo);
+        if (d.residual) REQUIRE(d.ldr % 4 == 0, "igemm: ldr=%d must be a multiple of 4", d.ldr);
+        if (d.flags & FFN_IG_OUT_PAIR) {
+            const int nout = (d.flags & FFN_IG_GEGLU) ? d.N / 2 : d.N;
+            REQUIRE(dtype == FFN_BF16X3 && d.ldo % 16 == 0 && d.ldo / 2 >= nout, "igemm: pair output needs FFN_BF16X3, ldo %% 16 == 0, ldo/2 >= columns");
+            REQUIRE(d.residual != d.out, "igemm: pair output cannot overwrite its fp32 residual");
+            REQUIRE((d.ldo / 2) % 32 != 0 || nout % 32 == 0 || nout == d.ldo / 2, "igemm: blocked pair output (ldo/2 %% 32 == 0) needs whole 32-column blocks");
+            // every producer derives the layout (blocked / planes) from the ROW WIDTH ldo / 2; the ping-pong GEGLU epilogue always writes blocked rows
+            REQUIRE(nout == d.ldo / 2 || (d.ldo / 2) % 32 == 0, "igemm: pair output into a wider row needs ldo/2 %% 32 == 0 (ldo=%d, columns=%d)", d.ldo, nout);
+        }
+        if (d.flags & FFN_IG_GEGLU) {
+            REQUIRE(d.N % 64 == 0, "igemm: GEGLU needs N %% 64 == 0 (N=%d)", d.N);
+            REQUIRE(!d.residual && !d.rowbias && !(d.flags & (FFN_IG_OUT_F32 | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU)), "igemm: GEGLU epilogue is exclusive");
+        }
     }
+    const int act = d.flags & (FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU);
+    REQUIRE((act & (act - 1)) == 0, "igemm: SILU / GELU / QGELU / RELU are mutually exclusive");
+    REQUIRE(d.splitk >= 0, "igemm: splitk must be >= 0");
     return FFN_OK;
 }
-// transposed-output (V^T) launches on the ping-pong kernel: deterministic tile choice (no tuning): the tile height whose tile count
-// wastes the least of the last round of 256 workgroups
-static bool pp_trans_tile(const ffn_igemm_desc& d, int* bm, int* bn) {
-    static const bool on = [] { const char* e = getenv("FFN_IGEMM_PP_TRANS"); return !(e && atoi(e) == 0); }();
-    if (!on) return false;
-    const long lim = (1l << 31) - 4096;
-    *bn = d.N % 320 == 0 ? 320 : (d.N % 256 == 0 ? 256 : 0);
-    if (!*bn || d.alpha != 1.0f || d.rows_per_batch % 16 != 0 || d.M % 4 != 0) return false;
-    if (d.x3) {         // split-bf16: blocked operands, K tiles of 32 real elements (d.K = the virtual 3 K), fp32 V^T
-        if (d.x3 != 2 || d.K % 96 != 0 || d.K < 192 || d.a_lo != 32) return false;
-    } else if (d.K % 64 != 0 || d.K < 128) return false;
-    if ((long)(d.M + 256) * d.lda * 2 >= lim || (long)d.N * d.Kpad * 2 >= lim) return false;
-    if ((long)((d.M + d.rows_per_batch - 1) / d.rows_per_batch) * d.N * d.ldo * (d.x3 ? 4 : 2) >= lim) return false;
-    long best = -1;
-    for (int h : {256, 192}) {
-        if (d.M < h) continue;
-        const long tiles = (long)((d.M + h - 1) / h) * (d.N / *bn);
-        const long cost = ((tiles + device_cus() - 1) / device_cus()) * h;
-        if (best < 0 || cost < best) { best = cost; *bm = h; }
+static bool tuned_family(int dtype, const ffn_igemm_desc& d) { return dtype != FFN_F32 && !(d.flags & FFN_IG_OUT_TRANSPOSED); }
+extern "C" int ffn_igemm_kernel_name(int dtype, const ffn_igemm_desc* d0, char* buf, int len) {
+    REQUIRE(d0 && buf && len > 0, "igemm_kernel_name: null argument");
+    if (int rc = igemm_validate(dtype, *d0)) return rc;
+    const ffn_igemm_desc d = igemm_view(dtype, *d0);
+    const bool tuned = tuned_family(dtype, d);
+    IgChoice ch;
+    if (tuned && !known_choice(d, &ch)) ch = heuristic_choice(d);
+    IgemmPlan p;
+    if (int rc = igemm_plan(dtype, d, tuned ? &ch : nullptr, &p)) return rc;
+    auto b = [](bool v) { return v ? "true" : "false"; };
+    switch (p.kind) {
+    case IG_RING:
+        snprintf(buf, len, "void igemm_glds_kernel<%s, %d, %d, %d, %s, 2, %d, %d, %s, %s, %s>(ffn_igemm_desc)", p.f32 ? "float" : "bf16", p.bm, p.bn, p.amode,
+                 b(p.swap), p.nwm, p.nwn, b(p.fastk), b(p.x3), b(p.f8));
+        break;
+    case IG_HALO: snprintf(buf, len, "void igemm_halo_kernel<bf16, %d, %d, %d, %d>(ffn_igemm_desc, int)", p.bm, p.bn, p.nwm, p.nwn); break;
+    case IG_PP:
+    case IG_PP_TRANS:
+        snprintf(buf, len, "void igemm_pp_kernel<%d, %d, %d, %s, %s, %s, %s, %s, %s>(ffn_igemm_desc, int)", p.bm, p.bn, p.amode, b(p.res), b(p.geglu), b(p.split),
+                 b(p.kind == IG_PP_TRANS), b(p.x3), b(p.f8));
+        break;
     }
-    return best >= 0;
-}
-template <bool X3 = false>
-static int launch_pp_trans(hipStream_t s, const ffn_igemm_desc& d, int bm, int bn) {
-    const int pplds = 2 * (bm + bn) * 128 + 12288;
-    const int nt = ((d.M + bm - 1) / bm) * (d.N / bn);
-    const int grid = nt < device_cus() ? nt : device_cus();
-    int rc = FFN_OK;
-    (void)hipGetLastError();
-#define FFN_PP_TR(BM_, BN_)                                                                         \
-    do {                                                                                            \
-        auto kern = igemm_pp_kernel<BM_, BN_, AMODE_DENSE, false, false, false, true, X3>;          \
-        if ((rc = set_lds(kern, pplds))) return rc;                                                 \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), pplds, s, d, 1);                            \
-    } while (0)
-    if (bm == 256 && bn == 320) FFN_PP_TR(256, 320);
-    else if (bm == 256) FFN_PP_TR(256, 256);
-    else if (bn == 320) FFN_PP_TR(192, 320);
-    else FFN_PP_TR(192, 256);
-#undef FFN_PP_TR
-    return check_launch("igemm(ping-pong, transposed)");
-}
-template <typename T>
-static int dispatch_igemm(hipStream_t s, const ffn_igemm_desc& d) {
-    const bool tr = d.flags & FFN_IG_OUT_TRANSPOSED;
-    if (d.conv) {
-        if (tr) return fail(FFN_EINVAL, "igemm: transposed output is only supported for dense A");
-        if constexpr (sizeof(T) == 2) return tuned_bf16<AMODE_CONV3>(s, d);
-        return dispatch_igemm_tile<T, AMODE_CONV3, true>(s, d);
-    }
-    if (tr) {
-        if constexpr (sizeof(T) == 2) {
-            int bm, bn;
-            if (pp_trans_tile(d, &bm, &bn)) return launch_pp_trans(s, d, bm, bn);
-        }
-        return dispatch_igemm_tile<T, AMODE_DENSE, false>(s, d);
-    }
-    if constexpr (sizeof(T) == 2) return tuned_bf16<AMODE_DENSE>(s, d);
-    return dispatch_igemm_tile<T, AMODE_DENSE, true>(s, d);
-}
-// the library's private view of a split-bf16 problem: the kernels and the tile / split-K logic see the VIRTUAL contraction 3K
-static ffn_igemm_desc x3_view(const ffn_igemm_desc& d) {
-    ffn_igemm_desc v = d;
-    v.x3 = d.x3 == 2 ? 2 : 1;          // operand layout: 1 = planes, 2 = 128-byte blocks [hi(32) | lo(32)] (include/freefine_hip.h)
-    v.f8 = 0;
-    v.K = 3 * d.K;
-    v.flags |= FFN_IG_OUT_F32;
-    return v;
-}
-template <int BM, int BN>
-static int launch_x3_trans(hipStream_t s, const ffn_igemm_desc& d) {
-    const int ntiles = ((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
-    return launch_igemm_kernel(igemm_glds_kernel<bf16, BM, BN, AMODE_DENSE, false, 2, 2, 2, false, true>, 2 * (BM + BN) * 128, s, d, ntiles, 1, 256, true);
-}
-static int dispatch_igemm_x3(hipStream_t s, const ffn_igemm_desc& d) {
-    const bool tr = d.flags & FFN_IG_OUT_TRANSPOSED;
-    if (d.conv) {
-        if (tr) return fail(FFN_EINVAL, "igemm: transposed output is only supported for dense A");
-        return tuned_bf16<AMODE_CONV3, true>(s, d);
-    }
-    if (tr) {            // V^T for the attention kernels, fp32 transposed stores: the ping-pong tile where it applies, else a generic tile
-        int bm, bn, sk;
-        if (pp_trans_tile(d, &bm, &bn)) return launch_pp_trans<true>(s, d, bm, bn);
-        igemm_plan_for(FFN_BF16, d, &bm, &bn, &sk);
-        if (bm == 128 && bn == 128) return launch_x3_trans<128, 128>(s, d);
-        if (bm == 128) return launch_x3_trans<128, 64>(s, d);
-        return launch_x3_trans<64, 64>(s, d);
-    }
-    return tuned_bf16<AMODE_DENSE, true>(s, d);
-}
-// fp8 problems: the kernels and every tile / split-K decision see a bf16-SHAPED view (two e4m3 bytes = one "element")
-static ffn_igemm_desc f8_view(const ffn_igemm_desc& d) {
-    ffn_igemm_desc v = d;
-    v.f8 = 1;
-    v.x3 = 0;
-    v.K = d.K / 2;
-    v.Cin = d.Cin / 2;
-    v.Kpad = d.Kpad / 2;
-    v.lda = d.lda / 2;
-    return v;
+    return FFN_OK;
 }
 extern "C" int ffn_split_pair(void* stream, const float* src, void* dst, long rows, int C, int ld_src) {
     REQUIRE(src && dst && rows > 0 && C > 0 && C % 4 == 0 && ld_src >= C && ld_src % 4 == 0, "split_pair: bad arguments (C=%d, ld_src=%d)", C, ld_src);
@@ -905,102 +837,29 @@ extern "C" int ffn_conv3x3_n4(void* stream, int dtype, const void* x, const floa
     }
     return check_launch("conv3x3_n4");
 }
-extern "C" int ffn_igemm(void* stream, int dtype, const ffn_igemm_desc* d) {
-    REQUIRE(d, "igemm: null descriptor");
-    REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16 || dtype == FFN_BF16X3 || dtype == FFN_FP8, "igemm: bad dtype %d", dtype);
+extern "C" int ffn_igemm(void* stream, int dtype, const ffn_igemm_desc* d0) {
+    REQUIRE(d0, "igemm: null descriptor");
+    if (int rc = igemm_validate(dtype, *d0)) return rc;
     if (dtype == FFN_FP8) {
-        REQUIRE(d->A && d->W && d->out && aligned16(d->A) && aligned16(d->W) && aligned16(d->out), "igemm(fp8): A/W/out must be non-null and 16-byte aligned");
-        REQUIRE(d->conv && d->Cin > 0 && d->Cin % 16 == 0 && d->K == 9 * d->Cin && d->Kpad >= d->K && d->Kpad % 16 == 0 && d->lda == d->Cin,
-                "igemm(fp8): 3x3 convolutions with Cin %% 16 == 0 only (Cin=%d, K=%d, Kpad=%d, lda=%d)", d->Cin, d->K, d->Kpad, d->lda);
-        REQUIRE(d->M > 0 && d->N > 0 && d->N % 4 == 0 && d->ldo % 4 == 0 && d->rows_per_batch > 0 && d->M % (d->Hout * d->Wout) == 0, "igemm(fp8): bad shape");
-        REQUIRE(!(d->flags & (FFN_IG_GEGLU | FFN_IG_OUT_TRANSPOSED | FFN_IG_OUT_PAIR | FFN_IG_OUT_F32)), "igemm(fp8): plain / SiLU / residual epilogues only");
-        REQUIRE(d->stride == 1 || d->stride == 2, "igemm(fp8): stride %d", d->stride);
-        int ex = 0;
-        REQUIRE(d->alpha > 0.f && frexpf(d->alpha, &ex) == 0.5f, "igemm(fp8): alpha must be a power of two (the un-scaling of two power-of-two operand scales)");
-        if (d->residual) REQUIRE(d->ldr % 4 == 0, "igemm(fp8): ldr=%d must be a multiple of 4", d->ldr);
-        if (d->ws) REQUIRE(aligned16(d->ws) && d->ws_bytes >= 0, "igemm(fp8): workspace must be 16-byte aligned");
-        return tuned_bf16<AMODE_CONV3, false, true>(reinterpret_cast<hipStream_t>(stream), f8_view(*d));
-    }
-    const int epc = dtype == FFN_F32 ? 4 : 8, kstage = 8 * epc;
-    const int kmul = dtype == FFN_BF16X3 ? (d->x3 == 2 ? 2 : 3) : 1;       // W row: [hi | lo | hi] planes (3 K) or [hi(32) | lo(32)] blocks (2 K)
-    REQUIRE(d->A && d->W && d->out, "igemm: null A/W/out");
-    REQUIRE(aligned16(d->A) && aligned16(d->W) && aligned16(d->out), "igemm: A/W/out must be 16-byte aligned");
-    REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "igemm: empty problem M=%d N=%d K=%d", d->M, d->N, d->K);
-    REQUIRE(d->Kpad >= kmul * d->K && d->Kpad % epc == 0, "igemm: Kpad=%d (row stride of W) must be >= %d x K=%d and a multiple of %d", d->Kpad, kmul, d->K, epc);
-    if (dtype == FFN_BF16X3) {
-        const int plane = d->conv ? d->Cin : d->K;
-        if (d->x3 == 2) {
-            REQUIRE(plane % 32 == 0 && d->a_lo == 32 && d->lda >= 2 * plane, "igemm: blocked split-bf16 operands need K (conv: Cin) %% 32 == 0, a_lo = 32, lda >= 2 x that (%d, a_lo=%d, lda=%d)", plane, d->a_lo, d->lda);
-        } else {
-            REQUIRE(d->a_lo % 8 == 0 && d->a_lo >= plane && d->a_lo + plane <= d->lda, "igemm: split-bf16 A needs planes of %d elements: a_lo=%d, lda=%d", plane, d->a_lo, d->lda);
-        }
-        REQUIRE(d->lda % 8 == 0, "igemm: lda=%d must be a multiple of 8", d->lda);
-        REQUIRE(d->alpha == 1.0f, "igemm: split-bf16 problems take alpha = 1");
-        if (d->residual) REQUIRE(aligned16(d->residual), "igemm: fp32 residual must be 16-byte aligned");
-    }
-    (void)kstage;
-    REQUIRE(d->K % epc == 0, "igemm: K=%d must be a multiple of %d", d->K, epc);
-    REQUIRE(d->rows_per_batch > 0, "igemm: rows_per_batch must be > 0");
-    if (d->conv) {
-        REQUIRE(d->Cin % epc == 0, "igemm: Cin=%d must be a multiple of %d", d->Cin, epc);
-        if (d->conv == 2) {
-            REQUIRE((dtype == FFN_BF16 || dtype == FFN_BF16X3) && d->K == 4 * d->Cin && d->stride == 1 && d->upsample == 0 && d->pad >= 0 && d->pad <= 3 && d->splitk <= 1,
-                    "igemm: 2x2 convolution needs FFN_BF16 / FFN_BF16X3, K = 4*Cin, stride 1, no upsample, pad in 0..3, no forced split");
-            const ffn_igemm_desc v = dtype == FFN_BF16X3 ? x3_view(*d) : *d;
-            bool any = false;
-            for (int bn : {320, 256})
-                for (int h : {256, 192}) any |= d->N % bn == 0 && pp_ok(v, h, bn);
-            REQUIRE(any, "igemm: 2x2 convolution M=%d N=%d Cin=%d fits no ping-pong tile (Cin %% 64 (split-bf16: 32), N %% 256 / 320, M >= 192)", d->M, d->N, d->Cin);
-        } else {
-            REQUIRE(d->conv == 1, "igemm: conv=%d", d->conv);
-            REQUIRE(d->K == 9 * d->Cin, "igemm: conv K=%d != 9*Cin=%d", d->K, 9 * d->Cin);
-        }
-        REQUIRE(d->stride == 1 || d->stride == 2, "igemm: stride %d", d->stride);
-        REQUIRE(d->upsample == 0 || d->upsample == 1, "igemm: upsample %d", d->upsample);
-        REQUIRE(d->M % (d->Hout * d->Wout) == 0, "igemm: M=%d not a multiple of Hout*Wout", d->M);
+        REQUIRE(d0->A && d0->W && d0->out && aligned16(d0->A) && aligned16(d0->W) && aligned16(d0->out), "igemm(fp8): A/W/out must be non-null and 16-byte aligned");
     } else {
-        REQUIRE(d->lda % epc == 0, "igemm: lda=%d must be a multiple of %d", d->lda, epc);
+        REQUIRE(d0->A && d0->W && d0->out, "igemm: null A/W/out");
+        REQUIRE(aligned16(d0->A) && aligned16(d0->W) && aligned16(d0->out), "igemm: A/W/out must be 16-byte aligned");
     }
-    if (d->flags & FFN_IG_OUT_KV64) {
-        REQUIRE(dtype == FFN_BF16X3 && !d->conv && !d->residual && !d->rowbias && d->splitk <= 1 &&
-                    !(d->flags & (FFN_IG_GEGLU | FFN_IG_OUT_PAIR | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU)),
-                "igemm: FFN_IG_OUT_KV64 needs FFN_BF16X3, dense A, the plain epilogue and no forced split-K");
-        if (d->flags & FFN_IG_OUT_TRANSPOSED) REQUIRE(d->rows_per_batch % 64 == 0 && d->M % d->rows_per_batch == 0 && d->ldo >= d->rows_per_batch && d->ldo % 64 == 0,
-                                                      "igemm: KV64 transposed output needs rows_per_batch %% 64 == 0, whole batches, ldo %% 64 == 0 (rows_per_batch=%d, ldo=%d)", d->rows_per_batch, d->ldo);
-        else REQUIRE(d->kv64_from >= 0 && d->kv64_from < d->N && d->kv64_from % 64 == 0 && d->N % 64 == 0 && d->ldo % 4 == 0,
-                     "igemm: KV64 output needs kv64_from and N %% 64 == 0 (kv64_from=%d, N=%d)", d->kv64_from, d->N);
-    }
-    if (d->flags & FFN_IG_OUT_TRANSPOSED) {
-        REQUIRE(d->ldo % 4 == 0, "igemm: transposed ldo=%d must be a multiple of 4", d->ldo);
-        REQUIRE(!(d->flags & (FFN_IG_GEGLU | FFN_IG_OUT_F32 | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU)) && !d->residual && !d->rowbias,
-                "igemm: transposed output supports bias only");
-    } else {
-        REQUIRE(d->N % 4 == 0 && d->ldo % 4 == 0, "igemm: N=%d and ldo=%d must be multiples of 4", d->N, d->ldo);
-        if (d->residual) REQUIRE(d->ldr % 4 == 0, "igemm: ldr=%d must be a multiple of 4", d->ldr);
-        if (d->flags & FFN_IG_OUT_PAIR) {
-            const int nout = (d->flags & FFN_IG_GEGLU) ? d->N / 2 : d->N;
-            REQUIRE(dtype == FFN_BF16X3 && d->ldo % 16 == 0 && d->ldo / 2 >= nout, "igemm: pair output needs FFN_BF16X3, ldo %% 16 == 0, ldo/2 >= columns");
-            REQUIRE(d->residual != d->out, "igemm: pair output cannot overwrite its fp32 residual");
-            REQUIRE((d->ldo / 2) % 32 != 0 || nout % 32 == 0 || nout == d->ldo / 2, "igemm: blocked pair output (ldo/2 %% 32 == 0) needs whole 32-column blocks");
-            // every producer derives the layout (blocked / planes) from the ROW WIDTH ldo / 2; the ping-pong GEGLU epilogue always writes blocked rows
-            REQUIRE(nout == d->ldo / 2 || (d->ldo / 2) % 32 == 0, "igemm: pair output into a wider row needs ldo/2 %% 32 == 0 (ldo=%d, columns=%d)", d->ldo, nout);
-        }
-        if (d->flags & FFN_IG_GEGLU) {
-            REQUIRE(d->N % 64 == 0, "igemm: GEGLU needs N %% 64 == 0 (N=%d)", d->N);
-            REQUIRE(!d->residual && !d->rowbias && !(d->flags & (FFN_IG_OUT_F32 | FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU)), "igemm: GEGLU epilogue is exclusive");
-        }
-    }
-    {
-        const int act = d->flags & (FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU);
-        REQUIRE((act & (act - 1)) == 0, "igemm: SILU / GELU / QGELU / RELU are mutually exclusive");
-    }
-    if (d->ws) REQUIRE(aligned16(d->ws) && d->ws_bytes >= 0, "igemm: workspace must be 16-byte aligned");
-    REQUIRE(d->splitk >= 0, "igemm: splitk must be >= 0");
+    if (dtype == FFN_BF16X3 && d0->residual) REQUIRE(aligned16(d0->residual), "igemm: fp32 residual must be 16-byte aligned");
+    if (d0->ws) REQUIRE(aligned16(d0->ws) && d0->ws_bytes >= 0, "igemm%s: workspace must be 16-byte aligned", dtype == FFN_FP8 ? "(fp8)" : "");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == FFN_BF16X3) return dispatch_igemm_x3(s, x3_view(*d));
-    ffn_igemm_desc plain = *d;
-    plain.x3 = plain.f8 = 0;
-    return dtype == FFN_F32 ? dispatch_igemm<float>(s, plain) : dispatch_igemm<bf16>(s, plain);
+    const ffn_igemm_desc d = igemm_view(dtype, *d0);
+    if (!tuned_family(dtype, d)) return igemm_run(s, dtype, d, nullptr);
+    IgChoice ch;
+    if (!known_choice(d, &ch)) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(s, &cap);
+        // (out aliasing residual: repeated launches would accumulate -- never time such a call)
+        if (tune_enabled() && cap == hipStreamCaptureStatusNone && d.residual != d.out) return igemm_tune_now(s, dtype, d);
+        ch = heuristic_choice(d);
+    }
+    return igemm_run(s, dtype, d, &ch);
 }
 
 extern "C" int ffn_igemm_tune(void* stream, int dtype, const ffn_igemm_desc* d) { return ffn_igemm(stream, dtype, d); }

@@ -12,10 +12,10 @@
 // Linear reached from override_forward (/root/reference/src/utils/attention.py:105-214) and the to_q/to_k/
 // to_v/to_out projections of the hooked Attention.forward (attention.py:372-407).
 //
-// Tile: BM x BN outputs per 256-thread workgroup (4 waves as 2x2), 128 bytes of K per stage (64 bf16 / 32
-// f32), two LDS stages, register-staged global loads issued one stage ahead (issue-early / write-late).
-// LDS rows are 128 B with a 16-byte-chunk XOR swizzle (chunk ^= row & 7): conflict-free for both the
-// ds_write_b128 of the loader and the ds_read_b128 fragment reads.
+// Tile: BM x BN outputs per workgroup of NWM x NWN waves (4, 8, 12 or 16), 128 bytes of K per stage (64 bf16 /
+// 32 f32) in a 2-deep LDS ring filled by direct-to-LDS loads (igemm_glds_kernel below), one stage in flight
+// while the other is multiplied.  LDS rows are 128 B with a 16-byte-chunk XOR swizzle (chunk ^= row & 7),
+// applied on the source side of the loads: conflict-free for the ds_read_b128 fragment reads.
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -192,157 +192,10 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc
     }
 }
 
-template <typename T, int BM, int BN, int AMODE, bool SWAP>
-__global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
-    constexpr int EPC = DT<T>::EPC;
-    constexpr int BKE = 8 * EPC;  // K elements per stage (128 bytes)
-    constexpr int WM = BM / 2, WN = BN / 2;
-    constexpr int FM = WM / 16, FN = WN / 16;
-    constexpr int NA = BM / 32, NB = BN / 32;  // 16-byte chunks per thread per stage
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* As = smem;                    // [2][BM][128]
-    char* Bs = smem + 2 * BM * 128;     // [2][BN][128]
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l15 = lane & 15, g = lane >> 4;
-
-    const int ntn = (p.N + BN - 1) / BN;
-    const int ntm = (p.M + BM - 1) / BM;
-    const int L = xcd_remap(blockIdx.x, ntm * ntn);
-    const int m0 = (L / ntn) * BM, n0 = (L % ntn) * BN;
-
-    const int lc = tid & 7, lr = tid >> 3;
-
-    // ---- per-thread loader state -------------------------------------------------------------
-    const T* __restrict__ Ag = reinterpret_cast<const T*>(p.A);
-    const T* __restrict__ Wg = reinterpret_cast<const T*>(p.W);
-    long a_base[NA];
-    int a_y[NA], a_x[NA];
-    bool a_ok[NA];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        const int m = m0 + lr + 32 * i;
-        a_ok[i] = m < p.M;
-        if (AMODE == AMODE_DENSE) {
-            a_base[i] = (long)m * p.lda;
-            a_y[i] = a_x[i] = 0;
-        } else {
-            const int hw = p.Hout * p.Wout;
-            const int b = m / hw, rem = m - b * hw;
-            const int yo = rem / p.Wout, xo = rem - yo * p.Wout;
-            a_base[i] = (long)b * p.Hin * p.Win;
-            a_y[i] = yo * p.stride - p.pad;
-            a_x[i] = xo * p.stride - p.pad;
-        }
-    }
-    long b_base[NB];
-    bool b_ok[NB];
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-        const int n = n0 + lr + 32 * i;
-        b_ok[i] = n < p.N;
-        b_base[i] = (long)n * p.Kpad;
-    }
-    const int He = p.Hin << p.upsample, We = p.Win << p.upsample;
-
-    u32x4 ra[NA], rb[NB];
-    auto issue_loads = [&](int k0) {
-        const int kk = k0 + lc * EPC;
-        if (AMODE == AMODE_DENSE) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                ra[i] = u32x4{0, 0, 0, 0};
-                if (a_ok[i] && kk < p.K) ra[i] = *reinterpret_cast<const u32x4*>(Ag + a_base[i] + kk);
-            }
-        } else {
-            const int tap = kk / p.Cin, ci = kk - tap * p.Cin;
-            const int ky = tap / 3, kx = tap - 3 * ky;
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                int yy = a_y[i] + ky, xx = a_x[i] + kx;
-                const bool inb = a_ok[i] && (kk < p.K) && yy >= 0 && yy < He && xx >= 0 && xx < We;
-                yy >>= p.upsample;
-                xx >>= p.upsample;
-                ra[i] = u32x4{0, 0, 0, 0};
-                if (inb) ra[i] = *reinterpret_cast<const u32x4*>(Ag + (a_base[i] + (long)yy * p.Win + xx) * p.Cin + ci);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            rb[i] = u32x4{0, 0, 0, 0};
-            if (b_ok[i] && kk < p.K) rb[i] = *reinterpret_cast<const u32x4*>(Wg + b_base[i] + kk);  // Kpad = row stride of W
-        }
-    };
-    auto write_lds = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int row = lr + 32 * i;
-            *reinterpret_cast<u32x4*>(As + buf * BM * 128 + row * 128 + ((lc ^ (row & 7)) << 4)) = ra[i];
-        }
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            const int row = lr + 32 * i;
-            *reinterpret_cast<u32x4*>(Bs + buf * BN * 128 + row * 128 + ((lc ^ (row & 7)) << 4)) = rb[i];
-        }
-    };
-
-    f32x4 acc[FM][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // split-K: blockIdx.y owns the K stages [kt0, nk); partial sums go to fp32 slabs, ffn's reduce kernel finishes
-    const int nk_all = (p.K + BKE - 1) / BKE;
-    const int spp = (nk_all + (int)gridDim.y - 1) / (int)gridDim.y;
-    const int kt0 = blockIdx.y * spp;
-    const int nk = min(nk_all, kt0 + spp);
-    issue_loads(kt0 * BKE);
-    write_lds(kt0 & 1);
-    __syncthreads();
-
-    for (int kt = kt0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < nk) issue_loads((kt + 1) * BKE);
-        const char* Ab = As + buf * BM * 128;
-        const char* Bb = Bs + buf * BN * 128;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            u32x4 fa[FM], fb[FN];
-#pragma unroll
-            for (int i = 0; i < FM; ++i) {
-                const int row = wm * WM + i * 16 + l15;
-                fa[i] = *reinterpret_cast<const u32x4*>(Ab + row * 128 + (((4 * s + g) ^ (row & 7)) << 4));
-            }
-#pragma unroll
-            for (int j = 0; j < FN; ++j) {
-                const int row = wn * WN + j * 16 + l15;
-                fb[j] = *reinterpret_cast<const u32x4*>(Bb + row * 128 + (((4 * s + g) ^ (row & 7)) << 4));
-            }
-#pragma unroll
-            for (int i = 0; i < FM; ++i)
-#pragma unroll
-                for (int j = 0; j < FN; ++j) {
-                    if (SWAP)
-                        DT<T>::mma(fb[j], fa[i], acc[i][j]);
-                    else
-                        DT<T>::mma(fa[i], fb[j], acc[i][j]);
-                }
-        }
-        if (kt + 1 < nk) write_lds(buf ^ 1);
-        __syncthreads();
-    }
-
-    igemm_epilogue<T, FM, FN, SWAP>(p, acc, m0 + wm * WM, n0 + wn * WN, l15, g);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// igemm_glds_kernel: same tile / fragment / epilogue scheme as igemm_kernel, but both operand tiles are staged with
-// direct-to-LDS loads (global_load_lds_dwordx4): no VGPR round trip and no ds_write (on gfx950 a ds_write_b128 stream
-// delivers only ~80 B/clk/CU, which made the register-staged loader's LDS writes as expensive as the MFMAs).
+// igemm_glds_kernel: both operand tiles are staged with direct-to-LDS loads (global_load_lds_dwordx4): no VGPR round
+// trip and no ds_write (on gfx950 a ds_write_b128 stream delivers only ~80 B/clk/CU, which made the LDS writes of a
+// register-staged loader as expensive as the MFMAs).
 // The LDS image must be lane-linear per wave instruction (8 rows x 128 B = 1 KiB), so the XOR swizzle is applied to
 // the SOURCE address: the lane that owns LDS slot c of row r fetches global chunk c ^ (r & 7).  Out-of-range chunks
 // (conv zero padding, M/N/K tails) are fetched from a 16-byte zero page.
@@ -355,7 +208,7 @@ __device__ __attribute__((aligned(128))) const uint32_t g_zero_page[16384] = {0}
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-// NS = LDS ring depth (NS-1 stages in flight), NWM x NWN = wave grid over the BM x BN tile (4 or 8 waves)
+// NS = LDS ring depth (NS-1 stages in flight; every launch uses 2), NWM x NWN = wave grid over the BM x BN tile
 // FASTK: the caller guarantees K % 64-byte-stage == 0 (dense) / Cin % stage == 0 (conv): the streaming loader below is used
 // X3 (FFN_BF16X3, "split-bf16"): every fp32 value is carried as hi + lo (two bf16) and a product as hi*hi + hi*lo + lo*hi on the bf16
 // MFMA with fp32 accumulation.  Nothing changes in the multiplier: the GEMM simply runs over a VIRTUAL contraction of 3K --
@@ -813,7 +666,7 @@ __global__ __launch_bounds__(64 * NWM * NWN) void igemm_halo_kernel(const IgemmP
     igemm_epilogue<T, FM, FN, true>(p, acc, m0 + wm * WM, n0 + wn * WN, l15, g);
 }
 
-// split-K finish: out[m, n..n+3] = epilogue(sum_s slab[s][m][n..n+3])  (same epilogue as the SWAP path of igemm_kernel)
+// split-K finish: out[m, n..n+3] = epilogue(sum_s slab[s][m][n..n+3])  (same epilogue as the SWAP path of igemm_glds_kernel)
 template <typename T>
 __global__ __launch_bounds__(256) void igemm_splitk_reduce_kernel(const IgemmParams p, int splitk) {
     const long nq = (long)p.M * (p.N / 4);

@@ -130,7 +130,8 @@ int ffn_groupnorm_f8(void* stream, const void* x_bf16, void* y_e4m3, const float
  * bf16 problems: the first time a problem shape is seen outside stream capture, ffn_igemm times its few plausible (tile, K-split)
  * configurations on the caller's stream (this one call synchronises the stream and launches the kernel several times: `out` must
  * not alias `residual`) and caches the winner; FFN_IGEMM_TUNE=0 in the environment keeps the deterministic rule-based choice
- * (f32 always uses it).  Testing hooks: the number of bf16 configurations, and forcing one (-1 = off; returns the previous value). */
+ * (f32 and transposed outputs always use it); no other environment variable changes which kernel runs.  Testing hooks: the number of bf16
+ * configurations, and forcing one wherever it is a candidate for the problem (-1 = off; returns the previous value). */
 /* explicit warm-up entry point: tunes (or looks up) the configuration for `d` now, exactly as the first ffn_igemm call would --
  * it IS a full ffn_igemm call: `out` is written (several times while candidates are timed) and holds the winner's result */
 int ffn_igemm_tune(void* stream, int dtype, const ffn_igemm_desc* d);
@@ -152,9 +153,9 @@ int ffn_igemm_tune_enable(int on);
 int ffn_igemm_tune_stamp(void);   /* first int of every entry this build exports */
 int ffn_igemm_num_configs(void);
 int ffn_igemm_force_config(int cfg);
-/* which tile (BM x BN) ffn_igemm dispatches for this problem -- lets a profiler name the kernel instantiation */
-int ffn_igemm_variant(const ffn_igemm_desc* d, int* bm, int* bn);
-/* the kernel instantiation ffn_igemm launches for this problem, spelled like rocprofv3's kernel trace */
+/* the kernel instantiation ffn_igemm launches for this problem, spelled like rocprofv3's kernel trace: the same choice as ffn_igemm's, without
+ * timing (a forced configuration, else the table's entry, else the rule-based one).  Nothing is launched and no buffer is looked at; a descriptor
+ * whose shape or flags ffn_igemm refuses gets the same error code and message. */
 int ffn_igemm_kernel_name(int dtype, const ffn_igemm_desc* d, char* buf, int len);
 
 /* ---- multi-pass masked attention (the FreeFine attention modulation) -----------------------------------------

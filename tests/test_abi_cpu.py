@@ -220,6 +220,102 @@ def test_attention_kernel_choice_table():
             assert ops.kv_images_ok(D, S, Sk, passes) == (got != -22), (D, S, Sk, got)
 
 
+def test_igemm_kernel_choice_table():
+    """ffn_igemm_kernel_name (nothing is launched: no GPU needed, the CU count falls back to 256) spells the plan ffn_igemm launches from.  Rule-based
+    rows: the names the library gave before the choice was gathered into one plan, pasted in -- they must not change.  Forced rows: under
+    ffn_igemm_force_config the name is that configuration's kernel wherever the configuration is a candidate for the problem, else the rule's.  Error
+    rows: a descriptor ffn_igemm refuses gets the same code and message from both entry points."""
+    import ctypes
+    from freefine_amd import _lib
+    lib = _lib.load()
+    F32, BF16, X3, F8 = _lib.FFN_F32, _lib.FFN_BF16, _lib.FFN_BF16X3, _lib.FFN_FP8
+    TR, GEGLU, KV64 = _lib.IG_OUT_TRANSPOSED, _lib.IG_GEGLU, _lib.IG_OUT_KV64
+
+    def desc(M, N, K, conv=0, hw=32, x3=0, **kw):
+        d = _lib.IgemmDesc()
+        d.A = d.W = d.out = 0x10000                   # never dereferenced
+        d.M, d.N, d.K, d.Kpad, d.lda, d.ldo, d.rows_per_batch, d.alpha = M, N, K, K, K, N, M, 1.0
+        if conv:                                      # hw x hw images, stride 1, K = taps * Cin
+            taps = 9 if conv == 1 else 4
+            d.conv, d.Cin, d.lda, d.Hin, d.Win, d.Hout, d.Wout, d.stride, d.pad, d.rows_per_batch = conv, K // taps, K // taps, hw, hw, hw, hw, 1, 1, hw * hw
+        if x3:                                        # 2: blocked operands, 1: planes
+            d.x3, d.a_lo, d.lda, d.Kpad = x3, (32 if x3 == 2 else d.lda), 2 * d.lda, (2 if x3 == 2 else 3) * K
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def name(dtype, d):
+        buf = ctypes.create_string_buffer(200)
+        rc = lib.ffn_igemm_kernel_name(dtype, ctypes.byref(d), buf, 200)
+        return buf.value.decode() if rc == 0 else rc
+
+    def glds(t, bm, bn, amode, swap, nwm, nwn, fastk=False, x3=False, f8=False):
+        f = lambda v: "true" if v else "false"
+        return f"void igemm_glds_kernel<{t}, {bm}, {bn}, {amode}, {f(swap)}, 2, {nwm}, {nwn}, {f(fastk)}, {f(x3)}, {f(f8)}>(ffn_igemm_desc)"
+
+    def pp(bm, bn, amode, res=False, geglu=False, split=False, trans=False, x3=False, f8=False):
+        f = lambda v: "true" if v else "false"
+        return f"void igemm_pp_kernel<{bm}, {bn}, {amode}, {f(res)}, {f(geglu)}, {f(split)}, {f(trans)}, {f(x3)}, {f(f8)}>(ffn_igemm_desc, int)"
+    lib.ffn_igemm_tune_clear()
+    lib.ffn_igemm_force_config(-1)
+    rows = [
+        (F32, desc(64, 320, 320), "igemm_glds_kernel<float, 64, 64, 0, true, 2, 2, 2, false, false, false>"),      # f32 dense: M = 64, 512, 4096 (the rule gives
+        (F32, desc(512, 320, 320), "igemm_glds_kernel<float, 128, 64, 0, true, 2, 4, 2, false, false, false>"),      # unsplit dense problems of M >= 128 the 128x64 tile)
+        (F32, desc(4096, 320, 320), "igemm_glds_kernel<float, 128, 64, 0, true, 2, 4, 2, false, false, false>"),
+        (F32, desc(2048, 320, 576, conv=1), "igemm_glds_kernel<float, 64, 64, 1, true, 2, 2, 2, false, false, false>"),      # f32 3x3 convolution
+        (F32, desc(65536, 320, 576, conv=1), "igemm_glds_kernel<float, 128, 128, 1, true, 2, 2, 4, false, false, false>"),      # ... and one large enough for 128x128
+        (BF16, desc(65536, 320, 320), "igemm_pp_kernel<256, 320, 0, false, false, false, false, false, false>"),      # bf16 dense on the ping-pong tile: plain,
+        (BF16, desc(65536, 320, 320, residual=0x20000, ldr=320), "igemm_pp_kernel<256, 320, 0, true, false, false, false, false, false>"),      # with residual,
+        (BF16, desc(16384, 2560, 320, flags=GEGLU, ldo=1280), "igemm_pp_kernel<256, 256, 0, false, true, false, false, false, false>"),      # GEGLU
+        (BF16, desc(4096, 320, 72), "igemm_glds_kernel<bf16, 128, 64, 0, true, 2, 4, 2, false, false, false>"),      # K % 64 != 0: no streaming loader
+        (BF16, desc(64, 320, 320), "igemm_glds_kernel<bf16, 64, 64, 0, true, 2, 2, 2, true, false, false>"),      # small M
+        (BF16, desc(65536, 320, 1152, conv=1), "igemm_pp_kernel<256, 320, 1, false, false, false, false, false, false>"),      # 3x3 convolution on a ping-pong tile
+        (BF16, desc(3072, 320, 1152, conv=1), "igemm_glds_kernel<bf16, 64, 64, 1, true, 2, 2, 2, true, false, false>"),      # ... below the 3/4-fill rule
+        (BF16, desc(2048, 320, 512, conv=2, pad=3), "igemm_pp_kernel<256, 320, 1, false, false, false, false, false, false>"),      # 2x2 convolution
+        (BF16, desc(4096, 320, 320, flags=TR, ldo=4096), "igemm_pp_kernel<192, 320, 0, false, false, false, true, false, false>"),      # transposed: ping-pong tile,
+        (BF16, desc(4096, 320, 64, flags=TR, ldo=4096), "igemm_glds_kernel<bf16, 128, 64, 0, false, 2, 4, 2, false, false, false>"),      # generic fallback (K = 64)
+        (X3, desc(65536, 320, 320, x3=2), "igemm_pp_kernel<256, 320, 0, false, false, false, false, true, false>"),      # split-bf16, blocked operands: dense,
+        (X3, desc(65536, 320, 1152, conv=1, x3=2), "igemm_pp_kernel<256, 320, 1, false, false, false, false, true, false>"),      # 3x3 convolution,
+        (X3, desc(4096, 320, 320, x3=2, flags=TR, ldo=4096), "igemm_pp_kernel<192, 320, 0, false, false, false, true, true, false>"),      # transposed,
+        (X3, desc(4096, 640, 320, x3=2, flags=KV64, kv64_from=320), "igemm_glds_kernel<bf16, 128, 64, 0, true, 2, 4, 2, false, true, false>"),      # KV64,
+        (X3, desc(65536, 128, 1152, conv=1, x3=2), "igemm_pp_kernel<256, 128, 1, false, false, false, false, true, false>"),      # the 256x128 tile
+        (X3, desc(4096, 320, 24, x3=1), "igemm_glds_kernel<bf16, 128, 64, 0, true, 2, 4, 2, false, true, false>"),      # split-bf16, planes
+        (F8, desc(65536, 320, 1152, conv=1, alpha=0.25), "igemm_pp_kernel<256, 320, 1, false, false, false, false, false, true>"),      # fp8 3x3 convolution
+        (BF16, desc(600, 512, 4096, splitk=8, ws=0x30000, ws_bytes=1 << 30), "igemm_glds_kernel<bf16, 128, 128, 0, true, 2, 4, 4, true, false, false>"),      # caller-forced split-K
+    ]
+    for dtype, d, want in rows:
+        assert name(dtype, d) == f"void {want}({'ffn_igemm_desc, int' if 'igemm_pp' in want else 'ffn_igemm_desc'})", (dtype, d.M, d.N, d.K, d.conv, d.flags, want)
+    # forced rows: one 3x3 stride-1 convolution, B = 3, 32x32, Cin = 128, N = 320.  kCfg of csrc/capi.hip: (BM, BN, NWM, NWN), then the halo
+    # kernel's four tiles and the ping-pong kernel's five.  Every generic and halo tile is a candidate (M = 3072 is whole tiles of whole image
+    # rows); of the ping-pong tiles the two 320 columns wide (N % 256 != 0; the 256x128 tile is for split-bf16 problems)
+    kcfg = [(64, 64, 2, 2), (128, 64, 4, 2), (128, 128, 2, 4), (128, 128, 4, 4), (256, 128, 4, 4), (256, 256, 4, 4), (128, 320, 4, 4), (128, 160, 4, 2), (192, 320, 3, 4),
+            (128, 320, 4, 4), (256, 128, 4, 4), (256, 256, 4, 4), (128, 128, 4, 4),
+            (256, 320, 2, 4), (256, 256, 2, 4), (192, 320, 2, 4), (192, 256, 2, 4), (256, 128, 2, 4)]
+    assert lib.ffn_igemm_num_configs() == len(kcfg)
+    conv = desc(3072, 320, 1152, conv=1)
+    rule = name(BF16, conv)
+    try:
+        for cfg, (bm, bn, nwm, nwn) in enumerate(kcfg):
+            lib.ffn_igemm_force_config(cfg)
+            if cfg < 9:
+                want = glds("bf16", bm, bn, 1, True, nwm, nwn, fastk=True)
+            elif cfg < 13:
+                want = f"void igemm_halo_kernel<bf16, {bm}, {bn}, {nwm}, {nwn}>(ffn_igemm_desc, int)"
+            else:
+                want = pp(bm, bn, 1) if bn == 320 else rule
+            assert name(BF16, conv) == want, cfg
+    finally:
+        lib.ffn_igemm_force_config(-1)
+    for dtype, d, msg in [(BF16, desc(2048, 320, 576, conv=1, flags=TR), b"transposed output is only supported for dense A"),
+                          (BF16, desc(4096, 2560, 320, flags=GEGLU, ldo=1280, residual=0x20000, ldr=1280), b"GEGLU epilogue is exclusive"),
+                          (BF16, desc(2048, 384, 512, conv=2), b"fits no ping-pong tile"),
+                          (BF16, desc(4096, 320, 320, Kpad=312), b"Kpad=312")]:
+        assert name(dtype, d) == -22
+        text = lib.ffn_last_error()
+        assert msg in text and text.startswith(b"igemm: "), text
+        assert lib.ffn_igemm(None, dtype, ctypes.byref(d)) == -22 and lib.ffn_last_error() == text
+
+
 def test_attention_row_split_minimises_resident_rounds():
     """ops.attn_row_split: rows per launch of a self-attention call on the one-workgroup-per-CU kernels (256 CUs): never more than FFN_ATT_MAXB, never more rounds
     than the fixed 16-row split, the documented cases, every row covered once."""

@@ -515,6 +515,11 @@ def test_kernels_are_deterministic(gpu):
     same(lambda: ops.attention(q, kt, vtt, heads, 0.125, loc, Sk=77), 3)
 
 
+# (BM, BN) of ffn_igemm's bf16 configurations (kCfg of csrc/capi.hip): 9 generic tiles, the halo kernel's 4, the ping-pong kernel's 5
+_IGEMM_CFG_TILES = [(64, 64), (128, 64), (128, 128), (128, 128), (256, 128), (256, 256), (128, 320), (128, 160), (192, 320),
+                    (128, 320), (256, 128), (256, 256), (128, 128), (256, 320), (256, 256), (192, 320), (192, 256), (256, 128)]
+
+
 def test_every_bf16_igemm_configuration(gpu):
     """ffn_igemm picks (tile, K-split) per shape by timing; force EVERY bf16 configuration in turn (incl. the 256x256 / 128x320
     tiles, the persistent tile walk and the weight-stationary kernels) on shapes where it is valid and check the result."""
@@ -550,6 +555,19 @@ def test_every_bf16_igemm_configuration(gpu):
             ref = torch.nn.functional.conv2d(xr, w.double().cpu(), b.double().cpu(), padding=1) + rb.double().cpu()[:, :, None, None]
             ref = ref.permute(0, 2, 3, 1).reshape(B, H * H, Cout) + r.double().cpu()
             assert relerr(out, ref) < tol(dt), (cfg, "conv")
+            # ffn_igemm_kernel_name makes ffn_igemm's choice (here with the device's CU count): it names the forced configuration's tile wherever that
+            # is a candidate for this convolution -- every generic tile and the ping-pong tiles 320 columns wide; M = 3 * 576 rows are no whole 128-row
+            # tiles, so no halo tile applies
+            wp = ops.pack_conv3x3(w, dt)
+            d = L.IgemmDesc()
+            d.A, d.W, d.out, d.bias, d.rowbias, d.residual = x.data_ptr(), wp.data_ptr(), out.data_ptr(), b.data_ptr(), rb.data_ptr(), r.data_ptr()
+            d.M, d.N, d.K, d.Kpad, d.lda, d.ldo, d.ldr, d.ldrb, d.rows_per_batch = B * H * H, Cout, 9 * Cin, wp.shape[1], Cin, Cout, Cout, Cout, H * H
+            d.Hin, d.Win, d.Cin, d.Hout, d.Wout, d.stride, d.pad, d.alpha, d.conv = H, H, Cin, H, H, 1, 1, 1.0, 1
+            d.ws, d.ws_bytes = ops._workspace(x.device).data_ptr(), ops.WS_BYTES
+            bm, bn = _IGEMM_CFG_TILES[cfg]
+            if cfg < 9 or (cfg >= 13 and bn == 320):
+                assert f"<bf16, {bm}, {bn}, " in ops._igemm_name(lib, L.FFN_BF16, d) or f"igemm_pp_kernel<{bm}, {bn}, " in ops._igemm_name(lib, L.FFN_BF16, d), \
+                    (cfg, ops._igemm_name(lib, L.FFN_BF16, d))
             # shapes the ping-pong kernel accepts (256-row tiles, N % 320 == 0 or N % 256 == 0, rows per image % 128 == 0), with the
             # time-embedding row bias arriving through its LDS column vectors and the residual through its accumulator start values
             for (B, H, W, Cin, Cout) in [(3, 32, 32, 128, 320), (2, 16, 48, 64, 512), (5, 16, 16, 192, 640)]:
