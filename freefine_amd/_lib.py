@@ -73,6 +73,14 @@ class PackDesc(C.Structure):
     ]
 
 
+class DiftDesc(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("tgt", C.c_void_p), ("kps", C.c_void_p), ("ws", C.c_void_p), ("out_rc", C.c_void_p), ("out_cos", C.c_void_p),
+        ("ws_bytes", C.c_long), ("es", C.c_long),
+        ("dtype", C.c_int), ("E", C.c_int), ("C", C.c_int), ("ld", C.c_int), ("h", C.c_int), ("w", C.c_int), ("H", C.c_int), ("W", C.c_int), ("K", C.c_int),
+    ]
+
+
 # every symbol include/freefine_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _f, _l = C.c_void_p, C.c_int, C.c_float, C.c_long
 SYMBOLS = {
@@ -123,6 +131,8 @@ SYMBOLS = {
     "ffn_splat_bin": (_i, [_vp, _i, _vp, _i, _f, _i, _i, _vp, _vp, _vp]),
     "ffn_splat_render": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp]),
     "ffn_embed_tokens": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _l, _i, _i, _i]),
+    "ffn_dift_match": (_i, [_vp, C.POINTER(DiftDesc)]),
+    "ffn_dift_workspace_bytes": (_l, [_i, _i, _i, _i]),
     "ffn_image_to_nhwc": (_i, [_vp, _i, _vp, _vp, _l, _i]),
     "ffn_nhwc_to_image": (_i, [_vp, _i, _vp, _vp, _i, _i, _i]),
 }

@@ -70,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 3; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers)
+extern "C" int ffn_version(void) { return 4; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -1129,6 +1129,34 @@ extern "C" int ffn_embed_tokens(void* stream, int dtype, const int* ids, const f
     REQUIRE(M > 0 && S > 0 && V > 0 && C > 0 && C % 4 == 0 && M < (1l << 31), "embed_tokens: bad shape M=%ld S=%d C=%d V=%d (C %% 4 == 0)", M, S, C, V);
     fembed_launch(reinterpret_cast<hipStream_t>(stream), dtype == FFN_BF16, ids, table, pos, out, M, S, C, V);
     return check_launch("embed_tokens");
+}
+
+// ---- DIFT correspondence search (kernels and launch sequence: dift.hip / dift_match.h) -----------------------------------------------------------
+extern "C" __attribute__((visibility("hidden"))) long fdift_ws_bytes(int C, int h, int w, int K);
+extern "C" __attribute__((visibility("hidden"))) void fdift_launch(hipStream_t s, const ffn_dift_desc* d);
+
+extern "C" long ffn_dift_workspace_bytes(int C, int h, int w, int K) {
+    REQUIRE(C > 0 && C % 4 == 0 && h >= 1 && w >= 1 && K >= 1 && (long)h * w < (1l << 31), "dift_workspace_bytes: bad shape C=%d h=%d w=%d K=%d (C %% 4 == 0)", C, h, w, K);
+    return fdift_ws_bytes(C, h, w, K);
+}
+
+extern "C" int ffn_dift_match(void* stream, const ffn_dift_desc* dp) {
+    REQUIRE(dp, "dift_match: null descriptor");
+    const ffn_dift_desc& d = *dp;
+    REQUIRE(d.dtype == FFN_F32 || d.dtype == FFN_BF16, "dift_match: bad dtype %d", d.dtype);
+    const int epc = d.dtype == FFN_F32 ? 4 : 8;
+    REQUIRE(d.C > 0 && d.C % 4 == 0 && d.E >= 1 && d.K >= 1 && d.h >= 1 && d.w >= 1 && d.H >= 1 && d.W >= 1,
+            "dift_match: bad shape E=%d C=%d h=%d w=%d H=%d W=%d K=%d (C %% 4 == 0, everything else >= 1)", d.E, d.C, d.h, d.w, d.H, d.W, d.K);
+    REQUIRE((long)d.H * d.W < (1l << 31) && (long)d.h * d.w < (1l << 31), "dift_match: H * W and h * w must be below 2^31");
+    REQUIRE(d.ld >= d.C && d.ld % epc == 0 && d.es >= 0 && d.es % epc == 0, "dift_match: ld=%d (>= C=%d) and es=%ld must be multiples of %d", d.ld, d.C, d.es, epc);
+    REQUIRE(d.src && d.tgt && d.kps && d.ws && d.out_rc && d.out_cos && aligned16(d.src) && aligned16(d.tgt) && aligned16(d.ws), "dift_match: null / unaligned pointer");
+    const long need = fdift_ws_bytes(d.C, d.h, d.w, d.K);
+    REQUIRE(d.ws_bytes >= need, "dift_match: workspace of %ld bytes, %ld needed (ffn_dift_workspace_bytes)", d.ws_bytes, need);
+    for (int k = 0; k < d.K; ++k)
+        REQUIRE(d.kps[2 * k] >= 0 && d.kps[2 * k] < d.H && d.kps[2 * k + 1] >= 0 && d.kps[2 * k + 1] < d.W, "dift_match: keypoint %d = (%d, %d) outside [0, %d) x [0, %d)", k,
+                d.kps[2 * k], d.kps[2 * k + 1], d.H, d.W);
+    fdift_launch(reinterpret_cast<hipStream_t>(stream), &d);
+    return check_launch("dift_match");
 }
 
 // ---- elementwise / resampling helpers of the depth front end ----------------------------------------------------------

@@ -1,8 +1,17 @@
-"""The model-free arithmetic of the GeoBench metric suite (/root/reference/evaluation/metrics/): warp error, the Frechet distance between two
-Gaussians of features, and the polynomial-kernel MMD^2 (the "kernel distance" of fid_kd.py).  The feature extractors the reference feeds them with
-(Inception-v3, DINOv2, CLIP, HPSv2, ImageReward, DIFT) need model weights that do not exist offline and are NOT built; these functions take
-features / images and are pinned to the reference's own functions by tests/golden/g11_metrics.npz (tools/gen_golden.py run_g11).
-Host-side numpy: a metric pass is a few reductions over at most thousands of feature rows."""
+"""The GeoBench metric suite (/root/reference/evaluation/metrics/) as far as it can be built offline.
+
+Model-free arithmetic: warp error, the Frechet distance between two Gaussians of features, and the polynomial-kernel MMD^2 (the "kernel distance" of
+fid_kd.py).  The feature extractors the reference feeds the last two with (Inception-v3, DINOv2, CLIP, HPSv2, ImageReward) need model weights that do not
+exist offline and are NOT built; these functions take features / images and are pinned to the reference's own functions by tests/golden/g11_metrics.npz
+(tools/gen_golden.py run_g11).  Host-side numpy: a metric pass is a few reductions over at most thousands of feature rows.
+
+Mean Distance (MD/mean_distance.py), the one metric of the suite that measures the GEOMETRY of an edit, needs no foreign network: its feature extractor is
+DIFT, i.e. Stable Diffusion itself, and runs on the project's kernels (freefine_amd/dift.py: HipVAE + HipUNet.features; the correspondence search is
+ops.dift_match).  transform_coordinates / mean_distance / calculate_md below are the metric; the coordinate maps are pinned to the reference's
+get_transform_coordinates by tests/golden/g13_md_coords.npz (tools/gen_golden.py run_g13; translation and uniform scale -- the rotation branch calls cv2 there
+and is pinned only to the documented matrix formula, src/utils/vis_utils.py::_rotation_matrix_2d).  The reference finds its keypoints with cv2 SIFT / ORB, which
+exists neither here nor is restated: keypoints are supplied by the caller or come from a documented deterministic sampler, and MD values are comparable to
+the reference's only when the same keypoints are supplied."""
 import numpy as np
 
 
@@ -79,3 +88,96 @@ def kernel_distance(feat_real, feat_gen, n_subsets=100, subset_size=1000, rng=No
         r = feat_gen[rng.choice(len(feat_gen), m, replace=False)]
         out[i] = polynomial_mmd2(g, r)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# Mean Distance (MD/mean_distance.py)
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+def transform_coordinates(edit_param, size, mask, path_3D=None):
+    """mean_distance.py:get_transform_coordinates (:81-108): [size[0], size[1], 2] float64, where the edit should have moved every pixel (row, col).  Quirks kept:
+    the translation branch (edit_param[0] = dx or edit_param[1] = dy non-zero) is (row + dy, col + dx); the rotation (edit_param[5], degrees) / uniform scale
+    (edit_param[6] == edit_param[7]) branch works about scipy.ndimage.center_of_mass(mask), a (row, col) pair passed UNCHANGED as the centre of a matrix that
+    is applied to (row, col, 1) points; otherwise the correspondence file `path_3D` (.npy) with its last axis reversed.  The rotation matrix is
+    cv2.getRotationMatrix2D as restated by src/utils/vis_utils.py::_rotation_matrix_2d (pinned to that formula only: no cv2 here to record a golden)."""
+    if edit_param[0] != 0 or edit_param[1] != 0:
+        rows, cols = np.meshgrid(np.arange(size[0]), np.arange(size[1]), indexing="ij")
+        return np.stack([rows + edit_param[1], cols + edit_param[0]], axis=-1).astype(np.float64)
+    if edit_param[5] != 0 or edit_param[6] != 1:
+        from scipy.ndimage import center_of_mass
+        center = center_of_mass(np.asarray(mask))
+        if edit_param[5] != 0:
+            from src.utils.vis_utils import _rotation_matrix_2d
+            matrix = _rotation_matrix_2d(center, edit_param[5], 1.0)
+        else:
+            assert edit_param[6] == edit_param[7], "uniform scale only"
+            scale = edit_param[6]
+            matrix = np.array([[scale, 0, (1 - scale) * center[0]], [0, scale, (1 - scale) * center[1]]])
+        rows, cols = np.meshgrid(np.arange(size[0]), np.arange(size[1]), indexing="ij")
+        points = np.stack((rows, cols, np.ones_like(rows)), axis=-1).reshape(-1, 3)
+        return np.dot(points, matrix.T).reshape(size[0], size[1], 2)
+    return np.load(path_3D)[..., ::-1].copy()
+
+
+def default_keypoints(mask, max_points=30):
+    """The keypoints used when the caller supplies none -- NOT the reference's (cv2 SIFT matches with an ORB fallback, mean_distance.py:28-79): the pixels with
+    mask >= 0.5 in row-major order, every s-th of them with s = ceil(count / max_points), i.e. at most max_points points spread over the object.  Deterministic.
+    -> int array [n, 2] of (row, col); an empty mask gives no points (the case then contributes nothing, like the reference's `continue`)."""
+    pts = np.argwhere(np.asarray(mask) >= 0.5)
+    if len(pts) == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    step = -(-len(pts) // max_points)
+    return pts[::step]
+
+
+def mean_distance(featurizer, src_img, gen_img, mask, edit_param, prompt, keypoints, path_3D=None, max_points=30, **featurizer_kw):
+    """One case of mean_distance.py:calculate_md (:119-165) -> the list of distances of its keypoints.  src_img / gen_img: uint8 HWC arrays; mask: HW array in
+    [0, 255]; keypoints: [[row, col], ...] on the source image (the first max_points are used).  The generated image and the mask are resized to the source
+    size with PIL BILINEAR and the mask divided by 255 (the reference passes shape[:-1] = (H, W) where PIL wants (W, H): the same for the square images of
+    GeoBench; here the source size is meant).  featurizer: freefine_amd.dift.HipSDFeaturizer; featurizer_kw (t, up_ft_index, ensemble_size, noise,
+    noise_edited, generator) go to its pair().  Per keypoint: the best cosine match of the source feature among the edited image's features, both upsampled
+    bilinearly to the image size (ops.dift_match), and its distance to where the edit should have moved the keypoint."""
+    from PIL import Image
+    from . import ops
+    src_img = np.asarray(src_img)
+    H, W = src_img.shape[:2]
+    gen_img = np.array(Image.fromarray(np.asarray(gen_img)).resize((W, H), Image.BILINEAR))
+    mask = np.array(Image.fromarray(np.asarray(mask)).resize((W, H), Image.BILINEAR)) / 255.0
+    kps = np.asarray(keypoints(src_img, gen_img, mask) if callable(keypoints) else keypoints).reshape(-1, 2)[:max_points].astype(np.int64)
+    if len(kps) == 0:
+        return []
+    rows_s, rows_e, hw = featurizer.pair(src_img, gen_img, prompt, **featurizer_kw)
+    rc, _ = ops.dift_match(rows_s, rows_e, hw, (H, W), kps)
+    rc = rc.cpu().numpy()
+    t_coords = transform_coordinates(edit_param, (H, W), mask, path_3D)
+    out = []
+    for k, m in zip(kps, rc):
+        d = (t_coords[k[0], k[1]] - m.astype(np.float64)).astype(np.float32)      # (tp - max_rc).float().norm()
+        out.append(float(np.sqrt(np.sum(d * d, dtype=np.float32))))
+    return out
+
+
+def calculate_md(data, image_label, pipe, keypoints=None, reader=None, max_points=30, **featurizer_kw):
+    """mean_distance.py:calculate_md over a GeoBench result tree data[image]["instances"][instance][sample] with ori_img_path / <image_label> / ori_mask_path /
+    edit_param / obj_label (the prompt) -> the mean distance over all keypoints of all cases.  pipe: a FreeFinePipeline (its checkpoint is the feature
+    extractor: freefine_amd/dift.py states the two deviations from the reference's SDFeaturizer) or a ready HipSDFeaturizer.  keypoints: a callable
+    (src_img, gen_img, mask / 255) -> [[row, col], ...]; None -> the sample's own "keypoints" list when it has one, else default_keypoints(mask).  MD values are
+    comparable to the reference's only when the reference's keypoints are supplied.  `reader` maps a path to an array (default: PIL)."""
+    from .dift import HipSDFeaturizer
+    if reader is None:
+        from PIL import Image
+        reader = lambda p: np.array(Image.open(p))
+    feat = pipe if isinstance(pipe, HipSDFeaturizer) else HipSDFeaturizer(pipe)
+    dists = []
+    for image in data.values():
+        for instance in image["instances"].values():
+            for sample in instance.values():
+                gen_path = sample[image_label]
+                parts = str(gen_path).split("/")
+                # the correspondence file of a 3-D edit, where the reference looks for it (mean_distance.py:121-122)
+                path_3D = str(gen_path).replace("zkl", "Hszhu").replace(parts[-4], "correspondence").replace(".png", ".npy") if len(parts) >= 4 and parts[-4] else None
+                kp = keypoints
+                if kp is None:
+                    kp = sample["keypoints"] if "keypoints" in sample else (lambda s, g, m: default_keypoints(m, max_points))
+                dists += mean_distance(feat, reader(sample["ori_img_path"]), reader(gen_path), reader(sample["ori_mask_path"]), sample["edit_param"],
+                                       sample["obj_label"], kp, path_3D, max_points, **featurizer_kw)
+    return float(np.mean(np.asarray(dists, dtype=np.float32))) if dists else float("nan")

@@ -6,6 +6,7 @@ import ctypes as CT
 import math
 
 import os
+import threading
 
 import torch
 
@@ -336,6 +337,30 @@ def _workspace(device):
         ws = _WS[key] = torch.empty(WS_BYTES // 4, dtype=torch.float32, device=device)
     return ws
 
+_TLS = threading.local()      # batch_invariant is per host thread: executors of a shared pipeline run on threads of their own
+
+
+def _invariant():
+    return getattr(_TLS, "batch_invariant", False)
+
+
+class batch_invariant:
+    """Within this context (per host thread) the launch choices that this module or the library would take from the NUMBER OF ROWS are pinned, so that a
+    row's result does not depend on what is computed beside it (HipUNet.features):
+      * ffn_igemm launches of linear / conv3x3 that leave the K split to the library run unsplit (splitk = 1): the library chooses a split from how many
+        tiles M x N fills the device with; unsplit, every output element is one K-ordered accumulation;
+      * GroupNorm takes the form the library would choose for ONE row (ffn_gn_fused(1, ...)): where that is the one-launch fused kernel, the batch goes in
+        chunks of rows small enough to keep it; where it is statistics + apply, any batch takes it anyway.  groupnorm_pair_raw decides the same way.
+    What is NOT pinned: the tile of an unsplit GEMM (rule table in fp32, first-use timing in bf16), which follows M.  HipUNet.features documents what was
+    measured about it."""
+
+    def __enter__(self):
+        self.prev, _TLS.batch_invariant = _invariant(), True
+
+    def __exit__(self, *exc):
+        _TLS.batch_invariant = self.prev
+
+
 def linear(x, w, bias=None, *, K=None, out=None, residual=None, rowbias=None, rows_per_batch=None, silu=False,
            geglu=False, out_f32=False, transposed_ld=None, alpha=1.0, splitk=0, out_pair=False, gelu=False, relu=False, kv64_from=None, qgelu=False):
     """out = x @ w[:, :K]^T (+bias ...).  x: [..., K] contiguous rows (M = prod of leading dims).
@@ -405,6 +430,8 @@ def linear(x, w, bias=None, *, K=None, out=None, residual=None, rowbias=None, ro
         d.kv64_from = int(kv64_from)
         splitk = 1
     d.flags, d.alpha, d.conv = flags, alpha, 0
+    if splitk == 0 and _invariant():
+        splitk = 1
     d.splitk, d.ws, d.ws_bytes = splitk, _workspace(x.device).data_ptr(), WS_BYTES
     if _PROF is None:
         L.check(lib.ffn_igemm(_stream(), dcode, CT.byref(d)), "ffn_igemm")
@@ -453,6 +480,8 @@ def conv3x3(x, w, bias, B, Hin, Win, Cin, *, stride=1, pad=1, upsample=False, ou
     d.Hin, d.Win, d.Cin, d.Hout, d.Wout = Hin, Win, Cin, Hout, Wout
     d.stride, d.pad, d.upsample = stride, pad, 1 if upsample else 0
     d.flags, d.alpha, d.conv = (L.IG_OUT_F32 if out_f32 else 0) | (L.IG_OUT_RELU if relu else 0), (w._ffn_f8[1] if f8 else 1.0), 1
+    if splitk == 0 and _invariant():
+        splitk = 1
     d.splitk, d.ws, d.ws_bytes = splitk, _workspace(x.device).data_ptr(), WS_BYTES
     if _PROF is None:
         L.check(lib.ffn_igemm(_stream(), dcode, CT.byref(d)), "ffn_igemm(conv)")
@@ -662,14 +691,17 @@ def groupnorm(x, gamma, beta, G, eps, silu=False, out=None, ws=None, pair=False)
         out = _mark_pair(torch.empty(B, HW, 2 * Cc, dtype=torch.bfloat16, device=x.device), Cc)
     if out is None:
         out = torch.empty_like(x)
-    if lib.ffn_gn_fused(B, HW, Cc, G):
+    nb = B
+    if _invariant() and lib.ffn_gn_fused(1, HW, Cc, G) and not lib.ffn_gn_fused(B, HW, Cc, G):
+        while not lib.ffn_gn_fused(nb, HW, Cc, G):   # batch_invariant: the form of one row, in chunks of rows that keep the fused kernel
+            nb = (nb + 1) // 2
+    if lib.ffn_gn_fused(nb, HW, Cc, G):
         partial = scale = shift = None
     else:
         partial, scale, shift = ws if ws is not None else gn_workspace(B, HW, Cc, x.device)
     fl = (L.NORM_SILU if silu else 0) | (L.NORM_OUT_PAIR if pair else 0)
     # Row chunks (three-launch form only): statistics and apply of a chunk run back to back, so that the apply pass finds the chunk's input in the
     # 256 MiB Infinity Cache instead of fetching it from HBM a second time (the three-launch form reads x twice: 12 bytes per element moved for 8).
-    nb = B
     if partial is not None and _GN_CHUNK_MB > 0 and x.is_contiguous() and out.is_contiguous():
         row_bytes = HW * Cc * x.element_size()
         nb = max(1, min(B, int(_GN_CHUNK_MB * 2 ** 20) // row_bytes))
@@ -696,7 +728,7 @@ def groupnorm_pair_raw(x, gamma, beta, G, eps, silu=False, ws=None):
     the second is what split_pair(x) would give, bit for bit.  Shapes the one-launch fused GroupNorm takes (small tensors) keep that kernel + a split_pair pass."""
     lib = L.load()
     B, HW, Cc = x.shape
-    if not _GN_RAW or Cc % 8 != 0 or lib.ffn_gn_fused(B, HW, Cc, G) or not x.is_contiguous():
+    if not _GN_RAW or Cc % 8 != 0 or lib.ffn_gn_fused(1 if _invariant() else B, HW, Cc, G) or not x.is_contiguous():
         return groupnorm(x, gamma, beta, G, eps, silu=silu, pair=True, ws=ws), split_pair(x, Cc)
     assert x.dtype == torch.float32
     y = _mark_pair(torch.empty(B, HW, 2 * Cc, dtype=torch.bfloat16, device=x.device), Cc)
@@ -927,6 +959,43 @@ def embed_tokens(ids, table, pos, dtype, out=None):
     else:
         L.check(_timed(f"embed_tokens_kernel<{_tname(out)}>", 0.0, (4.0 + out.element_size()) * out.numel(), call), "ffn_embed_tokens")
     return out
+
+
+_DIFT_WS = {}
+
+
+def dift_match(rows_src, rows_tgt, hw, HW, kps):
+    """The correspondence search of the Mean Distance metric (ffn_dift_match; csrc/dift_match.h).  rows_src / rows_tgt: DIFT activation rows [E, h*w, C] of the
+    source and the edited image (fp32 or bf16; rows may be strided, rows.stride(1) >= C, as HipUNet.features leaves them); hw = (h, w); HW = (H, W) the image size;
+    kps: K keypoints (row, col) at image resolution, host integers.  For every keypoint: the pixel of the edited image whose bilinearly upsampled feature has
+    the largest cosine with the source image's upsampled feature at the keypoint (ensemble means over E; numpy's argmax tie rule).
+    -> (rc int32 [K, 2], cos float32 [K]) on the device."""
+    import numpy as np
+    lib = L.load()
+    assert rows_src.ndim == 3 and rows_src.shape == rows_tgt.shape and rows_src.dtype == rows_tgt.dtype and rows_src.device == rows_tgt.device
+    assert rows_src.stride(2) == 1 and rows_tgt.stride() == rows_src.stride(), "source and target rows share one layout"
+    E, n, C = rows_src.shape
+    (h, w), (H, W) = hw, HW
+    assert n == h * w, (n, h, w)
+    kp = np.ascontiguousarray(np.asarray(kps).reshape(-1, 2), dtype=np.int32)
+    K = kp.shape[0]
+    key = (rows_src.device, torch.cuda.current_stream().cuda_stream, C, h, w, K)          # one buffer per stream, like the split-K scratch
+    ws = _DIFT_WS.get(key)
+    if ws is None:
+        nbytes = lib.ffn_dift_workspace_bytes(C, h, w, K)
+        if nbytes < 0:
+            L.check(int(nbytes), "ffn_dift_workspace_bytes")
+        if len(_DIFT_WS) > 16:
+            _DIFT_WS.clear()
+        ws = _DIFT_WS[key] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=rows_src.device)
+    rc = torch.empty(K, 2, dtype=torch.int32, device=rows_src.device)
+    cos = torch.empty(K, dtype=torch.float32, device=rows_src.device)
+    d = L.DiftDesc()
+    d.src, d.tgt, d.kps, d.ws, d.out_rc, d.out_cos = rows_src.data_ptr(), rows_tgt.data_ptr(), kp.ctypes.data, ws.data_ptr(), rc.data_ptr(), cos.data_ptr()
+    d.ws_bytes, d.es = ws.numel() * 4, (rows_src.stride(0) if E > 1 else 0)
+    d.dtype, d.E, d.C, d.ld, d.h, d.w, d.H, d.W, d.K = _dt(rows_src), E, C, rows_src.stride(1), h, w, H, W, K
+    L.check(_timed("dift_match", 2.0 * (K + 5) * n * C, (2.0 * E * n * C) * rows_src.element_size(), lambda: lib.ffn_dift_match(_stream(), CT.byref(d))), "ffn_dift_match")
+    return rc, cos
 
 
 def image_to_nhwc(img_u8, CP, dtype, out=None):

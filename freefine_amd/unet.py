@@ -306,6 +306,33 @@ class HipUNet:
             self.last_boundary, self.last_kv = g["boundary"], g["kv"]
         return self._expand(g["out"].clone())
 
+    def features(self, sample, timestep, enc, up_ft_index):
+        """The activations at the end of up block `up_ft_index` -- diffusers' block boundary, the block's upsampler included, which is what DIFT records
+        (the reference's evaluation/metrics/MD/dift_sd.py:124-155); nothing after that block is executed.  sample [B,Cin,h,w] fp32, enc [B,77,D] ->
+        (rows [B, H*W, C] in the activation dtype, (H, W)).  The rows are returned where the executor left them: an up block that is not the last writes
+        its output into the left columns of the next concatenation buffer, so rows.stride(1) may exceed C (no copy is made).  Plain attention whatever
+        controller is registered (it is set aside for the call and put back), none of the reuse modes, always eager: no graph is captured or replayed.
+        State shared with forward(): the per-call fields `_row_map`, `_reuse`, `_enc_rows` and the device timestep `t_dev` are overwritten, and the static
+        per-shape text K / V buffers (which captured graphs point at) are recomputed in place for `enc`; forward() sets the former on every call and
+        prepare_text re-projects the latter as soon as another tensor arrives, so a forward() after features() computes what it did before.
+        Batch invariance: the launch choices taken from the number of rows are pinned (ops.batch_invariant: no K split, GroupNorm in the form of one row) and
+        the upsamplers run as plain convolutions (the sub-pixel form is chosen by the row count).  The tile of an unsplit GEMM still follows M; a tile
+        changes which workgroup computes an element, not the K order of its accumulation.  Tested: a row's features are bit-identical at 6, 24 and 48 rows
+        on the tiny topology in all three modes, across the GroupNorm threshold (tests/test_dift_gpu.py).  Beyond what is tested -- the SD-2.1 size has
+        not been measured -- this is a property the pinned choices are meant to give, not a guarantee of the library."""
+        n = len(self.up)
+        assert isinstance(up_ft_index, int) and 0 <= up_ft_index < n, f"up_ft_index {up_ft_index} outside [0, {n})"
+        sample = sample.to(self.device, torch.float32).contiguous()
+        ctrl, self.controller = self.controller, None
+        try:
+            self._row_map, self._reuse, self._enc_rows = None, None, enc.shape[0]
+            self.t_dev.fill_(float(timestep))
+            with ops.batch_invariant():
+                x, H, W = self._run(sample, self.prepare_text(enc), stop_up=up_ft_index)
+        finally:
+            self.controller = ctrl
+        return x, (H, W)
+
     @staticmethod
     def _launch(g):
         """replay a captured forward.  Through the C ABI (ffn_graph_launch = hipGraphLaunch on the current stream): a ctypes call releases the GIL,
@@ -726,7 +753,9 @@ class HipUNet:
         h = ops.linear(y, t.ff2[0], t.ff2[1], K=4 * C, residual=h, out_pair=self.x3 and C % 32 == 0)
         return ops.linear(h, t.proj_out[0], t.proj_out[1], K=C, residual=res0, out=out)
 
-    def _run(self, sample, text_kv):
+    def _run(self, sample, text_kv, stop_up=None):
+        """stop_up (HipUNet.features): return (activation rows, H, W) at the end of up block `stop_up`, its upsampler included, instead of eps; the
+        upsamplers then take the plain convolution whatever the batch (the sub-pixel form is chosen by the row count and sums in another order)"""
         cfg = self.cfg
         B, _, H, W = sample.shape
         dt = self.dtype
@@ -808,11 +837,13 @@ class HipUNet:
                         B, temb_all = x.shape[0], temb_full[:x.shape[0]]
             if blk.up is not None:
                 C = x.shape[-1]
-                if blk.up2 is not None and ops.up2x_eligible(C, C, B * H * W):
+                if blk.up2 is not None and stop_up is None and ops.up2x_eligible(C, C, B * H * W):
                     x = ops.conv3x3_up2x(x, blk.up2, blk.up[1], B, H, W, C, out=cat_dst(C, 4 * H * W))
                 else:
                     x = ops.conv3x3(x, blk.up[0], blk.up[1], B, H, W, C, upsample=True, out=cat_dst(C, 4 * H * W))
                 H, W = 2 * H, 2 * W
+            if stop_up is not None and i == stop_up:
+                return x, H, W
         C = x.shape[-1]
         if self.conv_out_n4 is not None:
             x = ops.groupnorm(x, self.norm_out[0], self.norm_out[1], cfg.norm_num_groups, cfg.norm_eps, silu=True)      # plain activations (no pair rows)

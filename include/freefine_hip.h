@@ -333,6 +333,30 @@ int ffn_embed_tokens(void* stream, int dtype, const int* ids, const float* table
 int ffn_image_to_nhwc(void* stream, int dtype, const uint8_t* img, void* dst, long npix, int CP);
 int ffn_nhwc_to_image(void* stream, int dtype, const void* src, float* dst, int B, int HW, int ld);
 
+/* ---- DIFT correspondence search of the Mean Distance metric --------------------------------------------------------------------------
+ * Reference: evaluation/metrics/MD/mean_distance.py:139-165 -- both DIFT feature maps upsampled bilinearly to the image size (F.interpolate), then per keypoint
+ * the argmax over all pixels of CosineSimilarity(dim=1) between the source feature at the keypoint and the edited image's features.  Here the upsampled maps are
+ * never formed (csrc/dift_match.h: bilinear interpolation is linear, so every cosine is a few FMAs over low-resolution dot products).
+ * src / tgt: the activation rows [E][h*w][ld] (first C columns used, ld >= C; `es` elements between ensemble members) of the source and the edited image, fp32
+ * (FFN_F32) or bf16 (FFN_BF16); the ensemble mean over E is taken in fp32.  kps: HOST int32 [K][2] = (row, col) in [0, H) x [0, W), read before the call returns
+ * (they travel as kernel arguments).  out_rc: device int32 [K][2] = (row, col) of the match, numpy's argmax rule (lowest flat index row * W + col among equal
+ * cosines; NaN never wins); out_cos: device float [K], the cosine there, cos = dot / (max(|q|, 1e-8) * max(|f|, 1e-8)).  Deterministic: no atomics.
+ * ws: ffn_dift_workspace_bytes(C, h, w, K) bytes of 16-byte aligned device scratch.  C % 4 == 0; ld, es multiples of the 16-byte chunk (4 fp32 / 8 bf16);
+ * H * W < 2^31.  Any K (the library loops over groups of keypoints). */
+typedef struct ffn_dift_desc {
+    const void* src;
+    const void* tgt;
+    const int* kps;
+    void* ws;
+    int* out_rc;
+    float* out_cos;
+    long ws_bytes;
+    long es;
+    int dtype, E, C, ld, h, w, H, W, K;
+} ffn_dift_desc;
+int ffn_dift_match(void* stream, const ffn_dift_desc* d);
+long ffn_dift_workspace_bytes(int C, int h, int w, int K);
+
 #ifdef __cplusplus
 }
 #endif

@@ -714,8 +714,31 @@ def run_g11():
     print(f"[G11] frechet {out['frechet']}, mmd2 {out['mmd2']}, kd mean {out['kd'].mean():.6f}, warp error {out['we'][0]:.6f}")
 
 
+# --------------------------------------------------------------------------------------------------------------
+# G13: the coordinate maps of the Mean Distance metric (evaluation/metrics/MD/mean_distance.py:get_transform_coordinates), translation and
+# uniform-scale branches (the rotation branch calls cv2.getRotationMatrix2D, absent here: pinned to the documented matrix formula only)
+# --------------------------------------------------------------------------------------------------------------
+def run_g13():
+    import types
+    mroot = os.path.join(RH.REF, "evaluation", "metrics")
+    if mroot not in sys.path:
+        sys.path.insert(0, mroot)
+    sys.modules["diffusers"].UNet2DConditionModel = type("UNet2DConditionModel", (), {})      # base class of dift_sd.py's UNet, imported beside the function taken
+    from MD.mean_distance import get_transform_coordinates
+    size = (12, 10)
+    mask = np.zeros(size, dtype=np.float64)
+    mask[2:7, 5:9] = 1.0                                  # small off-centre rectangle
+    out = {"mask": mask}
+    for name, ep in (("trans_a", [3, -2, 0, 0, 0, 0, 1, 1, 1]), ("trans_b", [0, 4, 0, 0, 0, 0, 1, 1, 1]),
+                     ("scale_a", [0, 0, 0, 0, 0, 0, 1.5, 1.5, 1]), ("scale_b", [0, 0, 0, 0, 0, 0, 0.7, 0.7, 1])):
+        out[f"{name}_param"] = np.asarray(ep, dtype=np.float64)
+        out[f"{name}_coords"] = np.asarray(get_transform_coordinates(ep, size, mask, None), dtype=np.float64)
+    np.savez_compressed(os.path.join(GOLD, "g13_md_coords.npz"), **out)
+    print("[G13] " + ", ".join(f"{k} {v.shape}" for k, v in out.items() if k.endswith("_coords")))
+
+
 if __name__ == "__main__":
-    only = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g6b", "g7", "g8", "g9", "g11"]
+    only = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g6b", "g7", "g8", "g9", "g11", "g13"]
     torch.set_grad_enabled(False)
     A, Mo = RH.import_reference()
     if "g1" in only:
@@ -738,3 +761,5 @@ if __name__ == "__main__":
         run_g9(A, Mo)
     if "g11" in only:
         run_g11()
+    if "g13" in only:
+        run_g13()
