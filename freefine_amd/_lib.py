@@ -15,6 +15,7 @@ ELT_RELU, ELT_ADD = 0, 1
 ATT_MAXP, ATT_MAXB = 4, 16
 ATT_HEAD_RULE, ATT_UNIFORM_SEL1, ATT_UNIFORM_SEL0, ATT_CAUSAL = 1, 2, 4, 8
 NORM_SILU, NORM_OUT_PAIR = 1, 2
+IMGPREP_MAX_SIDE = 4096      # FFN_IMGPREP_MAX_SIDE
 
 
 class IgemmDesc(C.Structure):
@@ -133,6 +134,8 @@ SYMBOLS = {
     "ffn_embed_tokens": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _l, _i, _i, _i]),
     "ffn_dift_match": (_i, [_vp, C.POINTER(DiftDesc)]),
     "ffn_dift_workspace_bytes": (_l, [_i, _i, _i, _i]),
+    "ffn_resize_pil_bilinear_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i]),
+    "ffn_vit_patch_rows": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "ffn_image_to_nhwc": (_i, [_vp, _i, _vp, _vp, _l, _i]),
     "ffn_nhwc_to_image": (_i, [_vp, _i, _vp, _vp, _i, _i, _i]),
 }

@@ -70,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 4; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match
+extern "C" int ffn_version(void) { return 5; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -1157,6 +1157,38 @@ extern "C" int ffn_dift_match(void* stream, const ffn_dift_desc* dp) {
                 d.kps[2 * k], d.kps[2 * k + 1], d.H, d.W);
     fdift_launch(reinterpret_cast<hipStream_t>(stream), &d);
     return check_launch("dift_match");
+}
+
+// ---- device image preparation of the DINOv2 feature metrics (kernels and launches: imgprep.hip / imgprep.h) ----------------------------------------
+extern "C" __attribute__((visibility("hidden"))) void fimgprep_resize(hipStream_t s, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int oh, int ow,
+                                                                      const int* hb, const int* hk, int hks, const int* vb, const int* vk, int vks);
+extern "C" __attribute__((visibility("hidden"))) void fimgprep_patch_rows(hipStream_t s, int dtype, const uint8_t* src, const float* lut, void* out, int B, int H, int W,
+                                                                          int ps, int ldo);
+
+static inline int pil_ksize(int in, int out) { return 2 * (in > out ? (in + out - 1) / out : 1) + 1; }      // 2 ceil(max(in / out, 1)) + 1
+
+extern "C" int ffn_resize_pil_bilinear_u8(void* stream, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int oh, int ow,
+                                          const int* hbounds, const int* hcoef, int hksize, const int* vbounds, const int* vcoef, int vksize) {
+    const int lim = FFN_IMGPREP_MAX_SIDE;
+    REQUIRE(src && dst && scratch && hbounds && hcoef && vbounds && vcoef, "resize_pil_bilinear_u8: null pointer");
+    REQUIRE(B >= 1 && B <= 65535, "resize_pil_bilinear_u8: B=%d outside 1 .. 65535", B);
+    REQUIRE(H >= 1 && W >= 1 && H <= lim && W <= lim, "resize_pil_bilinear_u8: source %d x %d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE)", H, W, lim);
+    REQUIRE(oh >= 1 && ow >= 1 && oh <= lim && ow <= lim, "resize_pil_bilinear_u8: destination %d x %d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE)", oh, ow, lim);
+    REQUIRE(hksize == pil_ksize(W, ow) && vksize == pil_ksize(H, oh), "resize_pil_bilinear_u8: table widths %d, %d; %d -> %d and %d -> %d need %d, %d", hksize, vksize, W, ow,
+            H, oh, pil_ksize(W, ow), pil_ksize(H, oh));
+    fimgprep_resize(reinterpret_cast<hipStream_t>(stream), src, dst, scratch, B, H, W, oh, ow, hbounds, hcoef, hksize, vbounds, vcoef, vksize);
+    return check_launch("resize_pil_bilinear_u8");
+}
+
+extern "C" int ffn_vit_patch_rows(void* stream, int dtype, const uint8_t* src, const float* lut, void* out, int B, int H, int W, int patch, int ldo) {
+    const int lim = FFN_IMGPREP_MAX_SIDE;
+    REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16, "vit_patch_rows: bad dtype %d", dtype);
+    REQUIRE(src && lut && out, "vit_patch_rows: null pointer");
+    REQUIRE(B >= 1 && H >= 1 && W >= 1 && H <= lim && W <= lim, "vit_patch_rows: bad shape B=%d, %d x %d (sides 1 .. %d, FFN_IMGPREP_MAX_SIDE)", B, H, W, lim);
+    REQUIRE(patch >= 1 && patch <= 256 && H % patch == 0 && W % patch == 0, "vit_patch_rows: %d x %d is not whole patches of %d (1 .. 256)", H, W, patch);
+    REQUIRE(ldo >= 3 * patch * patch, "vit_patch_rows: ldo=%d below the %d columns of a patch", ldo, 3 * patch * patch);
+    fimgprep_patch_rows(reinterpret_cast<hipStream_t>(stream), dtype, src, lut, out, B, H, W, patch, ldo);
+    return check_launch("vit_patch_rows");
 }
 
 // ---- elementwise / resampling helpers of the depth front end ----------------------------------------------------------

@@ -1,0 +1,90 @@
+// Device image preparation of the DINOv2 feature metrics (FID-DINO, Kernel Distance): from the decoded uint8 image to the operand rows of the patch-embedding GEMM.
+//
+//   resize_h_kernel / resize_v_kernel   PIL's Image.resize(BILINEAR) on 8-bit images restated: two separable passes in int32 with 22-bit fixed-point
+//                                       coefficients (PIL libImaging/Resample.c: ImagingResampleHorizontal_8bpc / ImagingResampleVertical_8bpc,
+//                                       PRECISION_BITS = 32 - 8 - 2).  The coefficient tables are built on the host (ops.pil_bilinear_coeffs); the kernels only
+//                                       multiply, add, shift and clamp, so the result does not depend on the compiler's floating point.
+//   patch_rows_kernel                   ToTensor + Normalize as a [3][256] lookup (evaluated on the host by torch) and the im2col of a ViT patch embedding
+//                                       (Conv2d(kernel = stride = patch)): one row per patch, columns (channel, ky, kx), zero padding up to ldo.
+//
+// Traffic is small (a 512 x 512 image is 768 KB in, 147 KB out), so the kernels are plain: byte loads that are contiguous across a workgroup's threads
+// (bytes along an image row are contiguous over (x, c)), no vector loads (an image row starts at any byte address).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/freefine_hip.h"
+#include "common.h"
+
+// largest side of a source or destination image: one source row (3 * IMGPREP_MAX_SIDE bytes) is staged in LDS by the horizontal pass
+#define IMGPREP_MAX_SIDE FFN_IMGPREP_MAX_SIDE
+#define IMGPREP_THREADS 256
+
+__device__ __forceinline__ uint8_t imgprep_clip8(int acc) {
+    acc >>= 22;
+    return (uint8_t)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
+}
+
+// Horizontal pass: src [B][H][W][3] -> dst [B][H][ow][3].  One workgroup per source row (grid = (H, B)): the row is staged in LDS, then one thread per
+// output byte (xx, c).  bounds [ow][2] = (xmin, n), coef [ow][ksize].  (xmin, n) are clamped into the row: a bad table cannot make the kernel read outside it.
+__global__ __launch_bounds__(IMGPREP_THREADS) void resize_h_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int W, int ow,
+                                                                   const int* __restrict__ bounds, const int* __restrict__ coef, int ksize) {
+    __shared__ uint8_t row[3 * IMGPREP_MAX_SIDE];
+    const long r = (long)blockIdx.y * gridDim.x + blockIdx.x;              // row index over (b, y)
+    const uint8_t* s = src + r * W * 3;
+    for (int i = threadIdx.x; i < W * 3; i += IMGPREP_THREADS) row[i] = s[i];
+    __syncthreads();
+    uint8_t* d = dst + r * ow * 3;
+    for (int o = threadIdx.x; o < ow * 3; o += IMGPREP_THREADS) {
+        const int xx = o / 3, c = o - 3 * xx;
+        int xmin = bounds[2 * xx], n = bounds[2 * xx + 1];
+        xmin = xmin < 0 ? 0 : (xmin > W - 1 ? W - 1 : xmin);
+        n = n > ksize ? ksize : n;
+        n = n > W - xmin ? W - xmin : n;
+        const int* k = coef + (long)xx * ksize;
+        int acc = 1 << 21;
+        for (int x = 0; x < n; ++x) acc += (int)row[(xmin + x) * 3 + c] * k[x];
+        d[o] = imgprep_clip8(acc);
+    }
+}
+
+// Vertical pass: src [B][H][ow][3] -> dst [B][oh][ow][3].  One workgroup per output row and 256 consecutive bytes of it (grid = (ceil(3 ow / 256), oh, B)):
+// the row's coefficients are the same for the whole workgroup, every source row is read with contiguous bytes.
+__global__ __launch_bounds__(IMGPREP_THREADS) void resize_v_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int oh, int row_bytes,
+                                                                   const int* __restrict__ bounds, const int* __restrict__ coef, int ksize) {
+    const int o = blockIdx.x * IMGPREP_THREADS + threadIdx.x;
+    if (o >= row_bytes) return;
+    const int yy = blockIdx.y;
+    int ymin = bounds[2 * yy], n = bounds[2 * yy + 1];
+    ymin = ymin < 0 ? 0 : (ymin > H - 1 ? H - 1 : ymin);
+    n = n > ksize ? ksize : n;
+    n = n > H - ymin ? H - ymin : n;
+    const int* k = coef + (long)yy * ksize;
+    const uint8_t* s = src + ((long)blockIdx.z * H + ymin) * row_bytes + o;
+    int acc = 1 << 21;
+    for (int y = 0; y < n; ++y) acc += (int)s[(long)y * row_bytes] * k[y];
+    dst[((long)blockIdx.z * oh + yy) * row_bytes + o] = imgprep_clip8(acc);
+}
+
+// Patch rows: src [B][H][W][3] uint8 -> out [B * (H / ps) * (W / ps)][ldo] of T; column j = (c, ky, kx) holds lut[c][src[b][py ps + ky][px ps + kx][c]],
+// columns 3 ps ps .. ldo - 1 are zero.  One thread per output element (grid-stride): the writes of a workgroup are contiguous.
+template <typename T>
+__global__ __launch_bounds__(IMGPREP_THREADS) void patch_rows_kernel(const uint8_t* __restrict__ src, const float* __restrict__ lut, T* __restrict__ out, long total,
+                                                                     int H, int W, int ps, int ldo) {
+    __shared__ float tab[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += IMGPREP_THREADS) tab[i] = lut[i];
+    __syncthreads();
+    const int pw = W / ps, ph = H / ps, pp = ps * ps;
+    for (long i = (long)blockIdx.x * IMGPREP_THREADS + threadIdx.x; i < total; i += (long)gridDim.x * IMGPREP_THREADS) {
+        const long m = i / ldo;
+        const int j = (int)(i - m * ldo);
+        float v = 0.f;
+        if (j < 3 * pp) {
+            const int c = j / pp, rem = j - c * pp, ky = rem / ps, kx = rem - ky * ps;
+            const long b = m / ((long)ph * pw);
+            const int p = (int)(m - b * ph * pw), py = p / pw, px = p - py * pw;
+            v = tab[c * 256 + src[((b * H + (long)py * ps + ky) * W + (long)px * ps + kx) * 3 + c]];
+        }
+        DT<T>::st(out + i, v);
+    }
+}

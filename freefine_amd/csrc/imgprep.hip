@@ -1,0 +1,26 @@
+// Fifth translation unit of libfreefine_hip.so: the device image preparation of the DINOv2 feature metrics (imgprep.h).  A unit of its own, like dift.hip, so
+// that it compiles beside capi.hip; default code generation.  capi.o validates the arguments (ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows) and calls the
+// hidden functions below; nothing here is exported.
+#include <hip/hip_runtime.h>
+
+#include "../../include/freefine_hip.h"
+#include "imgprep.h"
+
+extern "C" __attribute__((visibility("hidden"))) void fimgprep_resize(hipStream_t s, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int oh, int ow,
+                                                                      const int* hb, const int* hk, int hks, const int* vb, const int* vk, int vks) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(resize_h_kernel, dim3((unsigned)H, (unsigned)B), dim3(IMGPREP_THREADS), 0, s, src, scratch, W, ow, hb, hk, hks);
+    const int row_bytes = 3 * ow;
+    hipLaunchKernelGGL(resize_v_kernel, dim3((unsigned)((row_bytes + IMGPREP_THREADS - 1) / IMGPREP_THREADS), (unsigned)oh, (unsigned)B), dim3(IMGPREP_THREADS), 0, s,
+                       scratch, dst, H, oh, row_bytes, vb, vk, vks);
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fimgprep_patch_rows(hipStream_t s, int dtype, const uint8_t* src, const float* lut, void* out, int B, int H, int W,
+                                                                          int ps, int ldo) {
+    (void)hipGetLastError();
+    const long total = (long)B * (H / ps) * (W / ps) * ldo;
+    long g = (total + IMGPREP_THREADS - 1) / IMGPREP_THREADS;
+    const unsigned grid = (unsigned)(g > 8192 ? 8192 : g);
+    if (dtype == FFN_BF16) hipLaunchKernelGGL(patch_rows_kernel<bf16>, dim3(grid), dim3(IMGPREP_THREADS), 0, s, src, lut, static_cast<bf16*>(out), total, H, W, ps, ldo);
+    else hipLaunchKernelGGL(patch_rows_kernel<float>, dim3(grid), dim3(IMGPREP_THREADS), 0, s, src, lut, static_cast<float*>(out), total, H, W, ps, ldo);
+}

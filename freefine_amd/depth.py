@@ -2,6 +2,8 @@
 (/root/reference/depth_anything/dpt.py:143-172 DPT_DINOv2.forward, :22-137 DPTHead, blocks.py:38-153,
 torchhub/facebookresearch_dinov2_main/vision_transformer.py:178-317).
 
+The encoder half (weights, tokens, blocks) is dino.py's HipDinoEncoder, shared with the metrics' feature extractor HipDinoV2; this module adds the DPT head.
+
 Same design as unet.py / vae.py: activations are token / NHWC rows, every Linear, 1x1 conv, 3x3 conv, patch embedding and
 transposed conv is an `ffn_igemm` call, LayerNorm and attention are the UNet's kernels (`ffn_layernorm`, `ffn_attn` with head
 dim 64 and the ragged S = 1 + (H/14)(W/14)); what the UNet did not need is in the C ABI as `FFN_IG_OUT_GELU` / `FFN_IG_OUT_RELU`
@@ -17,9 +19,9 @@ import math
 from types import SimpleNamespace
 
 import torch
-import torch.nn.functional as F
 
 from . import ops
+from .dino import HipDinoEncoder, _O, dinov2_param_shapes
 
 
 def depth_config(name="vitl"):
@@ -34,17 +36,8 @@ def depth_config(name="vitl"):
 
 def depth_param_shapes(cfg):
     """name -> shape of DPT_DINOv2(encoder, features, out_channels, use_bn=False, use_clstoken=False).state_dict() (dpt.py:143-153)"""
-    C, hid = cfg.embed_dim, cfg.embed_dim * cfg.mlp_ratio
-    n = (cfg.img_size // cfg.patch) ** 2
-    sh = {"pretrained.cls_token": (1, 1, C), "pretrained.pos_embed": (1, n + 1, C), "pretrained.mask_token": (1, C),
-          "pretrained.patch_embed.proj.weight": (C, 3, cfg.patch, cfg.patch), "pretrained.patch_embed.proj.bias": (C,),
-          "pretrained.norm.weight": (C,), "pretrained.norm.bias": (C,)}
-    for i in range(cfg.depth):
-        p = f"pretrained.blocks.{i}."
-        sh.update({p + "norm1.weight": (C,), p + "norm1.bias": (C,), p + "attn.qkv.weight": (3 * C, C), p + "attn.qkv.bias": (3 * C,),
-                   p + "attn.proj.weight": (C, C), p + "attn.proj.bias": (C,), p + "ls1.gamma": (C,),
-                   p + "norm2.weight": (C,), p + "norm2.bias": (C,), p + "mlp.fc1.weight": (hid, C), p + "mlp.fc1.bias": (hid,),
-                   p + "mlp.fc2.weight": (C, hid), p + "mlp.fc2.bias": (C,), p + "ls2.gamma": (C,)})
+    C = cfg.embed_dim
+    sh = dinov2_param_shapes(cfg, "pretrained.")
     oc, f = cfg.out_channels, cfg.features
     h = "depth_head."
     for i in range(4):
@@ -85,34 +78,17 @@ def synthetic_state(cfg, seed=0):
     return st
 
 
-class _O:
-    pass
-
-
-class HipDepthAnything:
+class HipDepthAnything(HipDinoEncoder):
     def __init__(self, cfg, state, dtype=torch.bfloat16, device="cuda:0"):
         """state: DPT_DINOv2.state_dict() (`pretrained.*`, `depth_head.*`; use_bn = False, use_clstoken = False)"""
-        assert dtype in (torch.float32, torch.bfloat16)
-        self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
-        C = cfg.embed_dim
-        assert C % cfg.num_heads == 0 and C % 8 == 0 and cfg.features % 16 == 0 and all(c % 8 == 0 for c in cfg.out_channels), \
+        self._init_encoder(cfg, dtype, device)
+        assert cfg.features % 16 == 0 and all(c % 8 == 0 for c in cfg.out_channels), \
             "channel counts must be whole 16-byte chunks (features / 2 feeds a 3x3 conv)"
-        self._pos = {}
         self._pack({k: v.detach().to(self.device, torch.float32) for k, v in state.items()})
 
     # ------------------------------------------------------------------------------------------------------------
-    # weights
+    # weights (the encoder's: dino.py HipDinoEncoder._pack_encoder)
     # ------------------------------------------------------------------------------------------------------------
-    def _lin(self, w, b=None, scale=None, n_pad=None):
-        w = w.reshape(w.shape[0], -1)
-        if scale is not None:                                 # LayerScale folded: gamma * (W x + b)
-            w = w * scale[:, None]
-            b = None if b is None else b * scale
-        if n_pad and n_pad > w.shape[0]:
-            w = torch.cat([w, torch.zeros(n_pad - w.shape[0], w.shape[1], device=w.device)], 0)
-            b = None if b is None else torch.cat([b, torch.zeros(n_pad - b.shape[0], device=b.device)], 0)
-        return ops.pack_linear(w.contiguous(), self.dtype), (None if b is None else b.float().contiguous()), w.shape[1]
-
     def _conv(self, st, name, bias=True):
         w = st[name + ".weight"]
         return ops.pack_conv3x3(w, self.dtype), (st[name + ".bias"].contiguous() if bias else None), w.shape[1]
@@ -126,28 +102,7 @@ class HipDepthAnything:
 
     def _pack(self, st):
         cfg = self.cfg
-        C = cfg.embed_dim
-        p = "pretrained."
-        e = 8
-        K = 3 * cfg.patch * cfg.patch
-        self.kpe = (K + e - 1) // e * e                        # patch-embedding contraction length, padded to whole chunks
-        wpe = torch.zeros(C, self.kpe, device=self.device)
-        wpe[:, :K] = st[p + "patch_embed.proj.weight"].reshape(C, K)
-        self.pe = (ops.pack_linear(wpe, self.dtype), st[p + "patch_embed.proj.bias"].contiguous())
-        self.pos_embed, self.cls_token = st[p + "pos_embed"], st[p + "cls_token"]
-        self.blocks = []
-        for i in range(cfg.depth):
-            b, q = _O(), f"{p}blocks.{i}."
-            b.n1 = (st[q + "norm1.weight"].contiguous(), st[q + "norm1.bias"].contiguous())
-            b.n2 = (st[q + "norm2.weight"].contiguous(), st[q + "norm2.bias"].contiguous())
-            wqkv, bqkv = st[q + "attn.qkv.weight"], st[q + "attn.qkv.bias"]
-            b.qk = self._lin(wqkv[:2 * C], bqkv[:2 * C])        # q | k in one GEMM, V^T from its own (transposed-output) GEMM
-            b.v = self._lin(wqkv[2 * C:], bqkv[2 * C:])
-            b.proj = self._lin(st[q + "attn.proj.weight"], st[q + "attn.proj.bias"], scale=st[q + "ls1.gamma"])
-            b.fc1 = self._lin(st[q + "mlp.fc1.weight"], st[q + "mlp.fc1.bias"])
-            b.fc2 = self._lin(st[q + "mlp.fc2.weight"], st[q + "mlp.fc2.bias"], scale=st[q + "ls2.gamma"])
-            self.blocks.append(b)
-        self.norm = (st[p + "norm.weight"].contiguous(), st[p + "norm.bias"].contiguous())
+        self._pack_encoder(st, "pretrained.")
         h = "depth_head."
         self.projects = [self._lin(st[h + f"projects.{i}.weight"], st[h + f"projects.{i}.bias"]) for i in range(4)]
         self.up0 = self._deconv(st, h + "resize_layers.0", 4)
@@ -166,87 +121,23 @@ class HipDepthAnything:
         self.oc3 = self._lin(st[h + "scratch.output_conv2.2.weight"], st[h + "scratch.output_conv2.2.bias"], n_pad=4)
 
     # ------------------------------------------------------------------------------------------------------------
-    # encoder
+    # encoder (tokens and blocks: dino.py HipDinoEncoder)
     # ------------------------------------------------------------------------------------------------------------
-    def _pos_tokens(self, H, W):
-        """(class row = cls_token + pos[0] [1, C], positional embedding of the H/14 x W/14 patches [N, C]) in the activation dtype --
-        vision_transformer.py:178-209 (bicubic, antialias off, offset 0.1; evaluated once per input size)"""
-        key = (H, W)
-        hit = self._pos.get(key)
-        if hit is not None:
-            return hit
-        cfg = self.cfg
-        pe = self.pos_embed.float()
-        N = pe.shape[1] - 1
-        npatch = (H // cfg.patch) * (W // cfg.patch)
-        patch_pos = pe[:, 1:]
-        if not (npatch == N and H == W):
-            dim = pe.shape[-1]
-            w0, h0 = H // cfg.patch + cfg.interpolate_offset, W // cfg.patch + cfg.interpolate_offset
-            sq = math.sqrt(N)
-            patch_pos = F.interpolate(patch_pos.reshape(1, int(sq), int(sq), dim).permute(0, 3, 1, 2), scale_factor=(float(w0) / sq, float(h0) / sq),
-                                      mode="bicubic", antialias=False)
-            assert int(w0) == patch_pos.shape[-2] and int(h0) == patch_pos.shape[-1]
-            patch_pos = patch_pos.permute(0, 2, 3, 1).reshape(1, -1, dim)
-        cls_row = (self.cls_token.float()[0] + pe[:, 0]).to(self.dtype).contiguous()
-        hit = self._pos[key] = (cls_row, patch_pos[0].to(self.dtype).contiguous())
-        return hit
-
-    @staticmethod
-    def _im2col(x, ps):
-        """[B, 3, H, W] -> [B * (H/ps) * (W/ps), 3 * ps * ps]: one row per patch (row-major over the patch grid), columns ordered (channel, ky, kx)
-        like patch_embed.proj.weight.reshape(C, -1) (patch_embed.py:75: Conv2d(kernel = stride = patch))"""
-        B, Cc, H, W = x.shape
-        ph, pw = H // ps, W // ps
-        return x.reshape(B, Cc, ph, ps, pw, ps).permute(0, 2, 4, 1, 3, 5).reshape(B * ph * pw, Cc * ps * ps)
-
-    @staticmethod
-    def _pixel_shuffle(y, B, H, W, k, cout):
-        """GEMM output [B, H*W, (dy, dx, co)] of a ConvTranspose2d(kernel = stride = k) -> NHWC rows [B, (H k)(W k), co]"""
-        return y.view(B, H, W, k, k, cout).permute(0, 1, 3, 2, 4, 5).reshape(B, H * k * W * k, cout).contiguous()
-
-    def _tokens(self, x):
-        """patch embedding (a GEMM over the im2col view of the image, positional embedding added as the GEMM's residual) + class row"""
-        cfg = self.cfg
-        B, _, H, W = x.shape
-        ps = cfg.patch
-        ph, pw = H // ps, W // ps
-        cols = self._im2col(x.to(self.device, torch.float32), ps)
-        a = torch.zeros(B * ph * pw, self.kpe, dtype=self.dtype, device=self.device)
-        a[:, :cols.shape[1]] = cols.to(self.dtype)
-        cls_row, pos = self._pos_tokens(H, W)
-        res = pos.unsqueeze(0).expand(B, -1, -1).reshape(B * ph * pw, -1).contiguous()
-        t = ops.linear(a, self.pe[0], self.pe[1], K=self.kpe, residual=res)
-        return torch.cat([cls_row.unsqueeze(0).expand(B, -1, -1), t.view(B, ph * pw, -1)], dim=1).contiguous(), ph, pw
-
-    def _block(self, b, t, B, S):
-        cfg = self.cfg
-        C, nh = cfg.embed_dim, cfg.num_heads
-        y = ops.layernorm(t, *b.n1, eps=cfg.ln_eps)
-        qk = ops.linear(y, b.qk[0], b.qk[1], K=C)                                   # [B, S, 2C]: q | k
-        vt = ops.linear(y, b.v[0], b.v[1], K=C, rows_per_batch=S, transposed_ld=(S + 7) // 8 * 8)      # V^T [B, C, S']
-        a = ops.attention(qk, qk[..., C:], vt, nh, (C // nh) ** -0.5, None, Sk=S, C=C)
-        t = ops.linear(a, b.proj[0], b.proj[1], K=C, residual=t)                     # x + ls1 * proj(attn)
-        y = ops.layernorm(t, *b.n2, eps=cfg.ln_eps)
-        y = ops.linear(y, b.fc1[0], b.fc1[1], K=C, gelu=True)
-        return ops.linear(y, b.fc2[0], b.fc2[1], K=C * cfg.mlp_ratio, residual=t)    # x + ls2 * fc2(gelu(fc1))
-
     def features(self, x):
         """get_intermediate_layers(x, 4, return_class_token=True, norm=True): patch tokens [B, N, C] of the last four blocks"""
         cfg = self.cfg
         t, ph, pw = self._tokens(x)
-        B, S, _ = t.shape
-        outs = []
-        for i, b in enumerate(self.blocks):
-            t = self._block(b, t, B, S)
-            if i >= cfg.depth - 4:
-                outs.append(t)
-        outs = [ops.layernorm(o, *self.norm, eps=cfg.ln_eps)[:, 1:].contiguous() for o in outs]
+        outs = [ops.layernorm(o, *self.norm, eps=cfg.ln_eps)[:, 1:].contiguous() for o in self._run_blocks(t, 4)]
         return outs, ph, pw
 
     # ------------------------------------------------------------------------------------------------------------
     # DPT head (NHWC rows)
     # ------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _pixel_shuffle(y, B, H, W, k, cout):
+        """GEMM output [B, H*W, (dy, dx, co)] of a ConvTranspose2d(kernel = stride = k) -> NHWC rows [B, (H k)(W k), co]"""
+        return y.view(B, H, W, k, k, cout).permute(0, 1, 3, 2, 4, 5).reshape(B, H * k * W * k, cout).contiguous()
+
     def _up(self, x, B, H, W, dc):
         w, b, cin, cout, k = dc
         y = ops.linear(x, w, b, K=cin)                                               # [B, H*W, k*k*cout]

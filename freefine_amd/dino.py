@@ -1,0 +1,233 @@
+"""The DINOv2 ViT on the HIP kernels: the one encoder of the project (`HipDinoEncoder`), used by the depth network (freefine_amd/depth.py: HipDepthAnything,
+the last four blocks' patch tokens) and by the feature extractor of the FID-DINO / Kernel Distance metrics (`HipDinoV2` below: the normalised class token;
+/root/reference/evaluation/metrics/FID/fid_dino.py:35, fid_kd.py:34 torch.hub dinov2_vitb14, fid_score.py:93-143 get_activations;
+torchhub/facebookresearch_dinov2_main/vision_transformer.py:178-257, 319-324).
+
+Activations are token rows, every Linear and the patch embedding is an `ffn_igemm` call, LayerNorm and attention are the UNet's kernels (`ffn_layernorm`,
+`ffn_attn` with head dim 64 and the ragged S = 1 + (H/14)(W/14)).  Folded at pack time: LayerScale into attn.proj / mlp.fc2 (rows scaled by gamma), the patch
+embedding into a [C, 3*14*14] GEMM weight over im2col rows of the image.  The rows come either from a float image (torch view plumbing, `_im2col`) or, for the
+metrics, straight from decoded uint8 images on the device: `features_u8` = ffn_resize_pil_bilinear_u8 (PIL's antialiased bilinear Resize, bit for bit) ->
+ffn_vit_patch_rows (ToTensor + Normalize as a lookup, im2col) -> the same GEMM.  torchvision is absent here: the transform's semantics are torchvision's
+documented ones (see ops.py), the resize is pinned to PIL itself.
+
+dtype float32 = parity mode (exact-fp32 MFMA), bfloat16 = fast mode.  No split-bf16 mode, no graph capture, no class-token-only last block."""
+import math
+from types import SimpleNamespace
+
+import torch
+import torch.nn.functional as F
+
+from . import ops
+
+_ENC = dict(vits=(384, 12, 6), vitb=(768, 12, 12), vitl=(1024, 24, 16), tiny=(128, 4, 2), mini=(192, 5, 3))
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # fid_score.py:122-123
+
+
+def dinov2_config(name="vitb"):
+    """dinov2_vitb14 (hubconf.py: img_size 518, patch 14, LayerScale, mlp ffn, interpolate_offset 0.1) -- the metrics' model -- and the small test sizes
+    "tiny" / "mini"; the same numbers as depth.depth_config"""
+    enc = {k: _ENC[k] for k in ("vitb", "tiny", "mini")}[name]
+    return SimpleNamespace(name=name, embed_dim=enc[0], depth=enc[1], num_heads=enc[2], patch=14, img_size=518, mlp_ratio=4, interpolate_offset=0.1, ln_eps=1e-6)
+
+
+def dinov2_param_shapes(cfg, prefix=""):
+    """name -> shape of DinoVisionTransformer.state_dict() (hub layout; `prefix` = "pretrained." inside DPT_DINOv2)"""
+    C, hid = cfg.embed_dim, cfg.embed_dim * cfg.mlp_ratio
+    n = (cfg.img_size // cfg.patch) ** 2
+    p = prefix
+    sh = {p + "cls_token": (1, 1, C), p + "pos_embed": (1, n + 1, C), p + "mask_token": (1, C),
+          p + "patch_embed.proj.weight": (C, 3, cfg.patch, cfg.patch), p + "patch_embed.proj.bias": (C,),
+          p + "norm.weight": (C,), p + "norm.bias": (C,)}
+    for i in range(cfg.depth):
+        q = f"{p}blocks.{i}."
+        sh.update({q + "norm1.weight": (C,), q + "norm1.bias": (C,), q + "attn.qkv.weight": (3 * C, C), q + "attn.qkv.bias": (3 * C,),
+                   q + "attn.proj.weight": (C, C), q + "attn.proj.bias": (C,), q + "ls1.gamma": (C,),
+                   q + "norm2.weight": (C,), q + "norm2.bias": (C,), q + "mlp.fc1.weight": (hid, C), q + "mlp.fc1.bias": (hid,),
+                   q + "mlp.fc2.weight": (C, hid), q + "mlp.fc2.bias": (C,), q + "ls2.gamma": (C,)})
+    return sh
+
+
+def synthetic_state(cfg, seed=0):
+    """seeded random weights of a plausible scale in hub layout, for benchmarks without a checkpoint (`tools/bench_dino.py`; there is no network)"""
+    g = torch.Generator().manual_seed(seed)
+    st = {}
+    for k, shp in dinov2_param_shapes(cfg).items():
+        if k.endswith("norm.weight") or k.endswith("norm1.weight") or k.endswith("norm2.weight"):
+            t = 1.0 + 0.1 * torch.randn(shp, generator=g)
+        elif k.endswith(".gamma"):
+            t = 0.5 + 0.25 * torch.rand(shp, generator=g)
+        elif k.endswith(".bias"):
+            t = 0.05 * torch.randn(shp, generator=g)
+        elif k.endswith("pos_embed") or k.endswith("cls_token") or k.endswith("mask_token"):
+            t = 0.2 * torch.randn(shp, generator=g)
+        else:
+            t = torch.randn(shp, generator=g) / math.sqrt(math.prod(shp[1:]))
+        st[k] = t.float()
+    return st
+
+
+class _O:
+    pass
+
+
+class HipDinoEncoder:
+    """The DINOv2 ViT encoder: weights packed from `<prefix>*` of a state dict, tokens, blocks.  Subclasses add what they read off the tokens."""
+
+    def _init_encoder(self, cfg, dtype, device):
+        assert dtype in (torch.float32, torch.bfloat16)
+        self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
+        C = cfg.embed_dim
+        assert C % cfg.num_heads == 0 and C % 8 == 0, "channel counts must be whole 16-byte chunks"
+        self._pos = {}
+
+    # ------------------------------------------------------------------------------------------------------------
+    # weights
+    # ------------------------------------------------------------------------------------------------------------
+    def _lin(self, w, b=None, scale=None, n_pad=None):
+        w = w.reshape(w.shape[0], -1)
+        if scale is not None:                                 # LayerScale folded: gamma * (W x + b)
+            w = w * scale[:, None]
+            b = None if b is None else b * scale
+        if n_pad and n_pad > w.shape[0]:
+            w = torch.cat([w, torch.zeros(n_pad - w.shape[0], w.shape[1], device=w.device)], 0)
+            b = None if b is None else torch.cat([b, torch.zeros(n_pad - b.shape[0], device=b.device)], 0)
+        return ops.pack_linear(w.contiguous(), self.dtype), (None if b is None else b.float().contiguous()), w.shape[1]
+
+    def _pack_encoder(self, st, p):
+        """st: fp32 tensors on the device; p: the prefix of the ViT's parameters (`pretrained.` inside DPT_DINOv2, empty in hub layout)"""
+        cfg = self.cfg
+        C = cfg.embed_dim
+        e = 8
+        K = 3 * cfg.patch * cfg.patch
+        self.kpe = (K + e - 1) // e * e                        # patch-embedding contraction length, padded to whole chunks
+        wpe = torch.zeros(C, self.kpe, device=self.device)
+        wpe[:, :K] = st[p + "patch_embed.proj.weight"].reshape(C, K)
+        self.pe = (ops.pack_linear(wpe, self.dtype), st[p + "patch_embed.proj.bias"].contiguous())
+        self.pos_embed, self.cls_token = st[p + "pos_embed"], st[p + "cls_token"]
+        self.blocks = []
+        for i in range(cfg.depth):
+            b, q = _O(), f"{p}blocks.{i}."
+            b.n1 = (st[q + "norm1.weight"].contiguous(), st[q + "norm1.bias"].contiguous())
+            b.n2 = (st[q + "norm2.weight"].contiguous(), st[q + "norm2.bias"].contiguous())
+            wqkv, bqkv = st[q + "attn.qkv.weight"], st[q + "attn.qkv.bias"]
+            b.qk = self._lin(wqkv[:2 * C], bqkv[:2 * C])        # q | k in one GEMM, V^T from its own (transposed-output) GEMM
+            b.v = self._lin(wqkv[2 * C:], bqkv[2 * C:])
+            b.proj = self._lin(st[q + "attn.proj.weight"], st[q + "attn.proj.bias"], scale=st[q + "ls1.gamma"])
+            b.fc1 = self._lin(st[q + "mlp.fc1.weight"], st[q + "mlp.fc1.bias"])
+            b.fc2 = self._lin(st[q + "mlp.fc2.weight"], st[q + "mlp.fc2.bias"], scale=st[q + "ls2.gamma"])
+            self.blocks.append(b)
+        self.norm = (st[p + "norm.weight"].contiguous(), st[p + "norm.bias"].contiguous())
+
+    # ------------------------------------------------------------------------------------------------------------
+    # tokens and blocks
+    # ------------------------------------------------------------------------------------------------------------
+    def _pos_tokens(self, H, W):
+        """(class row = cls_token + pos[0] [1, C], positional embedding of the H/14 x W/14 patches [N, C]) in the activation dtype --
+        vision_transformer.py:178-209 (bicubic, antialias off, offset 0.1; evaluated once per input size)"""
+        key = (H, W)
+        hit = self._pos.get(key)
+        if hit is not None:
+            return hit
+        cfg = self.cfg
+        pe = self.pos_embed.float()
+        N = pe.shape[1] - 1
+        npatch = (H // cfg.patch) * (W // cfg.patch)
+        patch_pos = pe[:, 1:]
+        if not (npatch == N and H == W):
+            dim = pe.shape[-1]
+            w0, h0 = H // cfg.patch + cfg.interpolate_offset, W // cfg.patch + cfg.interpolate_offset
+            sq = math.sqrt(N)
+            patch_pos = F.interpolate(patch_pos.reshape(1, int(sq), int(sq), dim).permute(0, 3, 1, 2), scale_factor=(float(w0) / sq, float(h0) / sq),
+                                      mode="bicubic", antialias=False)
+            assert int(w0) == patch_pos.shape[-2] and int(h0) == patch_pos.shape[-1]
+            patch_pos = patch_pos.permute(0, 2, 3, 1).reshape(1, -1, dim)
+        cls_row = (self.cls_token.float()[0] + pe[:, 0]).to(self.dtype).contiguous()
+        hit = self._pos[key] = (cls_row, patch_pos[0].to(self.dtype).contiguous())
+        return hit
+
+    @staticmethod
+    def _im2col(x, ps):
+        """[B, 3, H, W] -> [B * (H/ps) * (W/ps), 3 * ps * ps]: one row per patch (row-major over the patch grid), columns ordered (channel, ky, kx)
+        like patch_embed.proj.weight.reshape(C, -1) (patch_embed.py:75: Conv2d(kernel = stride = patch))"""
+        B, Cc, H, W = x.shape
+        ph, pw = H // ps, W // ps
+        return x.reshape(B, Cc, ph, ps, pw, ps).permute(0, 2, 4, 1, 3, 5).reshape(B * ph * pw, Cc * ps * ps)
+
+    def _patch_rows(self, x):
+        """float image [B, 3, H, W] -> the patch-embedding GEMM's operand rows [B * ph * pw, kpe] in the activation dtype (columns >= 3 * 14 * 14 zero)"""
+        B, _, H, W = x.shape
+        ps = self.cfg.patch
+        cols = self._im2col(x.to(self.device, torch.float32), ps)
+        a = torch.zeros(B * (H // ps) * (W // ps), self.kpe, dtype=self.dtype, device=self.device)
+        a[:, :cols.shape[1]] = cols.to(self.dtype)
+        return a
+
+    def _embed(self, a, B, H, W):
+        """patch embedding of given operand rows (a GEMM, positional embedding added as the GEMM's residual) + class row -> ([B, 1 + ph * pw, C], ph, pw)"""
+        ps = self.cfg.patch
+        ph, pw = H // ps, W // ps
+        cls_row, pos = self._pos_tokens(H, W)
+        res = pos.unsqueeze(0).expand(B, -1, -1).reshape(B * ph * pw, -1).contiguous()
+        t = ops.linear(a, self.pe[0], self.pe[1], K=self.kpe, residual=res)
+        return torch.cat([cls_row.unsqueeze(0).expand(B, -1, -1), t.view(B, ph * pw, -1)], dim=1).contiguous(), ph, pw
+
+    def _tokens(self, x):
+        """patch rows from a float image, embedded"""
+        B, _, H, W = x.shape
+        return self._embed(self._patch_rows(x), B, H, W)
+
+    def _block(self, b, t, B, S):
+        cfg = self.cfg
+        C, nh = cfg.embed_dim, cfg.num_heads
+        y = ops.layernorm(t, *b.n1, eps=cfg.ln_eps)
+        qk = ops.linear(y, b.qk[0], b.qk[1], K=C)                                   # [B, S, 2C]: q | k
+        vt = ops.linear(y, b.v[0], b.v[1], K=C, rows_per_batch=S, transposed_ld=(S + 7) // 8 * 8)      # V^T [B, C, S']
+        a = ops.attention(qk, qk[..., C:], vt, nh, (C // nh) ** -0.5, None, Sk=S, C=C)
+        t = ops.linear(a, b.proj[0], b.proj[1], K=C, residual=t)                     # x + ls1 * proj(attn)
+        y = ops.layernorm(t, *b.n2, eps=cfg.ln_eps)
+        y = ops.linear(y, b.fc1[0], b.fc1[1], K=C, gelu=True)
+        return ops.linear(y, b.fc2[0], b.fc2[1], K=C * cfg.mlp_ratio, residual=t)    # x + ls2 * fc2(gelu(fc1))
+
+    def _run_blocks(self, t, keep_last=1):
+        """all blocks over tokens [B, S, C] -> the outputs of the last `keep_last` blocks (before the final LayerNorm)"""
+        B, S, _ = t.shape
+        outs = []
+        for i, b in enumerate(self.blocks):
+            t = self._block(b, t, B, S)
+            if i >= self.cfg.depth - keep_last:
+                outs.append(t)
+        return outs
+
+
+class HipDinoV2(HipDinoEncoder):
+    """DinoVisionTransformer.forward with the hub's identity head: the final LayerNorm's class token (vision_transformer.py:319-324, 236-257)."""
+
+    def __init__(self, cfg, state, dtype=torch.float32, device="cuda:0"):
+        """state: DinoVisionTransformer.state_dict() in hub layout (no `pretrained.` prefix; mask_token accepted and unused)"""
+        self._init_encoder(cfg, dtype, device)
+        self._pack_encoder({k: v.detach().to(self.device, torch.float32) for k, v in state.items()}, "")
+        self._lut = ops.vit_norm_table(IMAGENET_MEAN, IMAGENET_STD).to(self.device)
+
+    def _cls(self, t):
+        """tokens -> blocks -> final LayerNorm on the class rows only -> fp32 [B, C]"""
+        last = self._run_blocks(t, 1)[0]
+        return ops.layernorm(last[:, 0].contiguous(), *self.norm, eps=self.cfg.ln_eps).float()
+
+    @torch.no_grad()
+    def forward(self, x):
+        """x float [B, 3, H, W] (normalised image, H and W multiples of 14) -> fp32 [B, C]: the reference's model(batch) = head(x_norm_clstoken), head = identity"""
+        assert x.shape[2] % self.cfg.patch == 0 and x.shape[3] % self.cfg.patch == 0, "DINOv2 patch embedding: image sides must be multiples of 14"
+        return self._cls(self._tokens(x)[0])
+
+    __call__ = forward
+
+    @torch.no_grad()
+    def features_u8(self, images, size=224):
+        """images uint8 [B, H, W, 3] of ONE size (numpy or torch, host or device) -> fp32 [B, C]: the transform of fid_score.py:124 -- Resize((size, size)) of the
+        PIL image, ToTensor, Normalize(imagenet) -- and the network, all on the device: resize -> patch rows -> encoder."""
+        img = torch.as_tensor(images)
+        assert img.dtype == torch.uint8 and img.ndim == 4 and img.shape[-1] == 3 and size % self.cfg.patch == 0
+        img = img.to(self.device).contiguous()
+        small = ops.resize_pil_bilinear_u8(img, size, size)
+        a = ops.vit_patch_rows(small, self._lut, self.cfg.patch, self.kpe, self.dtype)
+        return self._cls(self._embed(a, img.shape[0], size, size)[0])

@@ -1,9 +1,15 @@
 """The GeoBench metric suite (/root/reference/evaluation/metrics/) as far as it can be built offline.
 
 Model-free arithmetic: warp error, the Frechet distance between two Gaussians of features, and the polynomial-kernel MMD^2 (the "kernel distance" of
-fid_kd.py).  The feature extractors the reference feeds the last two with (Inception-v3, DINOv2, CLIP, HPSv2, ImageReward) need model weights that do not
-exist offline and are NOT built; these functions take features / images and are pinned to the reference's own functions by tests/golden/g11_metrics.npz
-(tools/gen_golden.py run_g11).  Host-side numpy: a metric pass is a few reductions over at most thousands of feature rows.
+fid_kd.py); pinned to the reference's own functions by tests/golden/g11_metrics.npz (tools/gen_golden.py run_g11).  Host-side numpy: a metric pass is a few
+reductions over at most thousands of feature rows.
+
+FID-DINO (FID/fid_dino.py) and Kernel Distance (FID/fid_kd.py) feed those functions with DINOv2 ViT-B/14 class tokens.  The reference vendors the DINOv2 source
+(torchhub/facebookresearch_dinov2_main), so the extractor is built and pinned: freefine_amd/dino.py HipDinoV2 runs the encoder on the project's kernels (pinned to
+the vendored DinoVisionTransformer by tests/golden/g14_dinov2_cls.npz, tools/gen_golden.py run_g14) and prepares the images on the device, bit-exact against
+PIL (ops.resize_pil_bilinear_u8, ops.vit_patch_rows).  get_activations / calculate_fid_dino / calculate_fid_kd below are the drivers; the WEIGHTS still come
+from the caller (a state dict in hub layout: there is no hub download).  The other extractors of the suite (Inception-v3, DINO v1 ViT-B/16, CLIP image tower,
+HPSv2, ImageReward) have no model code in the reference tree, nothing to pin them to, and are NOT built.
 
 Mean Distance (MD/mean_distance.py), the one metric of the suite that measures the GEOMETRY of an edit, needs no foreign network: its feature extractor is
 DIFT, i.e. Stable Diffusion itself, and runs on the project's kernels (freefine_amd/dift.py: HipVAE + HipUNet.features; the correspondence search is
@@ -88,6 +94,69 @@ def kernel_distance(feat_real, feat_gen, n_subsets=100, subset_size=1000, rng=No
         r = feat_gen[rng.choice(len(feat_gen), m, replace=False)]
         out[i] = polynomial_mmd2(g, r)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# FID-DINO (FID/fid_dino.py) and Kernel Distance (FID/fid_kd.py): DINOv2 class tokens into the two functions above
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+def get_activations(files, model, batch_size=64, reader=None):
+    """fid_score.py:get_activations (:93-143) -> float64 [len(files), C] in file order.  model: a freefine_amd.dino.HipDinoV2 (anything with
+    features_u8(uint8 [B, H, W, 3]) -> [B, C]); the transform of the reference's dataset (Resize((224, 224)), ToTensor, Normalize) runs inside it, on the
+    device.  Images are grouped by size so that one launch sees one size, batched by `batch_size` within a group (a model's row does not depend on its
+    batch), and the rows scattered back to file order.  `reader` maps a path to a uint8 HWC array (default: PIL, converted to RGB)."""
+    if reader is None:
+        from PIL import Image
+        reader = lambda p: np.array(Image.open(p).convert("RGB"))
+    images = [np.ascontiguousarray(reader(p), dtype=np.uint8) for p in files]
+    groups = {}
+    for i, im in enumerate(images):
+        assert im.ndim == 3 and im.shape[2] == 3, f"{files[i]}: expected an RGB image, got shape {im.shape}"
+        groups.setdefault(im.shape[:2], []).append(i)
+    out = None
+    for idx in groups.values():
+        for s in range(0, len(idx), batch_size):
+            part = idx[s:s + batch_size]
+            f = model.features_u8(np.stack([images[i] for i in part]))
+            f = f.detach().cpu().numpy() if hasattr(f, "detach") else np.asarray(f)
+            if out is None:
+                out = np.empty((len(files), f.shape[1]), dtype=np.float64)
+            out[part] = f
+    return np.empty((0, 0)) if out is None else out
+
+
+def parse_data(data, image_label, real_root_path):
+    """fid_dino.py / fid_kd.py:parse_data -> (real files, generated files).  Quirk kept: the real set is the DIRECTORY LISTING of real_root_path (os.listdir
+    order), not the samples' ori_img_path entries, which the reference collects and then overwrites."""
+    import os
+    gen = [sample[image_label] for image in data.values() for instance in image["instances"].values() for sample in instance.values()]
+    return [os.path.join(real_root_path, n) for n in os.listdir(real_root_path)], gen
+
+
+def _dino_model(model):
+    """a HipDinoV2 as it is; a state dict (DinoVisionTransformer.state_dict() of dinov2_vitb14, hub layout) becomes one in fp32, like the reference's model"""
+    if isinstance(model, dict):
+        import torch
+        from .dino import HipDinoV2, dinov2_config
+        return HipDinoV2(dinov2_config("vitb"), model, dtype=torch.float32)
+    return model
+
+
+def calculate_fid_dino(data, image_label, real_root_path, model, batch_size=64, reader=None):
+    """fid_dino.py:calculate_fid_dino: the Frechet distance between the DINOv2 class tokens of the real images (the listing of real_root_path) and of the generated
+    ones (data[...][image_label]).  model: a HipDinoV2 or a dinov2_vitb14 state dict (the reference downloads it from the hub; here the caller brings it)."""
+    model = _dino_model(model)
+    real, gen = parse_data(data, image_label, real_root_path)
+    m1, s1 = feature_statistics(get_activations(real, model, batch_size, reader))
+    m2, s2 = feature_statistics(get_activations(gen, model, batch_size, reader))
+    return frechet_distance(m1, s1, m2, s2)
+
+
+def calculate_fid_kd(data, image_label, real_root_path, model, batch_size=64, reader=None):
+    """fid_kd.py:calculate_fid_kd: the mean of kernel_distance(real, generated) over DINOv2 class tokens (numpy's global generator picks the subsets, as in
+    the reference)"""
+    model = _dino_model(model)
+    real, gen = parse_data(data, image_label, real_root_path)
+    return kernel_distance(get_activations(real, model, batch_size, reader), get_activations(gen, model, batch_size, reader)).mean()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------

@@ -998,6 +998,109 @@ def dift_match(rows_src, rows_tgt, hw, HW, kps):
     return rc, cos
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# device image preparation of the DINOv2 feature metrics (csrc/imgprep.h).  torchvision is absent here: the semantics restated below -- Resize((h, w)) of a
+# PIL image = Image.resize((w, h), BILINEAR) (antialiased: the support grows with the down-scaling factor), ToTensor = float32(byte) / 255 in CHW,
+# Normalize(mean, std) = (x - float32(mean)) / float32(std) in place -- are torchvision's DOCUMENTED ones, not recorded from it.  The resize is pinned to PIL
+# itself (tests/test_dino_cpu.py, tests/test_dino_gpu.py).
+# ---------------------------------------------------------------------------------------------------------------
+_PIL_COEFFS = {}
+_PIL_COEFFS_DEV = {}
+
+
+def pil_bilinear_coeffs(in_size, out_size):
+    """The tables of one axis of PIL's Image.resize(BILINEAR) on 8-bit images (libImaging/Resample.c: precompute_coeffs with the bilinear filter of support 1,
+    normalize_coeffs_8bpc with PRECISION_BITS = 22), evaluated in float64 like PIL's C doubles.  Pure host function, cached per (in, out).
+    -> (bounds int32 [out, 2] = (first source index, number of taps), coef int32 [out, ksize], ksize = 2 ceil(max(in / out, 1)) + 1; taps past the count are 0).
+    An output value is clamp((2^21 + sum_x pixel[xmin + x] * coef[x]) >> 22, 0, 255); an axis whose size does not change gets the identity (one tap of 2^22).
+    The tap weight is max(0, 1 - |(x + xmin - center + 0.5) * (1 / fs)|): the product with the reciprocal, as PIL's C spells it."""
+    import numpy as np
+    key = (int(in_size), int(out_size))
+    hit = _PIL_COEFFS.get(key)
+    if hit is not None:
+        return hit
+    n_in, n_out = key
+    assert n_in >= 1 and n_out >= 1
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    ksize = 2 * int(math.ceil(support)) + 1
+    ss = 1.0 / fs
+    bounds = np.zeros((n_out, 2), dtype=np.int32)
+    coef = np.zeros((n_out, ksize), dtype=np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        xmin = max(0, int(center - support + 0.5))
+        n = min(n_in, int(center + support + 0.5)) - xmin
+        w = np.maximum(0.0, 1.0 - np.abs((np.arange(n, dtype=np.float64) + xmin - center + 0.5) * ss))
+        tot = 0.0
+        for v in w:                                           # PIL sums the weights left to right in a double
+            tot += float(v)
+        if tot != 0.0:
+            w = w / tot
+        bounds[xx] = (xmin, n)
+        coef[xx, :n] = (w * float(1 << 22) + 0.5).astype(np.int64)      # weights are >= 0: int(0.5 + w 2^22) truncates like the C cast
+    bounds.setflags(write=False)
+    coef.setflags(write=False)
+    hit = _PIL_COEFFS[key] = (bounds, coef)
+    return hit
+
+
+def _pil_coeffs_dev(in_size, out_size, device):
+    key = (int(in_size), int(out_size), torch.device(device))
+    hit = _PIL_COEFFS_DEV.get(key)
+    if hit is None:
+        if len(_PIL_COEFFS_DEV) > 64:
+            _PIL_COEFFS_DEV.clear()
+        b, k = pil_bilinear_coeffs(in_size, out_size)
+        hit = _PIL_COEFFS_DEV[key] = (torch.from_numpy(b.copy()).to(device), torch.from_numpy(k.copy()).to(device), k.shape[1])
+    return hit
+
+
+def resize_pil_bilinear_u8(img, oh, ow, out=None, scratch=None):
+    """uint8 [B, H, W, 3] (device, contiguous) -> uint8 [B, oh, ow, 3]: PIL's Image.resize((ow, oh), BILINEAR) bit for bit (ffn_resize_pil_bilinear_u8).
+    H, W, oh, ow <= _lib.IMGPREP_MAX_SIDE."""
+    lib = L.load()
+    assert img.dtype == torch.uint8 and img.ndim == 4 and img.shape[-1] == 3 and img.is_contiguous()
+    B, H, W, _ = img.shape
+    hb, hk, hks = _pil_coeffs_dev(W, ow, img.device)
+    vb, vk, vks = _pil_coeffs_dev(H, oh, img.device)
+    if out is None:
+        out = torch.empty(B, oh, ow, 3, dtype=torch.uint8, device=img.device)
+    if scratch is None:
+        scratch = torch.empty(B, H, ow, 3, dtype=torch.uint8, device=img.device)
+    assert out.is_contiguous() and out.numel() == B * oh * ow * 3 and scratch.numel() >= B * H * ow * 3
+    L.check(_timed("resize_pil_bilinear_u8", 0.0, 3.0 * B * (H * W + 2 * H * ow + oh * ow),
+                   lambda: lib.ffn_resize_pil_bilinear_u8(_stream(), img.data_ptr(), out.data_ptr(), scratch.data_ptr(), B, H, W, oh, ow, hb.data_ptr(), hk.data_ptr(), hks,
+                                                          vb.data_ptr(), vk.data_ptr(), vks)), "ffn_resize_pil_bilinear_u8")
+    return out
+
+
+def vit_norm_table(mean, std):
+    """[3, 256] fp32: ToTensor + Normalize(mean, std) of every byte value per channel, evaluated by the very torch expressions the transform runs on an image
+    (float32(byte) / 255, then in place - float32(mean[c]), / float32(std[c])) -- the kernel only looks values up."""
+    import numpy as np
+    mean32 = torch.as_tensor(np.asarray(mean, dtype=np.float64), dtype=torch.float32)
+    std32 = torch.as_tensor(np.asarray(std, dtype=np.float64), dtype=torch.float32)
+    return torch.stack([torch.arange(256, dtype=torch.uint8).float().div(255).sub_(mean32[c]).div_(std32[c]) for c in range(3)])
+
+
+def vit_patch_rows(img, lut, patch, ldo, dtype, out=None):
+    """uint8 [B, H, W, 3] (device) + lut fp32 [3, 256] (device) -> [B (H / patch)(W / patch), ldo] of `dtype`: the normalised image as the operand rows of the
+    patch-embedding GEMM, columns (channel, ky, kx), zero from 3 patch^2 on (ffn_vit_patch_rows)."""
+    lib = L.load()
+    assert img.dtype == torch.uint8 and img.ndim == 4 and img.shape[-1] == 3 and img.is_contiguous()
+    assert lut.dtype == torch.float32 and lut.shape == (3, 256) and lut.is_contiguous() and lut.device == img.device
+    B, H, W, _ = img.shape
+    M = B * (H // patch) * (W // patch)
+    if out is None:
+        out = torch.empty(M, ldo, dtype=dtype, device=img.device)
+    assert out.dtype == dtype and out.is_contiguous() and out.numel() == M * ldo
+    L.check(_timed(f"patch_rows_kernel<{_tname(out)}>", 0.0, 3.0 * B * H * W + float(M) * ldo * out.element_size(),
+                   lambda: lib.ffn_vit_patch_rows(_stream(), _dt(out), img.data_ptr(), lut.data_ptr(), out.data_ptr(), B, H, W, patch, ldo)), "ffn_vit_patch_rows")
+    return out
+
+
 def image_to_nhwc(img_u8, CP, dtype, out=None):
     """uint8 [B,H,W,3] -> dtype [B,HW,CP] in [-1,1]."""
     lib = L.load()

@@ -357,6 +357,26 @@ typedef struct ffn_dift_desc {
 int ffn_dift_match(void* stream, const ffn_dift_desc* d);
 long ffn_dift_workspace_bytes(int C, int h, int w, int K);
 
+/* ---- device image preparation of the DINOv2 feature metrics (FID-DINO, Kernel Distance) ---------------------------------------------------
+ * Reference: evaluation/metrics/FID/fid_score.py:122-124 -- TF.Resize((224, 224)) of a PIL image (antialiased bilinear), TF.ToTensor, TF.Normalize, on the
+ * host; here from the decoded uint8 image to the operand rows of the patch-embedding GEMM on the device (csrc/imgprep.h).  Images are [B][H][W][3] uint8,
+ * contiguous, any byte alignment.  No side of a source or destination image may exceed FFN_IMGPREP_MAX_SIDE (the horizontal pass stages one source row
+ * in LDS); larger images are refused with FFN_EINVAL.
+ *
+ * ffn_resize_pil_bilinear_u8: PIL's Image.resize((ow, oh), BILINEAR) in PIL's own integer arithmetic (libImaging/Resample.c, 8 bits per channel): a
+ * horizontal pass src -> scratch [B][H][ow][3], a vertical pass scratch -> dst [B][oh][ow][3], each clamp((2^21 + sum pixel * k) >> 22, 0, 255) in int32.
+ * The tables are device int32 arrays the caller builds on the host in float64 (freefine_amd.ops.pil_bilinear_coeffs): bounds [out][2] = (first source index,
+ * number of taps), coef [out][ksize] with ksize = 2 ceil(max(in / out, 1)) + 1 (checked).  Bounds are clamped into the image by the kernels.  B <= 65535.
+ *
+ * ffn_vit_patch_rows: out [B (H / patch)(W / patch)][ldo] in fp32 (FFN_F32) or bf16 (FFN_BF16, round to nearest even): row = patch (row-major over the patch
+ * grid), column (c, ky, kx) = lut[c][src[b][py patch + ky][px patch + kx][c]], columns 3 patch^2 .. ldo - 1 zero -- the im2col rows of
+ * Conv2d(3, C, kernel = stride = patch) over the normalised image.  lut: device fp32 [3][256], ToTensor + Normalize per channel and byte value, evaluated by the
+ * caller.  H, W multiples of patch; ldo >= 3 patch^2. */
+#define FFN_IMGPREP_MAX_SIDE 4096
+int ffn_resize_pil_bilinear_u8(void* stream, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int oh, int ow, const int* hbounds,
+                               const int* hcoef, int hksize, const int* vbounds, const int* vcoef, int vksize);
+int ffn_vit_patch_rows(void* stream, int dtype, const uint8_t* src, const float* lut, void* out, int B, int H, int W, int patch, int ldo);
+
 #ifdef __cplusplus
 }
 #endif

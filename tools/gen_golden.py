@@ -737,8 +737,41 @@ def run_g13():
     print("[G13] " + ", ".join(f"{k} {v.shape}" for k, v in out.items() if k.endswith("_coords")))
 
 
+# --------------------------------------------------------------------------------------------------------------
+# G14: the feature extractor of the FID-DINO / Kernel Distance metrics -- the reference's own DinoVisionTransformer.forward (the hub's dinov2_vitb14 call:
+# identity head over the normalised class token), class tokens only
+# --------------------------------------------------------------------------------------------------------------
+def run_g14():
+    """oracle/dpt.py::vit_features(cfg, st, x, 1)[0][1] against model(x) of the in-tree DINOv2 (torchhub/facebookresearch_dinov2_main/vision_transformer.py:
+    319-324) with the hub's keyword arguments, seeded weights: the two small encoders at 224 x 224 (the metrics' size: positional embedding interpolated
+    37^2 -> 16^2) and at their own grid (518 x 518, no interpolation), ViT-B/14 at 224 x 224 with batch 2.  Only the [B, C] outputs are stored; tests regenerate
+    the weights and inputs from the seeds (tests/test_dino_cpu.py::g14_inputs)."""
+    hub = os.path.join(RH.REF, "torchhub", "facebookresearch_dinov2_main")
+    if hub not in sys.path:
+        sys.path.insert(0, hub)
+    import vision_transformer as vits
+    from oracle import dpt as OD
+    out = {}
+    for name, H, W, B in (("tiny", 224, 224, 2), ("tiny", 518, 518, 1), ("mini", 224, 224, 2), ("mini", 518, 518, 1), ("vitb", 224, 224, 2)):
+        cfg = OD.dpt_config(name)
+        st = OD.dpt_synthetic_state(cfg, seed=14 + len(name))
+        vit = vits.DinoVisionTransformer(img_size=cfg.img_size, patch_size=14, embed_dim=cfg.embed_dim, depth=cfg.depth, num_heads=cfg.num_heads,
+                                         mlp_ratio=cfg.mlp_ratio, init_values=1.0, ffn_layer="mlp", block_chunks=0, num_register_tokens=0,
+                                         interpolate_antialias=False, interpolate_offset=0.1).eval()
+        missing, unexpected = vit.load_state_dict({k[len("pretrained."):]: v for k, v in st.items() if k.startswith("pretrained.")}, strict=True)
+        assert not missing and not unexpected
+        x = rng_tensor(140 + H + len(name), (B, 3, H, W))
+        with torch.no_grad():
+            y = vit(x)                                          # forward: head(forward_features(x)["x_norm_clstoken"]), head = Identity
+            o = OD.vit_features(cfg, st, x, 1)[0][1]
+        key = f"{name}_{H}x{W}"
+        out[key] = y.numpy()
+        print(f"[G14] {key}: oracle vs reference  class token max abs diff {(y - o).abs().max().item():.3e} (|y|max {y.abs().max():.3f}, shape {tuple(y.shape)})")
+    np.savez_compressed(os.path.join(GOLD, "g14_dinov2_cls.npz"), **out)
+
+
 if __name__ == "__main__":
-    only = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g6b", "g7", "g8", "g9", "g11", "g13"]
+    only = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g6b", "g7", "g8", "g9", "g11", "g13", "g14"]
     torch.set_grad_enabled(False)
     A, Mo = RH.import_reference()
     if "g1" in only:
@@ -763,3 +796,5 @@ if __name__ == "__main__":
         run_g11()
     if "g13" in only:
         run_g13()
+    if "g14" in only:
+        run_g14()
