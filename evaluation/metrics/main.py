@@ -1,0 +1,138 @@
+"""The GeoBench metric driver on the MI355X engine -- the same command line as the reference's evaluation/metrics/main.py:
+
+    python evaluation/metrics/main.py --path <generated_results.json> [--task 100111111] [--level 0..3] [--no_rotate] [--3d]
+           [--use_relative_path --base_dir <GeoBenchMeta>] [--fid_path <real images>] [--gen_img_key gen_img_path]
+           [--clip_weights <file>] [--dino_weights <file>] [--dinov2_weights <file>] [--model <SD folder | synthetic:sd21-base>]
+
+--task is nine digits (1 = compute): FID, IRS, HPS, BGC, SUBC, WRAP_E, MD, FID_DINO, FID_KD.  The reference downloads its extractors (clip.load, torch.hub); there
+is no download here, the weights are local files: --clip_weights (CLIP ViT-B/32: a transformers CLIPVisionModelWithProjection state dict or the OpenAI
+checkpoint's visual.* names), --dino_weights (dino_vitb16), --dinov2_weights (dinov2_vitb14), each a .safetensors file or a torch.save'd state dict;
+--model is the Stable-Diffusion checkpoint whose features Mean Distance matches.  FID (Inception-v3), IRS (ImageReward) and HPS (HPSv2) have no model code in the
+reference tree to pin an implementation to: they are reported as `not built`, and the other metrics still run.  A metric whose weights were not given is
+reported as such, likewise."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+
+NAMES = ("FID", "IRS", "HPS", "BGC", "SUBC", "WRAP_E", "MD", "FID_DINO", "FID_KD")
+NOT_BUILT = {"FID": "not built (Inception-v3: no model code to pin it to)", "IRS": "not built (ImageReward: no model code to pin it to)",
+             "HPS": "not built (HPSv2: no model code to pin it to)"}
+LEVEL_WORDS = {1: ("lightly", "slightly", "gently", "mildly"), 2: ("moderately", "markedly", "appreciably"), 3: ("heavily", "intensely", "significantly", "strongly")}
+PATH_KEYS = ("ori_img_path", "coarse_input_path", "ori_mask_path", "tgt_mask_path")
+
+
+def samples(data):
+    """(instance dict, case id, sample) of every case of a result tree data[image]["instances"][instance][case]"""
+    for image in data.values():
+        for instance in image["instances"].values():
+            for case_id in list(instance):
+                yield instance, case_id, instance[case_id]
+
+
+def edit_level(prompt):
+    low = prompt.lower()
+    for level, words in LEVEL_WORDS.items():
+        if any(w in low for w in words):
+            return level
+    raise ValueError(f"No Level found for {prompt}")
+
+
+def filter_data(data, args):
+    """the reference's filters, in its order: --level keeps the cases whose edit_prompt names that level, --no_rotate drops the cases with a rotation
+    (edit_param[5] != 0), --3d takes mask and coarse input from target_mask_0 / coarse_input_path_0, --use_relative_path joins the paths to --base_dir"""
+    for instance, case_id, sample in samples(data):
+        if args.level and edit_level(sample.get("edit_prompt", "")) != args.level:
+            del instance[case_id]
+        elif args.no_rotate and sample.get("edit_param", "")[5] != 0:
+            del instance[case_id]
+    for _, _, sample in samples(data):
+        if args.three_d:
+            sample["tgt_mask_path"], sample["coarse_input_path"] = sample["target_mask_0"], sample["coarse_input_path_0"]
+        if args.use_relative_path:
+            for key in PATH_KEYS + (args.gen_img_key,):
+                if key in sample:
+                    sample[key] = os.path.join(args.base_dir, sample[key])
+    return data
+
+
+def load_state(path):
+    """a .safetensors file or a torch.save'd state dict (loaded as data: weights_only)"""
+    if path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        return load_file(path)
+    import torch
+    st = torch.load(path, map_location="cpu", weights_only=True)
+    return st.get("state_dict", st) if isinstance(st, dict) else st
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Evaluation")
+    ap.add_argument("--path", required=True, help="JSON file of generated results")
+    ap.add_argument("--level", default=0, type=int, help="edit level (0 = all, 1 = easy, 2 = medium, 3 = hard)")
+    ap.add_argument("--task", default="100111111", type=str, help="nine digits, 1 = compute: " + ", ".join(NAMES))
+    ap.add_argument("--gen_img_key", default="gen_img_path", help="JSON key of the generated image paths")
+    ap.add_argument("--no_rotate", action="store_true", help="leave out the cases with a rotation")
+    ap.add_argument("--3d", dest="three_d", action="store_true", help="use the 3-D evaluation's masks and coarse inputs")
+    ap.add_argument("--fid_path", default=None, help="folder of real images (FID_DINO, FID_KD)")
+    ap.add_argument("--use_relative_path", action="store_true", help="join the JSON's paths to --base_dir")
+    ap.add_argument("--base_dir", default=None, help="base folder of relative paths")
+    ap.add_argument("--clip_weights", default=None, help="CLIP ViT-B/32 weights (BGC)")
+    ap.add_argument("--dino_weights", default=None, help="DINO ViT-B/16 weights (SUBC)")
+    ap.add_argument("--dinov2_weights", default=None, help="DINOv2 ViT-B/14 weights (FID_DINO, FID_KD)")
+    ap.add_argument("--model", default=None, help="Stable-Diffusion folder or synthetic:<name> (MD)")
+    ap.add_argument("--clip_config", default="vitb32", help=argparse.SUPPRESS)        # "tiny": the test sizes
+    ap.add_argument("--dino_config", default="vitb16", help=argparse.SUPPRESS)
+    args = ap.parse_args(argv)
+    if len(args.task) != len(NAMES) or set(args.task) - set("01"):
+        ap.error(f"--task takes {len(NAMES)} digits of 0 / 1")
+    if args.use_relative_path and args.base_dir is None:
+        ap.error("--use_relative_path needs --base_dir")
+    with open(args.path) as f:
+        data = filter_data(json.load(f), args)
+    label = args.gen_img_key
+    want = [n for n, t in zip(NAMES, args.task) if t == "1"]
+
+    def dinov2():
+        return load_state(args.dinov2_weights)
+
+    def run(name):
+        import torch
+        from freefine_amd import metrics as FM
+        if name in NOT_BUILT:
+            return NOT_BUILT[name]
+        if name == "BGC":
+            if not args.clip_weights:
+                return "not run (--clip_weights missing)"
+            from freefine_amd.clipvision import HipCLIPVision
+            return FM.calculate_bgc(data, label, HipCLIPVision(args.clip_config, load_state(args.clip_weights), dtype=torch.float32))
+        if name == "SUBC":
+            if not args.dino_weights:
+                return "not run (--dino_weights missing)"
+            from freefine_amd.dino import HipDino, dino_config
+            return FM.calculate_subc(data, label, HipDino(dino_config(args.dino_config), load_state(args.dino_weights), dtype=torch.float32))
+        if name == "WRAP_E":
+            return FM.calculate_we(data, label)
+        if name == "MD":
+            if not args.model:
+                return "not run (--model missing)"
+            from freefine_amd.pipeline import FreeFinePipeline
+            return FM.calculate_md(data, label, FreeFinePipeline.from_pretrained(args.model, torch_dtype=torch.float32, device=torch.device("cuda:0")))
+        if not args.dinov2_weights or not args.fid_path:
+            return "not run (--dinov2_weights or --fid_path missing)"
+        return (FM.calculate_fid_dino if name == "FID_DINO" else FM.calculate_fid_kd)(data, label, args.fid_path, dinov2())
+
+    result = {}
+    for name in want:
+        print(f"-----{name}-----", flush=True)
+        result[name] = run(name)
+    print("-----Result-----")
+    for k, v in result.items():
+        print(f"{k}: {v}")
+    return result
+
+
+if __name__ == "__main__":
+    main()

@@ -16,6 +16,8 @@ ATT_MAXP, ATT_MAXB = 4, 16
 ATT_HEAD_RULE, ATT_UNIFORM_SEL1, ATT_UNIFORM_SEL0, ATT_CAUSAL = 1, 2, 4, 8
 NORM_SILU, NORM_OUT_PAIR = 1, 2
 IMGPREP_MAX_SIDE = 4096      # FFN_IMGPREP_MAX_SIDE
+IMGPREP_MAX_TAPS = 2 * 3 * IMGPREP_MAX_SIDE + 1      # FFN_IMGPREP_MAX_TAPS
+KEEP_NONE, KEEP_SUM_LT128, KEEP_GT128 = 0, 1, 2
 
 
 class IgemmDesc(C.Structure):
@@ -82,6 +84,15 @@ class DiftDesc(C.Structure):
     ]
 
 
+class ResizePilDesc(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("dst", C.c_void_p), ("scratch", C.c_void_p), ("m1", C.c_void_p), ("m2", C.c_void_p),
+        ("hbounds", C.c_void_p), ("hcoef", C.c_void_p), ("vbounds", C.c_void_p), ("vcoef", C.c_void_p),
+        ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("oh", C.c_int), ("ow", C.c_int), ("hksize", C.c_int), ("vksize", C.c_int),
+        ("y0", C.c_int), ("x0", C.c_int), ("ch", C.c_int), ("cw", C.c_int), ("rule", C.c_int),
+    ]
+
+
 # every symbol include/freefine_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _f, _l = C.c_void_p, C.c_int, C.c_float, C.c_long
 SYMBOLS = {
@@ -135,6 +146,7 @@ SYMBOLS = {
     "ffn_dift_match": (_i, [_vp, C.POINTER(DiftDesc)]),
     "ffn_dift_workspace_bytes": (_l, [_i, _i, _i, _i]),
     "ffn_resize_pil_bilinear_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i]),
+    "ffn_resize_pil_u8": (_i, [_vp, C.POINTER(ResizePilDesc)]),
     "ffn_vit_patch_rows": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "ffn_image_to_nhwc": (_i, [_vp, _i, _vp, _vp, _l, _i]),
     "ffn_nhwc_to_image": (_i, [_vp, _i, _vp, _vp, _i, _i, _i]),

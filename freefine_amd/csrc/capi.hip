@@ -70,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 5; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows
+extern "C" int ffn_version(void) { return 6; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -1178,6 +1178,27 @@ extern "C" int ffn_resize_pil_bilinear_u8(void* stream, const uint8_t* src, uint
             H, oh, pil_ksize(W, ow), pil_ksize(H, oh));
     fimgprep_resize(reinterpret_cast<hipStream_t>(stream), src, dst, scratch, B, H, W, oh, ow, hbounds, hcoef, hksize, vbounds, vcoef, vksize);
     return check_launch("resize_pil_bilinear_u8");
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fimgprep_resize_win(hipStream_t s, const ffn_resize_pil_desc* d);
+
+extern "C" int ffn_resize_pil_u8(void* stream, const ffn_resize_pil_desc* d) {
+    const int lim = FFN_IMGPREP_MAX_SIDE, taps = FFN_IMGPREP_MAX_TAPS;
+    REQUIRE(d, "resize_pil_u8: null descriptor");
+    REQUIRE(d->src && d->dst && d->scratch && d->hbounds && d->hcoef && d->vbounds && d->vcoef, "resize_pil_u8: null pointer");
+    REQUIRE(d->B >= 1 && d->B <= 65535, "resize_pil_u8: B=%d outside 1 .. 65535", d->B);
+    REQUIRE(d->C == 1 || d->C == 3, "resize_pil_u8: C=%d channels (1 or 3)", d->C);
+    REQUIRE(d->H >= 1 && d->W >= 1 && d->H <= lim && d->W <= lim, "resize_pil_u8: source %d x %d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE)", d->H, d->W, lim);
+    REQUIRE(d->oh >= 1 && d->ow >= 1 && d->oh <= lim && d->ow <= lim, "resize_pil_u8: destination %d x %d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE)", d->oh, d->ow, lim);
+    REQUIRE(d->hksize >= 1 && d->vksize >= 1 && d->hksize <= taps && d->vksize <= taps, "resize_pil_u8: table widths %d, %d outside 1 .. %d (FFN_IMGPREP_MAX_TAPS)",
+            d->hksize, d->vksize, taps);
+    REQUIRE(d->y0 >= 0 && d->x0 >= 0 && d->ch >= 1 && d->cw >= 1 && d->ch <= d->oh - d->y0 && d->cw <= d->ow - d->x0,
+            "resize_pil_u8: window (%d, %d, %d, %d) outside the %d x %d destination", d->y0, d->x0, d->ch, d->cw, d->oh, d->ow);
+    REQUIRE(d->rule == FFN_KEEP_NONE || d->rule == FFN_KEEP_SUM_LT128 || d->rule == FFN_KEEP_GT128, "resize_pil_u8: unknown keep rule %d", d->rule);
+    REQUIRE(d->rule == FFN_KEEP_NONE || d->C == 3, "resize_pil_u8: a keep mask needs C=3 (C=%d)", d->C);
+    REQUIRE(d->rule == FFN_KEEP_NONE || d->m1, "resize_pil_u8: keep rule %d without m1 (null pointer)", d->rule);
+    fimgprep_resize_win(reinterpret_cast<hipStream_t>(stream), d);
+    return check_launch("resize_pil_u8");
 }
 
 extern "C" int ffn_vit_patch_rows(void* stream, int dtype, const uint8_t* src, const float* lut, void* out, int B, int H, int W, int patch, int ldo) {

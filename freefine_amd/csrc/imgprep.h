@@ -1,9 +1,11 @@
-// Device image preparation of the DINOv2 feature metrics (FID-DINO, Kernel Distance): from the decoded uint8 image to the operand rows of the patch-embedding GEMM.
+// Device image preparation of the feature metrics (FID-DINO, Kernel Distance, Background / Subject Consistency): from the decoded uint8 image to the operand rows
+// of the patch-embedding GEMM.
 //
 //   resize_h_kernel / resize_v_kernel   PIL's Image.resize(BILINEAR) on 8-bit images restated: two separable passes in int32 with 22-bit fixed-point
 //                                       coefficients (PIL libImaging/Resample.c: ImagingResampleHorizontal_8bpc / ImagingResampleVertical_8bpc,
 //                                       PRECISION_BITS = 32 - 8 - 2).  The coefficient tables are built on the host (ops.pil_bilinear_coeffs); the kernels only
 //                                       multiply, add, shift and clamp, so the result does not depend on the compiler's floating point.
+//   resize_win_h_kernel / _v_kernel     the same passes for any PIL filter's tables, 1 or 3 channels, a destination crop window and a keep mask (below)
 //   patch_rows_kernel                   ToTensor + Normalize as a [3][256] lookup (evaluated on the host by torch) and the im2col of a ViT patch embedding
 //                                       (Conv2d(kernel = stride = patch)): one row per patch, columns (channel, ky, kx), zero padding up to ldo.
 //
@@ -64,6 +66,60 @@ __global__ __launch_bounds__(IMGPREP_THREADS) void resize_v_kernel(const uint8_t
     int acc = 1 << 21;
     for (int y = 0; y < n; ++y) acc += (int)s[(long)y * row_bytes] * k[y];
     dst[((long)blockIdx.z * oh + yy) * row_bytes + o] = imgprep_clip8(acc);
+}
+
+// ---- the general PIL resize (ffn_resize_pil_u8): any filter's tables (signed coefficients, any width up to FFN_IMGPREP_MAX_TAPS), C = 1 or 3 channels, a
+// destination crop window (y0, x0, ch, cw) inside oh x ow, and an optional keep mask applied while the source row is staged in LDS -- the masked image of the
+// consistency metrics (Background / Subject Consistency) never exists in memory.  Same arithmetic as the two bilinear kernels above; the sum is kept in
+// uint32 (two's complement: the same bits as PIL's int) so that a bad table wraps instead of overflowing a signed int.
+
+// keep rule of one pixel: SUM_LT128 = (uint8)(m1 + m2) < 128 (the reference's uint8 wrap: 200 + 100 = 44 keeps, 128 + 128 = 0 keeps), GT128 = m1 > 128
+__device__ __forceinline__ bool imgprep_keep(int rule, const uint8_t* __restrict__ m1, const uint8_t* __restrict__ m2, long i) {
+    if (rule == FFN_KEEP_SUM_LT128) return (uint8_t)((unsigned)m1[i] + (m2 ? (unsigned)m2[i] : 0u)) < 128;
+    if (rule == FFN_KEEP_GT128) return m1[i] > 128;
+    return true;
+}
+
+// Horizontal pass: src [B][H][W][C] -> dst [B][H][cw][C], only the window's columns x0 .. x0 + cw - 1 of the ow the tables describe.  One workgroup per source
+// row (grid = (H, B)); the row is staged in LDS with dropped pixels as 0 in all channels (m1 / m2 [B][H][W], rule FFN_KEEP_*), then one thread per output byte.
+template <int C>
+__global__ __launch_bounds__(IMGPREP_THREADS) void resize_win_h_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const uint8_t* __restrict__ m1,
+                                                                       const uint8_t* __restrict__ m2, int rule, int W, int x0, int cw,
+                                                                       const int* __restrict__ bounds, const int* __restrict__ coef, int ksize) {
+    __shared__ uint8_t row[3 * IMGPREP_MAX_SIDE];
+    const long r = (long)blockIdx.y * gridDim.x + blockIdx.x;              // row index over (b, y)
+    const uint8_t* s = src + r * W * C;
+    for (int i = threadIdx.x; i < W * C; i += IMGPREP_THREADS) row[i] = imgprep_keep(rule, m1, m2, r * W + i / C) ? s[i] : (uint8_t)0;
+    __syncthreads();
+    uint8_t* d = dst + r * cw * C;
+    for (int o = threadIdx.x; o < cw * C; o += IMGPREP_THREADS) {
+        const int j = o / C, c = o - C * j, xx = x0 + j;
+        int xmin = bounds[2 * xx], n = bounds[2 * xx + 1];
+        xmin = xmin < 0 ? 0 : (xmin > W - 1 ? W - 1 : xmin);
+        n = n > ksize ? ksize : n;
+        n = n > W - xmin ? W - xmin : n;
+        const int* k = coef + (long)xx * ksize;
+        unsigned acc = 1u << 21;
+        for (int x = 0; x < n; ++x) acc += (unsigned)row[(xmin + x) * C + c] * (unsigned)k[x];
+        d[o] = imgprep_clip8((int)acc);
+    }
+}
+
+// Vertical pass: src [B][H][cw][C] -> dst [B][ch][cw][C], only the window's rows y0 .. y0 + ch - 1.  grid = (ceil(row_bytes / 256), ch, B), row_bytes = cw C.
+__global__ __launch_bounds__(IMGPREP_THREADS) void resize_win_v_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int y0, int ch, int row_bytes,
+                                                                       const int* __restrict__ bounds, const int* __restrict__ coef, int ksize) {
+    const int o = blockIdx.x * IMGPREP_THREADS + threadIdx.x;
+    if (o >= row_bytes) return;
+    const int yy = y0 + blockIdx.y;
+    int ymin = bounds[2 * yy], n = bounds[2 * yy + 1];
+    ymin = ymin < 0 ? 0 : (ymin > H - 1 ? H - 1 : ymin);
+    n = n > ksize ? ksize : n;
+    n = n > H - ymin ? H - ymin : n;
+    const int* k = coef + (long)yy * ksize;
+    const uint8_t* s = src + ((long)blockIdx.z * H + ymin) * row_bytes + o;
+    unsigned acc = 1u << 21;
+    for (int y = 0; y < n; ++y) acc += (unsigned)s[(long)y * row_bytes] * (unsigned)k[y];
+    dst[((long)blockIdx.z * ch + blockIdx.y) * row_bytes + o] = imgprep_clip8((int)acc);
 }
 
 // Patch rows: src [B][H][W][3] uint8 -> out [B * (H / ps) * (W / ps)][ldo] of T; column j = (c, ky, kx) holds lut[c][src[b][py ps + ky][px ps + kx][c]],

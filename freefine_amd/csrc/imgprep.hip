@@ -1,5 +1,5 @@
 // Fifth translation unit of libfreefine_hip.so: the device image preparation of the DINOv2 feature metrics (imgprep.h).  A unit of its own, like dift.hip, so
-// that it compiles beside capi.hip; default code generation.  capi.o validates the arguments (ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows) and calls the
+// that it compiles beside capi.hip; default code generation.  capi.o validates the arguments (ffn_resize_pil_bilinear_u8, ffn_resize_pil_u8, ffn_vit_patch_rows) and calls the
 // hidden functions below; nothing here is exported.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,18 @@ extern "C" __attribute__((visibility("hidden"))) void fimgprep_resize(hipStream_
     const int row_bytes = 3 * ow;
     hipLaunchKernelGGL(resize_v_kernel, dim3((unsigned)((row_bytes + IMGPREP_THREADS - 1) / IMGPREP_THREADS), (unsigned)oh, (unsigned)B), dim3(IMGPREP_THREADS), 0, s,
                        scratch, dst, H, oh, row_bytes, vb, vk, vks);
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fimgprep_resize_win(hipStream_t s, const ffn_resize_pil_desc* d) {
+    (void)hipGetLastError();
+    const dim3 gh((unsigned)d->H, (unsigned)d->B), blk(IMGPREP_THREADS);
+    if (d->C == 1)
+        hipLaunchKernelGGL(resize_win_h_kernel<1>, gh, blk, 0, s, d->src, d->scratch, d->m1, d->m2, d->rule, d->W, d->x0, d->cw, d->hbounds, d->hcoef, d->hksize);
+    else
+        hipLaunchKernelGGL(resize_win_h_kernel<3>, gh, blk, 0, s, d->src, d->scratch, d->m1, d->m2, d->rule, d->W, d->x0, d->cw, d->hbounds, d->hcoef, d->hksize);
+    const int row_bytes = d->C * d->cw;
+    hipLaunchKernelGGL(resize_win_v_kernel, dim3((unsigned)((row_bytes + IMGPREP_THREADS - 1) / IMGPREP_THREADS), (unsigned)d->ch, (unsigned)d->B), blk, 0, s, d->scratch,
+                       d->dst, d->H, d->y0, d->ch, row_bytes, d->vbounds, d->vcoef, d->vksize);
 }
 
 extern "C" __attribute__((visibility("hidden"))) void fimgprep_patch_rows(hipStream_t s, int dtype, const uint8_t* src, const float* lut, void* out, int B, int H, int W,

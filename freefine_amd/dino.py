@@ -10,6 +10,11 @@ metrics, straight from decoded uint8 images on the device: `features_u8` = ffn_r
 ffn_vit_patch_rows (ToTensor + Normalize as a lookup, im2col) -> the same GEMM.  torchvision is absent here: the transform's semantics are torchvision's
 documented ones (see ops.py), the resize is pinned to PIL itself.
 
+`HipDino` is the same encoder as DINO v1's ViT-B/16, the extractor of Subject Consistency (evaluation/metrics/VBench/subject_consistency.py:10-35, torch.hub
+dino_vitb16): patch 16, 224 x 224 positional grid, no LayerScale.  DINO v1's own source is on neither machine; what IS pinned is the reference's vendored
+DinoVisionTransformer configured that way (patch_size=16, init_values=None, interpolate_offset=0.1; tests/golden/g15_dino16_cls.npz, tools/gen_golden.py
+run_g15), and the claim that this equals dino_vitb16 rests on the two published sources, not on a recording.
+
 dtype float32 = parity mode (exact-fp32 MFMA), bfloat16 = fast mode.  No split-bf16 mode, no graph capture, no class-token-only last block."""
 import math
 from types import SimpleNamespace
@@ -30,6 +35,14 @@ def dinov2_config(name="vitb"):
     return SimpleNamespace(name=name, embed_dim=enc[0], depth=enc[1], num_heads=enc[2], patch=14, img_size=518, mlp_ratio=4, interpolate_offset=0.1, ln_eps=1e-6)
 
 
+def dino_config(name="vitb16"):
+    """DINO v1 ViT-B/16 as the vendored DinoVisionTransformer spells it -- patch 16, img_size 224 (a 14 x 14 positional grid), no LayerScale (init_values=None),
+    interpolate_offset 0.1 -- and the small test size "tiny16" """
+    enc = {"vitb16": _ENC["vitb"], "tiny16": _ENC["tiny"]}[name]
+    return SimpleNamespace(name=name, embed_dim=enc[0], depth=enc[1], num_heads=enc[2], patch=16, img_size=224, mlp_ratio=4, interpolate_offset=0.1, ln_eps=1e-6,
+                           layerscale=False)
+
+
 def dinov2_param_shapes(cfg, prefix=""):
     """name -> shape of DinoVisionTransformer.state_dict() (hub layout; `prefix` = "pretrained." inside DPT_DINOv2)"""
     C, hid = cfg.embed_dim, cfg.embed_dim * cfg.mlp_ratio
@@ -38,13 +51,19 @@ def dinov2_param_shapes(cfg, prefix=""):
     sh = {p + "cls_token": (1, 1, C), p + "pos_embed": (1, n + 1, C), p + "mask_token": (1, C),
           p + "patch_embed.proj.weight": (C, 3, cfg.patch, cfg.patch), p + "patch_embed.proj.bias": (C,),
           p + "norm.weight": (C,), p + "norm.bias": (C,)}
+    ls = getattr(cfg, "layerscale", True)                      # dino_config: no ls*.gamma
     for i in range(cfg.depth):
         q = f"{p}blocks.{i}."
         sh.update({q + "norm1.weight": (C,), q + "norm1.bias": (C,), q + "attn.qkv.weight": (3 * C, C), q + "attn.qkv.bias": (3 * C,),
                    q + "attn.proj.weight": (C, C), q + "attn.proj.bias": (C,), q + "ls1.gamma": (C,),
                    q + "norm2.weight": (C,), q + "norm2.bias": (C,), q + "mlp.fc1.weight": (hid, C), q + "mlp.fc1.bias": (hid,),
                    q + "mlp.fc2.weight": (C, hid), q + "mlp.fc2.bias": (C,), q + "ls2.gamma": (C,)})
+        if not ls:
+            del sh[q + "ls1.gamma"], sh[q + "ls2.gamma"]
     return sh
+
+
+param_shapes = dinov2_param_shapes
 
 
 def synthetic_state(cfg, seed=0):
@@ -112,9 +131,9 @@ class HipDinoEncoder:
             wqkv, bqkv = st[q + "attn.qkv.weight"], st[q + "attn.qkv.bias"]
             b.qk = self._lin(wqkv[:2 * C], bqkv[:2 * C])        # q | k in one GEMM, V^T from its own (transposed-output) GEMM
             b.v = self._lin(wqkv[2 * C:], bqkv[2 * C:])
-            b.proj = self._lin(st[q + "attn.proj.weight"], st[q + "attn.proj.bias"], scale=st[q + "ls1.gamma"])
+            b.proj = self._lin(st[q + "attn.proj.weight"], st[q + "attn.proj.bias"], scale=st.get(q + "ls1.gamma"))      # no ls*.gamma: no LayerScale
             b.fc1 = self._lin(st[q + "mlp.fc1.weight"], st[q + "mlp.fc1.bias"])
-            b.fc2 = self._lin(st[q + "mlp.fc2.weight"], st[q + "mlp.fc2.bias"], scale=st[q + "ls2.gamma"])
+            b.fc2 = self._lin(st[q + "mlp.fc2.weight"], st[q + "mlp.fc2.bias"], scale=st.get(q + "ls2.gamma"))
             self.blocks.append(b)
         self.norm = (st[p + "norm.weight"].contiguous(), st[p + "norm.bias"].contiguous())
 
@@ -216,7 +235,7 @@ class HipDinoV2(HipDinoEncoder):
     @torch.no_grad()
     def forward(self, x):
         """x float [B, 3, H, W] (normalised image, H and W multiples of 14) -> fp32 [B, C]: the reference's model(batch) = head(x_norm_clstoken), head = identity"""
-        assert x.shape[2] % self.cfg.patch == 0 and x.shape[3] % self.cfg.patch == 0, "DINOv2 patch embedding: image sides must be multiples of 14"
+        assert x.shape[2] % self.cfg.patch == 0 and x.shape[3] % self.cfg.patch == 0, f"patch embedding: image sides must be multiples of {self.cfg.patch}"
         return self._cls(self._tokens(x)[0])
 
     __call__ = forward
@@ -231,3 +250,26 @@ class HipDinoV2(HipDinoEncoder):
         small = ops.resize_pil_bilinear_u8(img, size, size)
         a = ops.vit_patch_rows(small, self._lut, self.cfg.patch, self.kpe, self.dtype)
         return self._cls(self._embed(a, img.shape[0], size, size)[0])
+
+
+class HipDino(HipDinoV2):
+    """DINO ViT-B/16 (module docstring): the same class-token extractor at patch 16 without LayerScale; `forward` is HipDinoV2's.  `features_u8` is the transform
+    of subject_consistency.py:11-15 on the device -- image * keep mask, Resize(224) (short side to 224, PIL BILINEAR, NO crop: a non-square image stays
+    non-square), ToTensor, Normalize(imagenet) -- with the window that floors both sides to multiples of 16: the patch embedding of DINO v1 is a strided
+    convolution, which drops a trailing partial patch."""
+
+    @torch.no_grad()
+    def features_u8(self, images, keep=None, size=224):
+        """images uint8 [B, H, W, 3] of ONE size (numpy or torch, host or device); keep = None or (rule, m1, m2) as in ops.resize_pil_u8 (uint8 [B, H, W], host or
+        device) -> fp32 [B, C]"""
+        img = torch.as_tensor(images)
+        assert img.dtype == torch.uint8 and img.ndim == 4 and img.shape[-1] == 3
+        img = img.to(self.device).contiguous()
+        if keep is not None:
+            keep = (keep[0],) + tuple(None if m is None else torch.as_tensor(m).to(self.device).contiguous() for m in keep[1:])
+        ps = self.cfg.patch
+        oh, ow = ops.torchvision_resize_size(img.shape[1], img.shape[2], size)
+        H, W = oh // ps * ps, ow // ps * ps
+        small = ops.resize_pil_u8(img, oh, ow, "bilinear", crop=(0, 0, H, W), keep=keep)
+        a = ops.vit_patch_rows(small, self._lut, ps, self.kpe, self.dtype)
+        return self._cls(self._embed(a, img.shape[0], H, W)[0])

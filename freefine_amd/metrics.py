@@ -8,8 +8,17 @@ FID-DINO (FID/fid_dino.py) and Kernel Distance (FID/fid_kd.py) feed those functi
 (torchhub/facebookresearch_dinov2_main), so the extractor is built and pinned: freefine_amd/dino.py HipDinoV2 runs the encoder on the project's kernels (pinned to
 the vendored DinoVisionTransformer by tests/golden/g14_dinov2_cls.npz, tools/gen_golden.py run_g14) and prepares the images on the device, bit-exact against
 PIL (ops.resize_pil_bilinear_u8, ops.vit_patch_rows).  get_activations / calculate_fid_dino / calculate_fid_kd below are the drivers; the WEIGHTS still come
-from the caller (a state dict in hub layout: there is no hub download).  The other extractors of the suite (Inception-v3, DINO v1 ViT-B/16, CLIP image tower,
-HPSv2, ImageReward) have no model code in the reference tree, nothing to pin them to, and are NOT built.
+from the caller (a state dict in hub layout: there is no hub download).
+
+Background Consistency (VBench/background_consistency.py) and Subject Consistency (VBench/subject_consistency.py) say whether an edit kept what it should keep:
+the cosine between features of the source and the generated image, the background outside both masks (BGC: CLIP ViT-B/32 image embeddings) or the object inside
+its mask (SUBC: DINO ViT-B/16 class tokens).  Their extractors are pinned too: freefine_amd/clipvision.py HipCLIPVision to transformers'
+CLIPVisionModelWithProjection (the arithmetic of clip's encode_image), freefine_amd/dino.py HipDino to the vendored DinoVisionTransformer at patch 16 without
+LayerScale (tests/golden/g15_dino16_cls.npz).  Masking, resizing (PIL bicubic / bilinear bit for bit) and cropping run on the device in one entry
+(ops.resize_pil_u8).  consistency_pairs / calculate_bgc / calculate_subc below are the drivers; weights from the caller.
+
+The remaining extractors of the suite (Inception-v3 for FID, HPSv2, ImageReward) have no model code in the reference tree, nothing to pin them to, and are NOT
+built; evaluation/metrics/main.py reports them as such.
 
 Mean Distance (MD/mean_distance.py), the one metric of the suite that measures the GEOMETRY of an edit, needs no foreign network: its feature extractor is
 DIFT, i.e. Stable Diffusion itself, and runs on the project's kernels (freefine_amd/dift.py: HipVAE + HipUNet.features; the correspondence search is
@@ -157,6 +166,112 @@ def calculate_fid_kd(data, image_label, real_root_path, model, batch_size=64, re
     model = _dino_model(model)
     real, gen = parse_data(data, image_label, real_root_path)
     return kernel_distance(get_activations(real, model, batch_size, reader), get_activations(gen, model, batch_size, reader)).mean()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# Background Consistency (VBench/background_consistency.py) and Subject Consistency (VBench/subject_consistency.py)
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+def consistency_pairs(data, image_label):
+    """background_consistency.py:parse_data (:9-16) -> [(ori_img_path, generated image path, ori_mask_path, tgt_mask_path), ...]"""
+    return [(sample["ori_img_path"], sample[image_label], sample["ori_mask_path"], sample["tgt_mask_path"])
+            for image in data.values() for instance in image["instances"].values() for sample in instance.values()]
+
+
+def _consistency_read(pair, reader):
+    """the four arrays of one pair, checked: RGB uint8 images [H, W, 3], mode-"L" uint8 masks [h, w].  Other modes are refused: the reference multiplies the
+    image by mask[..., None], which means something else (or fails) for a palette / RGBA image or a multi-channel / 1-bit / 16-bit mask."""
+    if reader is None:
+        from PIL import Image
+        reader = lambda p: np.array(Image.open(p))
+    arrs = [np.asarray(reader(p)) for p in pair]
+    for p, a in zip(pair[:2], arrs[:2]):
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"{p}: RGB images only (8 bits, 3 channels); got dtype {a.dtype}, shape {a.shape}")
+    for p, a in zip(pair[2:], arrs[2:]):
+        if a.dtype != np.uint8 or a.ndim != 2:
+            raise ValueError(f"{p}: mode-\"L\" masks only (8 bits, one channel); got dtype {a.dtype}, shape {a.shape}")
+    return [np.ascontiguousarray(a) for a in arrs]
+
+
+def _mask_to(masks, hw, device):
+    """uint8 [B, h, w] -> [B, H, W]: PIL's mask.resize(image.size) with the default filter, which for mode "L" is BICUBIC; on the device (ffn_resize_pil_u8 with
+    one channel), skipped when the sizes already agree (GeoBench's do)"""
+    if tuple(masks.shape[1:]) == tuple(hw):
+        return masks
+    import torch
+    from . import ops
+    if device is None:
+        raise ValueError(f"masks of {masks.shape[2]} x {masks.shape[1]} for images of {hw[1]} x {hw[0]}: resizing them needs the extractor's `.device`")
+    return ops.resize_pil_u8(torch.as_tensor(masks).to(device).contiguous(), hw[0], hw[1], "bicubic")
+
+
+def consistency_scores(pairs, model, kind, batch_size=32, reader=None):
+    """The per-pair values of calculate_bgc (kind "bgc") / calculate_subc (kind "subc"), in the order of `pairs`.  Pairs are grouped by the sizes of their four
+    files so that one launch sees one size, batched by `batch_size` within a group.  model: anything with features_u8(uint8 [B, H, W, 3], keep=(rule, m1, m2))
+    -> [B, C] and (for masks that need resizing) a `.device`.
+      bgc   both masks resized to the SOURCE image's size; keep where (uint8)(m_ori + m_tgt) < 128 -- numpy's uint8 wrap, as in the reference -- applied to the
+            source and to the generated image alike, which therefore must have the source's size (the reference's multiplication fails otherwise)
+      subc  the source mask (resized to the source image) keeps the source image where it is > 128, the target mask (resized to the generated image) the
+            generated image
+    then F.normalize, F.cosine_similarity in fp32 and max(0.0, .) per pair."""
+    import torch
+    import torch.nn.functional as F
+    assert kind in ("bgc", "subc")
+    loaded = [_consistency_read(p, reader) for p in pairs]
+    groups = {}
+    for i, (src, gen, m1, m2) in enumerate(loaded):
+        if kind == "bgc" and gen.shape != src.shape:
+            raise ValueError(f"{pairs[i][1]}: generated image {gen.shape[1]} x {gen.shape[0]} but source {src.shape[1]} x {src.shape[0]}; Background Consistency "
+                             "masks both with one mask of the source's size")
+        groups.setdefault((src.shape, gen.shape, m1.shape, m2.shape), []).append(i)
+    dev = getattr(model, "device", None)
+    out = [None] * len(pairs)
+    for idx in groups.values():
+        for s in range(0, len(idx), batch_size):
+            part = idx[s:s + batch_size]
+            src, gen, m1, m2 = (np.stack([loaded[i][j] for i in part]) for j in range(4))
+            if kind == "bgc":
+                a, b = _mask_to(m1, src.shape[1:3], dev), _mask_to(m2, src.shape[1:3], dev)
+                fs, fg = model.features_u8(src, keep=("sum_lt128", a, b)), model.features_u8(gen, keep=("sum_lt128", a, b))
+            else:
+                fs = model.features_u8(src, keep=("gt128", _mask_to(m1, src.shape[1:3], dev), None))
+                fg = model.features_u8(gen, keep=("gt128", _mask_to(m2, gen.shape[1:3], dev), None))
+            fs, fg = (F.normalize(torch.as_tensor(f).float(), dim=-1, p=2) for f in (fs, fg))
+            cos = F.cosine_similarity(fs, fg).cpu()
+            for i, c in zip(part, cos):
+                out[i] = max(0.0, c.item())
+    return out
+
+
+def _clip_model(model):
+    """a HipCLIPVision as it is; a state dict (CLIP ViT-B/32: CLIPVisionModelWithProjection.state_dict() or the OpenAI checkpoint's visual.* names) becomes one in fp32"""
+    if isinstance(model, dict):
+        import torch
+        from .clipvision import HipCLIPVision
+        return HipCLIPVision("vitb32", model, dtype=torch.float32)
+    return model
+
+
+def _dino16_model(model):
+    """a HipDino as it is; a state dict (dino_vitb16 in the vendored DinoVisionTransformer's layout) becomes one in fp32"""
+    if isinstance(model, dict):
+        import torch
+        from .dino import HipDino, dino_config
+        return HipDino(dino_config("vitb16"), model, dtype=torch.float32)
+    return model
+
+
+def calculate_bgc(data, image_label, model, batch_size=32, reader=None):
+    """background_consistency.py:calculate_bgc: the mean over all pairs of the clamped cosine between the CLIP image embeddings of the masked source and the
+    masked generated image.  model: a HipCLIPVision or a CLIP ViT-B/32 state dict (the reference's clip.load downloads it; here the caller brings it)."""
+    scores = consistency_scores(consistency_pairs(data, image_label), _clip_model(model), "bgc", batch_size, reader)
+    return sum(scores) / len(scores)
+
+
+def calculate_subc(data, image_label, model, batch_size=32, reader=None):
+    """subject_consistency.py:calculate_subc: the same over DINO ViT-B/16 class tokens of the object cut out by its own mask.  model: a HipDino or a state dict."""
+    scores = consistency_scores(consistency_pairs(data, image_label), _dino16_model(model), "subc", batch_size, reader)
+    return sum(scores) / len(scores)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------

@@ -1076,6 +1076,124 @@ def resize_pil_bilinear_u8(img, oh, ow, out=None, scratch=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# the general PIL resize of the consistency metrics (csrc/imgprep.h resize_win_*; evaluation/metrics/VBench/{background,subject}_consistency.py).  CLIP's
+# transform is Resize(224, BICUBIC) + CenterCrop(224) of the PIL image, DINO's is torchvision Resize(224) (BILINEAR).  torchvision is absent here: the two
+# size rules below (torchvision_resize_size, center_crop_window) are torchvision's DOCUMENTED ones (transforms.functional.resize with an int size: "the smaller
+# edge of the image will be matched to this number", the other side int(size * long / short); center_crop: top = int(round((h - size) / 2.0)), likewise left),
+# not recorded from it.  The resampling itself is pinned to PIL (tests/test_consistency_cpu.py, tests/test_consistency_gpu.py).
+# ---------------------------------------------------------------------------------------------------------------
+PIL_FILTERS = ("bilinear", "bicubic")
+KEEP_RULES = {"sum_lt128": L.KEEP_SUM_LT128, "gt128": L.KEEP_GT128}
+
+
+def _pil_bicubic(x):
+    """libImaging/Resample.c bicubic_filter (a = -0.5), the C expression operation for operation in float64"""
+    import numpy as np
+    a = -0.5
+    x = np.abs(x)
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+def pil_resample_coeffs(in_size, out_size, filter="bilinear"):
+    """The tables of one axis of PIL's Image.resize on 8-bit images for `filter` in PIL_FILTERS, in the form of pil_bilinear_coeffs (which "bilinear" calls
+    through to: the same arrays).  "bicubic": support 2, a = -0.5, ksize = 2 ceil(2 max(in / out, 1)) + 1, SIGNED coefficients rounded as
+    normalize_coeffs_8bpc rounds them: int(-0.5 + w 2^22) for w < 0, int(0.5 + w 2^22) otherwise (the C cast truncates towards zero).  An axis whose size does
+    not change gets the identity from the filter itself (bicubic(+-1) = bicubic(+-2) = 0).  Pure host function, cached."""
+    import numpy as np
+    if filter == "bilinear":
+        return pil_bilinear_coeffs(in_size, out_size)
+    if filter != "bicubic":
+        raise ValueError(f"pil_resample_coeffs: filter {filter!r} (one of {PIL_FILTERS})")
+    key = (int(in_size), int(out_size), filter)
+    hit = _PIL_COEFFS.get(key)
+    if hit is not None:
+        return hit
+    n_in, n_out = key[:2]
+    assert n_in >= 1 and n_out >= 1
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = 2 * int(math.ceil(support)) + 1
+    ss = 1.0 / fs
+    bounds = np.zeros((n_out, 2), dtype=np.int32)
+    coef = np.zeros((n_out, ksize), dtype=np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        xmin = max(0, int(center - support + 0.5))
+        n = min(n_in, int(center + support + 0.5)) - xmin
+        w = _pil_bicubic((np.arange(n, dtype=np.float64) + xmin - center + 0.5) * ss)
+        tot = 0.0
+        for v in w:                                           # PIL sums the weights left to right in a double
+            tot += float(v)
+        if tot != 0.0:
+            w = w / tot
+        bounds[xx] = (xmin, n)
+        coef[xx, :n] = np.trunc(np.where(w < 0, -0.5, 0.5) + w * float(1 << 22)).astype(np.int64)
+    bounds.setflags(write=False)
+    coef.setflags(write=False)
+    hit = _PIL_COEFFS[key] = (bounds, coef)
+    return hit
+
+
+def _pil_resample_dev(in_size, out_size, filter, device):
+    if filter == "bilinear":
+        return _pil_coeffs_dev(in_size, out_size, device)
+    key = (int(in_size), int(out_size), filter, torch.device(device))
+    hit = _PIL_COEFFS_DEV.get(key)
+    if hit is None:
+        if len(_PIL_COEFFS_DEV) > 64:
+            _PIL_COEFFS_DEV.clear()
+        b, k = pil_resample_coeffs(in_size, out_size, filter)
+        hit = _PIL_COEFFS_DEV[key] = (torch.from_numpy(b.copy()).to(device), torch.from_numpy(k.copy()).to(device), k.shape[1])
+    return hit
+
+
+def torchvision_resize_size(h, w, size):
+    """(oh, ow) of torchvision's Resize(size) with an int size (its documented rule, see above): short side -> size, long side -> int(size * long / short)"""
+    if h <= w:
+        return size, int(size * w / h)
+    return int(size * h / w), size
+
+
+def center_crop_window(h, w, size):
+    """(top, left, size, size) of torchvision's CenterCrop(size) on an h x w image with both sides >= size (its documented rule, see above)"""
+    assert h >= size and w >= size
+    return int(round((h - size) / 2.0)), int(round((w - size) / 2.0)), size, size
+
+
+def resize_pil_u8(img, oh, ow, filter, crop=None, keep=None, out=None, scratch=None):
+    """uint8 [B, H, W, C] with C in (1, 3), or [B, H, W] (one channel), device and contiguous -> the window `crop` = (y0, x0, ch, cw) (default: everything) of
+    PIL's Image.resize((ow, oh), filter), bit for bit: uint8 [B, ch, cw, C] (or [B, ch, cw]) (ffn_resize_pil_u8).  keep = (rule, m1, m2) with rule in
+    KEEP_RULES, m1 / m2 uint8 [B, H, W] on the device (m2 may be None): pixels the rule drops read as 0, the masked image is never stored.
+    H, W, oh, ow <= _lib.IMGPREP_MAX_SIDE."""
+    lib = L.load()
+    assert img.dtype == torch.uint8 and img.ndim in (3, 4) and img.is_contiguous()
+    B, H, W = img.shape[:3]
+    C = 1 if img.ndim == 3 else img.shape[3]
+    y0, x0, ch, cw = (0, 0, oh, ow) if crop is None else (int(v) for v in crop)
+    hb, hk, hks = _pil_resample_dev(W, ow, filter, img.device)
+    vb, vk, vks = _pil_resample_dev(H, oh, filter, img.device)
+    if out is None:
+        out = torch.empty((B, ch, cw) + tuple(img.shape[3:]), dtype=torch.uint8, device=img.device)
+    if scratch is None:
+        scratch = torch.empty(B * H * cw * C, dtype=torch.uint8, device=img.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == B * ch * cw * C and scratch.dtype == torch.uint8 and scratch.numel() >= B * H * cw * C
+    d = L.ResizePilDesc()
+    d.src, d.dst, d.scratch = img.data_ptr(), out.data_ptr(), scratch.data_ptr()
+    d.hbounds, d.hcoef, d.vbounds, d.vcoef = hb.data_ptr(), hk.data_ptr(), vb.data_ptr(), vk.data_ptr()
+    d.B, d.H, d.W, d.C, d.oh, d.ow, d.hksize, d.vksize = B, H, W, C, oh, ow, hks, vks
+    d.y0, d.x0, d.ch, d.cw = y0, x0, ch, cw
+    d.rule = L.KEEP_NONE
+    if keep is not None:
+        rule, m1, m2 = keep
+        for m in (m1, m2):
+            assert m is None or (m.dtype == torch.uint8 and tuple(m.shape) == (B, H, W) and m.is_contiguous() and m.device == img.device)
+        d.rule, d.m1, d.m2 = KEEP_RULES[rule], m1.data_ptr(), (None if m2 is None else m2.data_ptr())
+    L.check(_timed("resize_pil_u8", 0.0, float(C) * B * (H * W + 2 * H * cw + ch * cw), lambda: lib.ffn_resize_pil_u8(_stream(), CT.byref(d))), "ffn_resize_pil_u8")
+    return out
+
+
 def vit_norm_table(mean, std):
     """[3, 256] fp32: ToTensor + Normalize(mean, std) of every byte value per channel, evaluated by the very torch expressions the transform runs on an image
     (float32(byte) / 255, then in place - float32(mean[c]), / float32(std[c])) -- the kernel only looks values up."""

@@ -377,6 +377,37 @@ int ffn_resize_pil_bilinear_u8(void* stream, const uint8_t* src, uint8_t* dst, u
                                const int* hcoef, int hksize, const int* vbounds, const int* vcoef, int vksize);
 int ffn_vit_patch_rows(void* stream, int dtype, const uint8_t* src, const float* lut, void* out, int B, int H, int W, int patch, int ldo);
 
+/* ---- the general PIL resize of the consistency metrics (Background / Subject Consistency; ABI version 6) -----------------------------------------
+ * Reference: evaluation/metrics/VBench/background_consistency.py:18-28 (image * keep mask, then CLIP's transform: PIL BICUBIC resize, centre crop),
+ * VBench/subject_consistency.py:10-22 (image * keep mask, torchvision Resize(224): PIL BILINEAR).  What ffn_resize_pil_bilinear_u8 does, plus:
+ *   any PIL filter   the caller gives the table widths (1 <= hksize, vksize <= FFN_IMGPREP_MAX_TAPS: what PIL's widest filter, Lanczos of support 3, needs at
+ *                    FFN_IMGPREP_MAX_SIDE); coefficients are signed (bicubic has negative taps); (first index, taps) are clamped into the row by the kernels
+ *   C = 1 or 3       src [B][H][W][C] (a mask is a one-channel image)
+ *   a crop window    rows y0 .. y0 + ch - 1 and columns x0 .. x0 + cw - 1 of the oh x ow destination the tables describe: dst [B][ch][cw][C],
+ *                    scratch [B][H][cw][C]; only the window is computed
+ *   a keep mask      rule FFN_KEEP_SUM_LT128: a pixel is kept iff (uint8)(m1 + m2) < 128 (numpy's uint8 wrap: 200 + 100 = 44 keeps, 128 + 128 = 0 keeps;
+ *                    m2 may be null = 0); FFN_KEEP_GT128: iff m1 > 128 (m2 ignored); a dropped pixel reads as 0 in all channels.  m1 / m2: uint8 [B][H][W].
+ *                    FFN_KEEP_NONE: no mask (m1, m2 ignored).  Masks need C = 3.  The masked image is never written to memory.
+ * Refused with FFN_EINVAL before any launch: null pointers, sides beyond FFN_IMGPREP_MAX_SIDE, C outside {1, 3}, a window outside the destination, an unknown
+ * rule, a mask with C = 1, a rule without m1, a table width outside 1 .. FFN_IMGPREP_MAX_TAPS.  B <= 65535. */
+#define FFN_IMGPREP_MAX_TAPS (2 * 3 * FFN_IMGPREP_MAX_SIDE + 1)
+enum { FFN_KEEP_NONE = 0, FFN_KEEP_SUM_LT128 = 1, FFN_KEEP_GT128 = 2 };
+typedef struct {
+    const uint8_t* src;
+    uint8_t* dst;
+    uint8_t* scratch;
+    const uint8_t* m1;
+    const uint8_t* m2;
+    const int* hbounds;
+    const int* hcoef;
+    const int* vbounds;
+    const int* vcoef;
+    int B, H, W, C, oh, ow, hksize, vksize;
+    int y0, x0, ch, cw;
+    int rule;
+} ffn_resize_pil_desc;
+int ffn_resize_pil_u8(void* stream, const ffn_resize_pil_desc* d);
+
 #ifdef __cplusplus
 }
 #endif

@@ -770,8 +770,45 @@ def run_g14():
     np.savez_compressed(os.path.join(GOLD, "g14_dinov2_cls.npz"), **out)
 
 
+# --------------------------------------------------------------------------------------------------------------
+# G15: the feature extractor of Subject Consistency -- DINO ViT-B/16 as the reference's vendored DinoVisionTransformer configured with patch 16 and no
+# LayerScale (DINO v1's own source is not in the reference tree: that this configuration IS dino_vitb16 is the claim freefine_amd/dino.py states), class tokens only
+# --------------------------------------------------------------------------------------------------------------
+G15_CASES = (("tiny16", 224, 224, 2), ("tiny16", 224, 288, 1), ("vitb16", 224, 224, 2))
+
+
+def g15_inputs(name, H, W, B):
+    """(configuration, seeded state in hub layout, input) of one G15 case -- tests/test_consistency_cpu.py restates these seeds"""
+    from freefine_amd import dino as FD
+    cfg = FD.dino_config(name)
+    return cfg, FD.synthetic_state(cfg, seed=15 + len(name)), rng_tensor(150 + H + W + len(name), (B, 3, H, W))
+
+
+def run_g15():
+    """model(x) of the in-tree DinoVisionTransformer(patch_size=16, init_values=None, interpolate_offset=0.1), seeded weights loaded strict=True: tiny16 at
+    224 x 224 and at 224 x 288 (positional embedding interpolated 14 x 14 -> 14 x 18), ViT-B/16 at 224 x 224.  Only the [B, C] class tokens are stored."""
+    hub = os.path.join(RH.REF, "torchhub", "facebookresearch_dinov2_main")
+    if hub not in sys.path:
+        sys.path.insert(0, hub)
+    import vision_transformer as vits
+    out = {}
+    for name, H, W, B in G15_CASES:
+        cfg, st, x = g15_inputs(name, H, W, B)
+        vit = vits.DinoVisionTransformer(img_size=cfg.img_size, patch_size=16, embed_dim=cfg.embed_dim, depth=cfg.depth, num_heads=cfg.num_heads,
+                                         mlp_ratio=cfg.mlp_ratio, init_values=None, ffn_layer="mlp", block_chunks=0, num_register_tokens=0,
+                                         interpolate_antialias=False, interpolate_offset=0.1).eval()
+        missing, unexpected = vit.load_state_dict(st, strict=True)
+        assert not missing and not unexpected
+        with torch.no_grad():
+            y = vit(x)
+        key = f"{name}_{H}x{W}"
+        out[key] = y.numpy()
+        print(f"[G15] {key}: class token |y|max {y.abs().max():.3f}, shape {tuple(y.shape)}")
+    np.savez_compressed(os.path.join(GOLD, "g15_dino16_cls.npz"), **out)
+
+
 if __name__ == "__main__":
-    only = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g6b", "g7", "g8", "g9", "g11", "g13", "g14"]
+    only = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g6b", "g7", "g8", "g9", "g11", "g13", "g14", "g15"]
     torch.set_grad_enabled(False)
     A, Mo = RH.import_reference()
     if "g1" in only:
@@ -798,3 +835,5 @@ if __name__ == "__main__":
         run_g13()
     if "g14" in only:
         run_g14()
+    if "g15" in only:
+        run_g15()
