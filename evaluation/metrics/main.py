@@ -2,14 +2,15 @@
 
     python evaluation/metrics/main.py --path <generated_results.json> [--task 100111111] [--level 0..3] [--no_rotate] [--3d]
            [--use_relative_path --base_dir <GeoBenchMeta>] [--fid_path <real images>] [--gen_img_key gen_img_path]
-           [--clip_weights <file>] [--dino_weights <file>] [--dinov2_weights <file>] [--model <SD folder | synthetic:sd21-base>]
+           [--clip_weights <file>] [--dino_weights <file>] [--dinov2_weights <file>] [--model <SD folder | synthetic:sd21-base>] [--precision f32|x3]
 
 --task is nine digits (1 = compute): FID, IRS, HPS, BGC, SUBC, WRAP_E, MD, FID_DINO, FID_KD.  The reference downloads its extractors (clip.load, torch.hub); there
 is no download here, the weights are local files: --clip_weights (CLIP ViT-B/32: a transformers CLIPVisionModelWithProjection state dict or the OpenAI
 checkpoint's visual.* names), --dino_weights (dino_vitb16), --dinov2_weights (dinov2_vitb14), each a .safetensors file or a torch.save'd state dict;
 --model is the Stable-Diffusion checkpoint whose features Mean Distance matches.  FID (Inception-v3), IRS (ImageReward) and HPS (HPSv2) have no model code in the
 reference tree to pin an implementation to: they are reported as `not built`, and the other metrics still run.  A metric whose weights were not given is
-reported as such, likewise."""
+reported as such, likewise.  --precision is the arithmetic of the networks: f32 (default: exact-fp32 MFMA) or x3 (split-bf16: hi + lo bf16 operand pairs, fp32
+accumulation; the three ViT towers are built with x3=True and the MD pipeline with from_pretrained(..., x3=True))."""
 import argparse
 import json
 import os
@@ -83,6 +84,7 @@ def main(argv=None):
     ap.add_argument("--dino_weights", default=None, help="DINO ViT-B/16 weights (SUBC)")
     ap.add_argument("--dinov2_weights", default=None, help="DINOv2 ViT-B/14 weights (FID_DINO, FID_KD)")
     ap.add_argument("--model", default=None, help="Stable-Diffusion folder or synthetic:<name> (MD)")
+    ap.add_argument("--precision", default="f32", choices=("f32", "x3"), help="arithmetic of the networks: f32 = exact fp32, x3 = split-bf16")
     ap.add_argument("--clip_config", default="vitb32", help=argparse.SUPPRESS)        # "tiny": the test sizes
     ap.add_argument("--dino_config", default="vitb16", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
@@ -94,6 +96,7 @@ def main(argv=None):
         data = filter_data(json.load(f), args)
     label = args.gen_img_key
     want = [n for n, t in zip(NAMES, args.task) if t == "1"]
+    x3 = args.precision == "x3"
 
     def dinov2():
         return load_state(args.dinov2_weights)
@@ -107,22 +110,22 @@ def main(argv=None):
             if not args.clip_weights:
                 return "not run (--clip_weights missing)"
             from freefine_amd.clipvision import HipCLIPVision
-            return FM.calculate_bgc(data, label, HipCLIPVision(args.clip_config, load_state(args.clip_weights), dtype=torch.float32))
+            return FM.calculate_bgc(data, label, HipCLIPVision(args.clip_config, load_state(args.clip_weights), dtype=torch.float32, x3=x3))
         if name == "SUBC":
             if not args.dino_weights:
                 return "not run (--dino_weights missing)"
             from freefine_amd.dino import HipDino, dino_config
-            return FM.calculate_subc(data, label, HipDino(dino_config(args.dino_config), load_state(args.dino_weights), dtype=torch.float32))
+            return FM.calculate_subc(data, label, HipDino(dino_config(args.dino_config), load_state(args.dino_weights), dtype=torch.float32, x3=x3))
         if name == "WRAP_E":
             return FM.calculate_we(data, label)
         if name == "MD":
             if not args.model:
                 return "not run (--model missing)"
             from freefine_amd.pipeline import FreeFinePipeline
-            return FM.calculate_md(data, label, FreeFinePipeline.from_pretrained(args.model, torch_dtype=torch.float32, device=torch.device("cuda:0")))
+            return FM.calculate_md(data, label, FreeFinePipeline.from_pretrained(args.model, torch_dtype=torch.float32, device=torch.device("cuda:0"), x3=x3))
         if not args.dinov2_weights or not args.fid_path:
             return "not run (--dinov2_weights or --fid_path missing)"
-        return (FM.calculate_fid_dino if name == "FID_DINO" else FM.calculate_fid_kd)(data, label, args.fid_path, dinov2())
+        return (FM.calculate_fid_dino if name == "FID_DINO" else FM.calculate_fid_kd)(data, label, args.fid_path, dinov2(), x3=x3)
 
     result = {}
     for name in want:

@@ -148,6 +148,7 @@ SYMBOLS = {
     "ffn_resize_pil_bilinear_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i]),
     "ffn_resize_pil_u8": (_i, [_vp, C.POINTER(ResizePilDesc)]),
     "ffn_vit_patch_rows": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "ffn_vit_patch_rows_pair": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "ffn_image_to_nhwc": (_i, [_vp, _i, _vp, _vp, _l, _i]),
     "ffn_nhwc_to_image": (_i, [_vp, _i, _vp, _vp, _i, _i, _i]),
 }

@@ -12,7 +12,13 @@ quick-gelu in the epilogues), `ffn_layernorm`, non-causal `ffn_attn` at S = 50 w
 `features_u8` is CLIP's transform on the device, from decoded uint8 images: image * keep mask, Resize(224, BICUBIC) (short side to 224), CenterCrop(224) -- one
 ffn_resize_pil_u8 with a crop window, PIL's bicubic bit for bit -- then ToTensor + Normalize(CLIP's mean / std) and the im2col as ffn_vit_patch_rows.
 
-dtype float32 = parity mode (exact-fp32 MFMA), bfloat16 = fast mode.  No split-bf16 mode."""
+dtype float32 = parity mode (exact-fp32 MFMA), float32 with x3=True = split-bf16, bfloat16 = fast mode.
+
+Split-bf16 (`HipCLIPVision(..., x3=True)`): every GEMM (the 768 -> 512 projection included) and the attention run FFN_BF16X3 -- operands as hi + lo bf16 pairs,
+three bf16 MFMAs per product term, fp32 accumulation -- built like text.HipCLIPTextEncoder: weights packed with ops.pack_linear(x3=True), layer_norm1 / 2 and
+post_layernorm write the pair rows their GEMMs read (`ffn_layernorm_pair`), attention and fc1 write pair rows for the GEMM behind them; the residual stream
+(pre_layrnorm writes it: fp32), the positional embedding, the class row and V^T stay fp32.  `features_u8` gets the patch GEMM's rows from
+`ffn_vit_patch_rows_pair` (pair rows straight from the bytes), `forward` from fp32 rows that ops.linear splits -- the same operand bytes."""
 from types import SimpleNamespace
 
 import torch
@@ -178,16 +184,20 @@ class HipCLIPVision:
     """CLIPVisionModelWithProjection(pixel_values).image_embeds = clip's encode_image on the HIP kernels (module docstring).  forward: float [B, 3, 224, 224]
     (normalised) -> fp32 [B, projection_dim]; features_u8: decoded uint8 images of any one size -> the same, the transform on the device."""
 
-    def __init__(self, config, state, dtype=torch.float32, device="cuda:0"):
+    def __init__(self, config, state, dtype=torch.float32, device="cuda:0", x3=False):
         assert dtype in (torch.float32, torch.bfloat16)
+        if x3 and dtype != torch.float32:
+            raise ValueError(f"x3=True (split-bf16) takes dtype=torch.float32: operands are split from fp32 values (dtype={dtype})")
         self.config = clip_vision_config(config)
-        self.dtype, self.device = dtype, torch.device(device)
+        self.dtype, self.device, self.x3 = dtype, torch.device(device), bool(x3)
         self.host = pack_vision_state(self.config, state)
         cfg, dev = self.config, self.device
         up = lambda k: self.host[k].to(dev)
-        lin = lambda k: (ops.pack_linear(up(k + ".w"), dtype), up(k + ".b"))
+        lin = lambda k: (ops.pack_linear(up(k + ".w"), dtype, x3=self.x3), up(k + ".b"))
         self.kpe = 3 * cfg.patch_size ** 2                       # 3072 at patch 32: whole 16-byte chunks
-        self.pe, self.proj = ops.pack_linear(up("pe.w"), dtype), ops.pack_linear(up("proj.w"), dtype)
+        if self.x3 and (self.kpe % 32 or cfg.hidden_size % 32 or cfg.intermediate_size % 32):
+            raise ValueError(f"HipCLIPVision x3: contraction lengths {self.kpe}, {cfg.hidden_size}, {cfg.intermediate_size} must be multiples of 32 (blocked pair rows)")
+        self.pe, self.proj = ops.pack_linear(up("pe.w"), dtype, x3=self.x3), ops.pack_linear(up("proj.w"), dtype, x3=self.x3)
         self.cls, self.pos = up("cls").to(dtype)[None].contiguous(), up("pos").to(dtype).contiguous()
         self.pre, self.post = (up("pre.w"), up("pre.b")), (up("post.w"), up("post.b"))
         self.blocks = [SimpleNamespace(ln1=(up(f"{i}.ln1.w"), up(f"{i}.ln1.b")), ln2=(up(f"{i}.ln2.w"), up(f"{i}.ln2.b")), qk=lin(f"{i}.qk"), v=lin(f"{i}.v"),
@@ -195,13 +205,14 @@ class HipCLIPVision:
         self._lut = ops.vit_norm_table(CLIP_MEAN, CLIP_STD).to(dev)
 
     @classmethod
-    def from_torch(cls, module, dtype=torch.float32, device="cuda:0"):
+    def from_torch(cls, module, dtype=torch.float32, device="cuda:0", x3=False):
         """from a transformers CLIPVisionModelWithProjection (its config and state_dict)"""
-        return cls(module.config, module.state_dict(), dtype=dtype, device=device)
+        return cls(module.config, module.state_dict(), dtype=dtype, device=device, x3=x3)
 
     def _tower(self, a, B):
-        """operand rows of the patch embedding [B n, 3 p p] in the activation dtype -> fp32 [B, projection_dim]"""
-        cfg = self.config
+        """operand rows of the patch embedding [B n, 3 p p] in the activation dtype (split-bf16: pair rows, or fp32 rows that ops.linear splits) -> fp32
+        [B, projection_dim]"""
+        cfg, x3 = self.config, self.x3
         C, nh, eps = cfg.hidden_size, cfg.num_attention_heads, cfg.layer_norm_eps
         n = self.pos.shape[0]
         S = n + 1
@@ -212,15 +223,15 @@ class HipCLIPVision:
         ld = (S + 7) // 8 * 8
         vt = torch.zeros(B, C, ld, dtype=self.dtype, device=self.device)      # V^T of every layer: padding columns zeroed once, no GEMM writes them
         for b in self.blocks:
-            y = ops.layernorm(x, *b.ln1, eps=eps)
+            y = ops.layernorm(x, *b.ln1, eps=eps, pair=x3)
             qk = ops.linear(y, b.qk[0], b.qk[1], K=C)                                               # [B, S, 2C]: q | k
             ops.linear(y, b.v[0], b.v[1], K=C, rows_per_batch=S, transposed_ld=ld, out=vt)
-            att = ops.attention(qk, qk[..., C:], vt, nh, 0.125, None, Sk=S, C=C)
+            att = ops.attention(qk, qk[..., C:], vt, nh, 0.125, None, Sk=S, C=C, x3=x3, out_pair=x3)
             x = ops.linear(att, b.o[0], b.o[1], K=C, residual=x)
-            y = ops.layernorm(x, *b.ln2, eps=eps)
-            h = ops.linear(y, b.fc1[0], b.fc1[1], K=C, qgelu=True)
+            y = ops.layernorm(x, *b.ln2, eps=eps, pair=x3)
+            h = ops.linear(y, b.fc1[0], b.fc1[1], K=C, qgelu=True, out_pair=x3)
             x = ops.linear(h, b.fc2[0], b.fc2[1], K=cfg.intermediate_size, residual=x)
-        pooled = ops.layernorm(x[:, 0].contiguous(), *self.post, eps=eps)                           # the class rows only
+        pooled = ops.layernorm(x[:, 0].contiguous(), *self.post, eps=eps, pair=x3)                  # the class rows only
         return ops.linear(pooled, self.proj, None, K=C).float()
 
     @torch.no_grad()
@@ -247,5 +258,8 @@ class HipCLIPVision:
         size = cfg.image_size
         oh, ow = ops.torchvision_resize_size(img.shape[1], img.shape[2], size)
         small = ops.resize_pil_u8(img, oh, ow, "bicubic", crop=ops.center_crop_window(oh, ow, size), keep=keep)
-        a = ops.vit_patch_rows(small, self._lut, cfg.patch_size, self.kpe, self.dtype)
+        if self.x3:
+            a = ops.vit_patch_rows_pair(small, self._lut, cfg.patch_size, self.kpe)
+        else:
+            a = ops.vit_patch_rows(small, self._lut, cfg.patch_size, self.kpe, self.dtype)
         return self._tower(a, img.shape[0])

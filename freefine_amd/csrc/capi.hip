@@ -70,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 6; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8
+extern "C" int ffn_version(void) { return 7; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -1210,6 +1210,22 @@ extern "C" int ffn_vit_patch_rows(void* stream, int dtype, const uint8_t* src, c
     REQUIRE(ldo >= 3 * patch * patch, "vit_patch_rows: ldo=%d below the %d columns of a patch", ldo, 3 * patch * patch);
     fimgprep_patch_rows(reinterpret_cast<hipStream_t>(stream), dtype, src, lut, out, B, H, W, patch, ldo);
     return check_launch("vit_patch_rows");
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fimgprep_patch_rows_pair(hipStream_t s, const uint8_t* src, const float* lut, void* out, int B, int H, int W, int ps,
+                                                                               int K);
+
+// the same rows as the pair operand of an FFN_BF16X3 GEMM (ABI version 7): 8 columns per thread, 16-byte stores
+extern "C" int ffn_vit_patch_rows_pair(void* stream, const uint8_t* src, const float* lut, void* out, int B, int H, int W, int patch, int K) {
+    const int lim = FFN_IMGPREP_MAX_SIDE;
+    REQUIRE(src && lut && out, "vit_patch_rows_pair: null pointer");
+    REQUIRE(B >= 1 && H >= 1 && W >= 1 && H <= lim && W <= lim, "vit_patch_rows_pair: bad shape B=%d, %d x %d (sides 1 .. %d, FFN_IMGPREP_MAX_SIDE)", B, H, W, lim);
+    REQUIRE(patch >= 1 && patch <= 256 && H % patch == 0 && W % patch == 0, "vit_patch_rows_pair: %d x %d is not whole patches of %d (1 .. 256)", H, W, patch);
+    REQUIRE(K >= 3 * patch * patch, "vit_patch_rows_pair: K=%d below the %d columns of a patch", K, 3 * patch * patch);
+    REQUIRE(K % 8 == 0, "vit_patch_rows_pair: K=%d is not a multiple of 8 (16-byte stores of both halves)", K);
+    REQUIRE(aligned16(out), "vit_patch_rows_pair: out must be 16-byte aligned");
+    fimgprep_patch_rows_pair(reinterpret_cast<hipStream_t>(stream), src, lut, out, B, H, W, patch, K);
+    return check_launch("vit_patch_rows_pair");
 }
 
 // ---- elementwise / resampling helpers of the depth front end ----------------------------------------------------------

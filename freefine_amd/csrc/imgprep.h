@@ -8,6 +8,8 @@
 //   resize_win_h_kernel / _v_kernel     the same passes for any PIL filter's tables, 1 or 3 channels, a destination crop window and a keep mask (below)
 //   patch_rows_kernel                   ToTensor + Normalize as a [3][256] lookup (evaluated on the host by torch) and the im2col of a ViT patch embedding
 //                                       (Conv2d(kernel = stride = patch)): one row per patch, columns (channel, ky, kx), zero padding up to ldo.
+//   patch_rows_pair_kernel              the same rows as the split-bf16 PAIR operand of an FFN_BF16X3 GEMM (hi = bf16(v), lo = bf16(v - hi); layout: common.h
+//                                       pair_pos): what patch_rows_kernel<float> + split_pair8_kernel write, bit for bit, without the fp32 rows in between.
 //
 // Traffic is small (a 512 x 512 image is 768 KB in, 147 KB out), so the kernels are plain: byte loads that are contiguous across a workgroup's threads
 // (bytes along an image row are contiguous over (x, c)), no vector loads (an image row starts at any byte address).
@@ -142,5 +144,48 @@ __global__ __launch_bounds__(IMGPREP_THREADS) void patch_rows_kernel(const uint8
             v = tab[c * 256 + src[((b * H + (long)py * ps + ky) * W + (long)px * ps + kx) * 3 + c]];
         }
         DT<T>::st(out + i, v);
+    }
+}
+
+// Patch rows in pair form: src [B][H][W][3] uint8 -> out bf16 [B * (H / ps) * (W / ps)][2K], the pair form of rows of K fp32 columns (K % 32 == 0: 128-byte
+// blocks [hi(32) | lo(32)]; else the planes [hi(K) | lo(K)]); columns 3 ps ps .. K - 1 are zero in both halves.  The table has 768 entries, so its split is
+// done once per workgroup: tab[c][byte] = hi | lo << 16 with hi = bf16(v) (RNE), lo = bf16(v - hi) -- the arithmetic of split_pair8_kernel -- and an element
+// costs one byte load and one LDS lookup.  One thread per 8 consecutive columns of a row (K % 8 == 0: a run of 8 never crosses a 32-column block), so both
+// halves leave as 16-byte stores; the (c, ky, kx) of the run's first column is divided out once and stepped from there.
+__global__ __launch_bounds__(IMGPREP_THREADS) void patch_rows_pair_kernel(const uint8_t* __restrict__ src, const float* __restrict__ lut, bf16* __restrict__ out, long total,
+                                                                          int H, int W, int ps, int K) {
+    __shared__ uint32_t tab[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += IMGPREP_THREADS) {
+        const float v = lut[i];
+        const uint32_t hi = f32_to_bf16(v);
+        tab[i] = hi | ((uint32_t)f32_to_bf16(v - bf16_to_f32((uint16_t)hi)) << 16);
+    }
+    __syncthreads();
+    const int pw = W / ps, ph = H / ps, pp = ps * ps, kq = K >> 3, lo_off = pair_lo(K);
+    for (long i = (long)blockIdx.x * IMGPREP_THREADS + threadIdx.x; i < total; i += (long)gridDim.x * IMGPREP_THREADS) {
+        const long m = i / kq;
+        const int j0 = (int)(i - m * kq) << 3;
+        const long b = m / ((long)ph * pw);
+        const int p = (int)(m - b * ph * pw), py = p / pw, px = p - py * pw;
+        int c = j0 / pp, rem = j0 - c * pp, ky = rem / ps, kx = rem - ky * ps;
+        uint32_t e[8];
+#pragma unroll
+        for (int w = 0; w < 8; ++w) {
+            e[w] = 0u;
+            if (j0 + w < 3 * pp) e[w] = tab[c * 256 + src[((b * H + (long)py * ps + ky) * W + (long)px * ps + kx) * 3 + c]];
+            if (++kx == ps) {
+                kx = 0;
+                if (++ky == ps) { ky = 0; ++c; }
+            }
+        }
+        u32x4 hi, lo;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            hi[w] = (e[2 * w] & 0xffffu) | (e[2 * w + 1] << 16);
+            lo[w] = (e[2 * w] >> 16) | (e[2 * w + 1] & 0xffff0000u);
+        }
+        bf16* q = out + m * 2 * K + pair_pos(j0, K);
+        *reinterpret_cast<u32x4*>(q) = hi;
+        *reinterpret_cast<u32x4*>(q + lo_off) = lo;
     }
 }

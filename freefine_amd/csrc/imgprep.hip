@@ -1,5 +1,5 @@
 // Fifth translation unit of libfreefine_hip.so: the device image preparation of the DINOv2 feature metrics (imgprep.h).  A unit of its own, like dift.hip, so
-// that it compiles beside capi.hip; default code generation.  capi.o validates the arguments (ffn_resize_pil_bilinear_u8, ffn_resize_pil_u8, ffn_vit_patch_rows) and calls the
+// that it compiles beside capi.hip; default code generation.  capi.o validates the arguments (ffn_resize_pil_bilinear_u8, ffn_resize_pil_u8, ffn_vit_patch_rows, ffn_vit_patch_rows_pair) and calls the
 // hidden functions below; nothing here is exported.
 #include <hip/hip_runtime.h>
 
@@ -35,4 +35,13 @@ extern "C" __attribute__((visibility("hidden"))) void fimgprep_patch_rows(hipStr
     const unsigned grid = (unsigned)(g > 8192 ? 8192 : g);
     if (dtype == FFN_BF16) hipLaunchKernelGGL(patch_rows_kernel<bf16>, dim3(grid), dim3(IMGPREP_THREADS), 0, s, src, lut, static_cast<bf16*>(out), total, H, W, ps, ldo);
     else hipLaunchKernelGGL(patch_rows_kernel<float>, dim3(grid), dim3(IMGPREP_THREADS), 0, s, src, lut, static_cast<float*>(out), total, H, W, ps, ldo);
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fimgprep_patch_rows_pair(hipStream_t s, const uint8_t* src, const float* lut, void* out, int B, int H, int W, int ps,
+                                                                               int K) {
+    (void)hipGetLastError();
+    const long total = (long)B * (H / ps) * (W / ps) * (K / 8);      // one thread per 8 columns
+    long g = (total + IMGPREP_THREADS - 1) / IMGPREP_THREADS;
+    const unsigned grid = (unsigned)(g > 8192 ? 8192 : g);
+    hipLaunchKernelGGL(patch_rows_pair_kernel, dim3(grid), dim3(IMGPREP_THREADS), 0, s, src, lut, static_cast<bf16*>(out), total, H, W, ps, K);
 }

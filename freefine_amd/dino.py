@@ -15,7 +15,14 @@ dino_vitb16): patch 16, 224 x 224 positional grid, no LayerScale.  DINO v1's own
 DinoVisionTransformer configured that way (patch_size=16, init_values=None, interpolate_offset=0.1; tests/golden/g15_dino16_cls.npz, tools/gen_golden.py
 run_g15), and the claim that this equals dino_vitb16 rests on the two published sources, not on a recording.
 
-dtype float32 = parity mode (exact-fp32 MFMA), bfloat16 = fast mode.  No split-bf16 mode, no graph capture, no class-token-only last block."""
+dtype float32 = parity mode (exact-fp32 MFMA), float32 with x3=True = split-bf16 (below), bfloat16 = fast mode.  No graph capture, no class-token-only last block.
+
+Split-bf16 (`HipDinoV2(..., x3=True)`, `HipDino` likewise; the depth network passes no x3 and stays as it is): every GEMM and the attention run FFN_BF16X3 --
+operands as hi + lo bf16 pairs, three bf16 MFMAs per product term, fp32 accumulation -- built like text.HipCLIPTextEncoder: weights packed with
+ops.pack_linear(x3=True) (LayerScale folded BEFORE the split), LayerNorms write the pair rows their GEMMs read (`ffn_layernorm_pair`), attention and fc1 write
+pair rows for the GEMM behind them; the residual stream, the positional embedding, the class row and V^T stay fp32.  The patch embedding's contraction length is
+rounded up to a multiple of 32 (608 at patch 14) so that both operands are in the blocked pair form; `features_u8` gets its rows from
+`ffn_vit_patch_rows_pair` (pair rows straight from the bytes), `forward` from fp32 rows that ops.linear splits -- the same operand bytes."""
 import math
 from types import SimpleNamespace
 
@@ -92,9 +99,11 @@ class _O:
 class HipDinoEncoder:
     """The DINOv2 ViT encoder: weights packed from `<prefix>*` of a state dict, tokens, blocks.  Subclasses add what they read off the tokens."""
 
-    def _init_encoder(self, cfg, dtype, device):
+    def _init_encoder(self, cfg, dtype, device, x3=False):
         assert dtype in (torch.float32, torch.bfloat16)
-        self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
+        if x3 and dtype != torch.float32:
+            raise ValueError(f"x3=True (split-bf16) takes dtype=torch.float32: operands are split from fp32 values (dtype={dtype})")
+        self.cfg, self.dtype, self.device, self.x3 = cfg, dtype, torch.device(device), bool(x3)
         C = cfg.embed_dim
         assert C % cfg.num_heads == 0 and C % 8 == 0, "channel counts must be whole 16-byte chunks"
         self._pos = {}
@@ -110,18 +119,18 @@ class HipDinoEncoder:
         if n_pad and n_pad > w.shape[0]:
             w = torch.cat([w, torch.zeros(n_pad - w.shape[0], w.shape[1], device=w.device)], 0)
             b = None if b is None else torch.cat([b, torch.zeros(n_pad - b.shape[0], device=b.device)], 0)
-        return ops.pack_linear(w.contiguous(), self.dtype), (None if b is None else b.float().contiguous()), w.shape[1]
+        return ops.pack_linear(w.contiguous(), self.dtype, x3=self.x3), (None if b is None else b.float().contiguous()), w.shape[1]
 
     def _pack_encoder(self, st, p):
         """st: fp32 tensors on the device; p: the prefix of the ViT's parameters (`pretrained.` inside DPT_DINOv2, empty in hub layout)"""
         cfg = self.cfg
         C = cfg.embed_dim
-        e = 8
+        e = 32 if self.x3 else 8                              # split-bf16: whole 32-column blocks, so that both operands are in the blocked pair form
         K = 3 * cfg.patch * cfg.patch
-        self.kpe = (K + e - 1) // e * e                        # patch-embedding contraction length, padded to whole chunks
+        self.kpe = (K + e - 1) // e * e                        # patch-embedding contraction length, padded to whole chunks (patch 14: 592; split-bf16: 608)
         wpe = torch.zeros(C, self.kpe, device=self.device)
         wpe[:, :K] = st[p + "patch_embed.proj.weight"].reshape(C, K)
-        self.pe = (ops.pack_linear(wpe, self.dtype), st[p + "patch_embed.proj.bias"].contiguous())
+        self.pe = (ops.pack_linear(wpe, self.dtype, x3=self.x3), st[p + "patch_embed.proj.bias"].contiguous())
         self.pos_embed, self.cls_token = st[p + "pos_embed"], st[p + "cls_token"]
         self.blocks = []
         for i in range(cfg.depth):
@@ -182,7 +191,8 @@ class HipDinoEncoder:
         return a
 
     def _embed(self, a, B, H, W):
-        """patch embedding of given operand rows (a GEMM, positional embedding added as the GEMM's residual) + class row -> ([B, 1 + ph * pw, C], ph, pw)"""
+        """patch embedding of given operand rows (a GEMM, positional embedding added as the GEMM's residual) + class row -> ([B, 1 + ph * pw, C], ph, pw).
+        Split-bf16: a = pair rows (ops.vit_patch_rows_pair) or fp32 rows, which ops.linear splits."""
         ps = self.cfg.patch
         ph, pw = H // ps, W // ps
         cls_row, pos = self._pos_tokens(H, W)
@@ -196,15 +206,15 @@ class HipDinoEncoder:
         return self._embed(self._patch_rows(x), B, H, W)
 
     def _block(self, b, t, B, S):
-        cfg = self.cfg
+        cfg, x3 = self.cfg, self.x3                  # split-bf16: the norms, the attention and fc1 write the pair rows the GEMM behind them reads
         C, nh = cfg.embed_dim, cfg.num_heads
-        y = ops.layernorm(t, *b.n1, eps=cfg.ln_eps)
+        y = ops.layernorm(t, *b.n1, eps=cfg.ln_eps, pair=x3)
         qk = ops.linear(y, b.qk[0], b.qk[1], K=C)                                   # [B, S, 2C]: q | k
         vt = ops.linear(y, b.v[0], b.v[1], K=C, rows_per_batch=S, transposed_ld=(S + 7) // 8 * 8)      # V^T [B, C, S']
-        a = ops.attention(qk, qk[..., C:], vt, nh, (C // nh) ** -0.5, None, Sk=S, C=C)
+        a = ops.attention(qk, qk[..., C:], vt, nh, (C // nh) ** -0.5, None, Sk=S, C=C, x3=x3, out_pair=x3)
         t = ops.linear(a, b.proj[0], b.proj[1], K=C, residual=t)                     # x + ls1 * proj(attn)
-        y = ops.layernorm(t, *b.n2, eps=cfg.ln_eps)
-        y = ops.linear(y, b.fc1[0], b.fc1[1], K=C, gelu=True)
+        y = ops.layernorm(t, *b.n2, eps=cfg.ln_eps, pair=x3)
+        y = ops.linear(y, b.fc1[0], b.fc1[1], K=C, gelu=True, out_pair=x3)
         return ops.linear(y, b.fc2[0], b.fc2[1], K=C * cfg.mlp_ratio, residual=t)    # x + ls2 * fc2(gelu(fc1))
 
     def _run_blocks(self, t, keep_last=1):
@@ -221,14 +231,21 @@ class HipDinoEncoder:
 class HipDinoV2(HipDinoEncoder):
     """DinoVisionTransformer.forward with the hub's identity head: the final LayerNorm's class token (vision_transformer.py:319-324, 236-257)."""
 
-    def __init__(self, cfg, state, dtype=torch.float32, device="cuda:0"):
-        """state: DinoVisionTransformer.state_dict() in hub layout (no `pretrained.` prefix; mask_token accepted and unused)"""
-        self._init_encoder(cfg, dtype, device)
+    def __init__(self, cfg, state, dtype=torch.float32, device="cuda:0", x3=False):
+        """state: DinoVisionTransformer.state_dict() in hub layout (no `pretrained.` prefix; mask_token accepted and unused); x3: split-bf16 arithmetic (module
+        docstring; needs dtype float32, ValueError otherwise)"""
+        self._init_encoder(cfg, dtype, device, x3=x3)
         self._pack_encoder({k: v.detach().to(self.device, torch.float32) for k, v in state.items()}, "")
         self._lut = ops.vit_norm_table(IMAGENET_MEAN, IMAGENET_STD).to(self.device)
 
+    def _rows_u8(self, small):
+        """resized uint8 images -> the patch GEMM's operand rows: the activation dtype's, or the pair rows of split-bf16"""
+        if self.x3:
+            return ops.vit_patch_rows_pair(small, self._lut, self.cfg.patch, self.kpe)
+        return ops.vit_patch_rows(small, self._lut, self.cfg.patch, self.kpe, self.dtype)
+
     def _cls(self, t):
-        """tokens -> blocks -> final LayerNorm on the class rows only -> fp32 [B, C]"""
+        """tokens -> blocks -> final LayerNorm on the class rows only (fp32 in split-bf16 mode too) -> fp32 [B, C]"""
         last = self._run_blocks(t, 1)[0]
         return ops.layernorm(last[:, 0].contiguous(), *self.norm, eps=self.cfg.ln_eps).float()
 
@@ -248,7 +265,7 @@ class HipDinoV2(HipDinoEncoder):
         assert img.dtype == torch.uint8 and img.ndim == 4 and img.shape[-1] == 3 and size % self.cfg.patch == 0
         img = img.to(self.device).contiguous()
         small = ops.resize_pil_bilinear_u8(img, size, size)
-        a = ops.vit_patch_rows(small, self._lut, self.cfg.patch, self.kpe, self.dtype)
+        a = self._rows_u8(small)
         return self._cls(self._embed(a, img.shape[0], size, size)[0])
 
 
@@ -271,5 +288,5 @@ class HipDino(HipDinoV2):
         oh, ow = ops.torchvision_resize_size(img.shape[1], img.shape[2], size)
         H, W = oh // ps * ps, ow // ps * ps
         small = ops.resize_pil_u8(img, oh, ow, "bilinear", crop=(0, 0, H, W), keep=keep)
-        a = ops.vit_patch_rows(small, self._lut, ps, self.kpe, self.dtype)
+        a = self._rows_u8(small)
         return self._cls(self._embed(a, img.shape[0], H, W)[0])

@@ -141,29 +141,31 @@ def parse_data(data, image_label, real_root_path):
     return [os.path.join(real_root_path, n) for n in os.listdir(real_root_path)], gen
 
 
-def _dino_model(model):
-    """a HipDinoV2 as it is; a state dict (DinoVisionTransformer.state_dict() of dinov2_vitb14, hub layout) becomes one in fp32, like the reference's model"""
+def _dino_model(model, x3=False):
+    """a HipDinoV2 as it is; a state dict (DinoVisionTransformer.state_dict() of dinov2_vitb14, hub layout) becomes one in fp32, like the reference's model
+    (x3: in split-bf16 arithmetic -- only where the tower is built here; a ready model keeps its own mode)"""
     if isinstance(model, dict):
         import torch
         from .dino import HipDinoV2, dinov2_config
-        return HipDinoV2(dinov2_config("vitb"), model, dtype=torch.float32)
+        return HipDinoV2(dinov2_config("vitb"), model, dtype=torch.float32, x3=x3)
     return model
 
 
-def calculate_fid_dino(data, image_label, real_root_path, model, batch_size=64, reader=None):
+def calculate_fid_dino(data, image_label, real_root_path, model, batch_size=64, reader=None, x3=False):
     """fid_dino.py:calculate_fid_dino: the Frechet distance between the DINOv2 class tokens of the real images (the listing of real_root_path) and of the generated
-    ones (data[...][image_label]).  model: a HipDinoV2 or a dinov2_vitb14 state dict (the reference downloads it from the hub; here the caller brings it)."""
-    model = _dino_model(model)
+    ones (data[...][image_label]).  model: a HipDinoV2 or a dinov2_vitb14 state dict (the reference downloads it from the hub; here the caller brings it);
+    x3: a tower built from a state dict runs split-bf16 arithmetic."""
+    model = _dino_model(model, x3)
     real, gen = parse_data(data, image_label, real_root_path)
     m1, s1 = feature_statistics(get_activations(real, model, batch_size, reader))
     m2, s2 = feature_statistics(get_activations(gen, model, batch_size, reader))
     return frechet_distance(m1, s1, m2, s2)
 
 
-def calculate_fid_kd(data, image_label, real_root_path, model, batch_size=64, reader=None):
+def calculate_fid_kd(data, image_label, real_root_path, model, batch_size=64, reader=None, x3=False):
     """fid_kd.py:calculate_fid_kd: the mean of kernel_distance(real, generated) over DINOv2 class tokens (numpy's global generator picks the subsets, as in
-    the reference)"""
-    model = _dino_model(model)
+    the reference); x3 as in calculate_fid_dino"""
+    model = _dino_model(model, x3)
     real, gen = parse_data(data, image_label, real_root_path)
     return kernel_distance(get_activations(real, model, batch_size, reader), get_activations(gen, model, batch_size, reader)).mean()
 
@@ -243,34 +245,37 @@ def consistency_scores(pairs, model, kind, batch_size=32, reader=None):
     return out
 
 
-def _clip_model(model):
-    """a HipCLIPVision as it is; a state dict (CLIP ViT-B/32: CLIPVisionModelWithProjection.state_dict() or the OpenAI checkpoint's visual.* names) becomes one in fp32"""
+def _clip_model(model, x3=False):
+    """a HipCLIPVision as it is; a state dict (CLIP ViT-B/32: CLIPVisionModelWithProjection.state_dict() or the OpenAI checkpoint's visual.* names) becomes one in fp32
+    (x3: in split-bf16 arithmetic)"""
     if isinstance(model, dict):
         import torch
         from .clipvision import HipCLIPVision
-        return HipCLIPVision("vitb32", model, dtype=torch.float32)
+        return HipCLIPVision("vitb32", model, dtype=torch.float32, x3=x3)
     return model
 
 
-def _dino16_model(model):
-    """a HipDino as it is; a state dict (dino_vitb16 in the vendored DinoVisionTransformer's layout) becomes one in fp32"""
+def _dino16_model(model, x3=False):
+    """a HipDino as it is; a state dict (dino_vitb16 in the vendored DinoVisionTransformer's layout) becomes one in fp32 (x3: in split-bf16 arithmetic)"""
     if isinstance(model, dict):
         import torch
         from .dino import HipDino, dino_config
-        return HipDino(dino_config("vitb16"), model, dtype=torch.float32)
+        return HipDino(dino_config("vitb16"), model, dtype=torch.float32, x3=x3)
     return model
 
 
-def calculate_bgc(data, image_label, model, batch_size=32, reader=None):
+def calculate_bgc(data, image_label, model, batch_size=32, reader=None, x3=False):
     """background_consistency.py:calculate_bgc: the mean over all pairs of the clamped cosine between the CLIP image embeddings of the masked source and the
-    masked generated image.  model: a HipCLIPVision or a CLIP ViT-B/32 state dict (the reference's clip.load downloads it; here the caller brings it)."""
-    scores = consistency_scores(consistency_pairs(data, image_label), _clip_model(model), "bgc", batch_size, reader)
+    masked generated image.  model: a HipCLIPVision or a CLIP ViT-B/32 state dict (the reference's clip.load downloads it; here the caller brings it); x3: a
+    tower built from a state dict runs split-bf16 arithmetic."""
+    scores = consistency_scores(consistency_pairs(data, image_label), _clip_model(model, x3), "bgc", batch_size, reader)
     return sum(scores) / len(scores)
 
 
-def calculate_subc(data, image_label, model, batch_size=32, reader=None):
-    """subject_consistency.py:calculate_subc: the same over DINO ViT-B/16 class tokens of the object cut out by its own mask.  model: a HipDino or a state dict."""
-    scores = consistency_scores(consistency_pairs(data, image_label), _dino16_model(model), "subc", batch_size, reader)
+def calculate_subc(data, image_label, model, batch_size=32, reader=None, x3=False):
+    """subject_consistency.py:calculate_subc: the same over DINO ViT-B/16 class tokens of the object cut out by its own mask.  model: a HipDino or a state dict; x3 as in
+    calculate_bgc."""
+    scores = consistency_scores(consistency_pairs(data, image_label), _dino16_model(model, x3), "subc", batch_size, reader)
     return sum(scores) / len(scores)
 
 

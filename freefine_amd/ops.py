@@ -1219,6 +1219,23 @@ def vit_patch_rows(img, lut, patch, ldo, dtype, out=None):
     return out
 
 
+def vit_patch_rows_pair(img, lut, patch, K, out=None):
+    """uint8 [B, H, W, 3] (device) + lut fp32 [3, 256] (device) -> bf16 PAIR rows [B (H / patch)(W / patch), 2K] (ffn_vit_patch_rows_pair; layout:
+    include/freefine_hip.h FFN_BF16X3): the bytes split_pair(vit_patch_rows(..., K, torch.float32)) gives, in one pass -- the A operand of the split-bf16
+    patch-embedding GEMM.  K % 8 == 0; columns from 3 patch^2 on are zero in both halves."""
+    lib = L.load()
+    assert img.dtype == torch.uint8 and img.ndim == 4 and img.shape[-1] == 3 and img.is_contiguous()
+    assert lut.dtype == torch.float32 and lut.shape == (3, 256) and lut.is_contiguous() and lut.device == img.device
+    B, H, W, _ = img.shape
+    M = B * (H // patch) * (W // patch)
+    if out is None:
+        out = torch.empty(M, 2 * K, dtype=torch.bfloat16, device=img.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == M * 2 * K
+    L.check(_timed("patch_rows_pair_kernel", 0.0, 3.0 * B * H * W + 4.0 * M * K,
+                   lambda: lib.ffn_vit_patch_rows_pair(_stream(), img.data_ptr(), lut.data_ptr(), out.data_ptr(), B, H, W, patch, K)), "ffn_vit_patch_rows_pair")
+    return _mark_pair(out, K)
+
+
 def image_to_nhwc(img_u8, CP, dtype, out=None):
     """uint8 [B,H,W,3] -> dtype [B,HW,CP] in [-1,1]."""
     lib = L.load()

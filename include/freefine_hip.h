@@ -371,11 +371,18 @@ long ffn_dift_workspace_bytes(int C, int h, int w, int K);
  * ffn_vit_patch_rows: out [B (H / patch)(W / patch)][ldo] in fp32 (FFN_F32) or bf16 (FFN_BF16, round to nearest even): row = patch (row-major over the patch
  * grid), column (c, ky, kx) = lut[c][src[b][py patch + ky][px patch + kx][c]], columns 3 patch^2 .. ldo - 1 zero -- the im2col rows of
  * Conv2d(3, C, kernel = stride = patch) over the normalised image.  lut: device fp32 [3][256], ToTensor + Normalize per channel and byte value, evaluated by the
- * caller.  H, W multiples of patch; ldo >= 3 patch^2. */
+ * caller.  H, W multiples of patch; ldo >= 3 patch^2.  FFN_BF16X3 is refused: the pair form has an entry of its own.
+ *
+ * ffn_vit_patch_rows_pair (ABI version 7): the same rows as the A operand of an FFN_BF16X3 GEMM -- out bf16 [B (H / patch)(W / patch)][2K], the PAIR form (FFN_BF16X3
+ * above) of rows of K fp32 columns: K % 32 == 0: 128-byte blocks [hi(32) | lo(32)], otherwise the planes [hi(K) | lo(K)]; hi = bf16(v) (round to nearest even),
+ * lo = bf16(v - hi), v = lut[c][byte]; columns 3 patch^2 .. K - 1 zero in both halves.  By definition the bytes ffn_vit_patch_rows(FFN_F32, ldo = K) followed by
+ * ffn_split_pair(rows, K, K) writes, without the fp32 rows going through memory.  Refused with FFN_EINVAL before any launch: what ffn_vit_patch_rows refuses,
+ * K < 3 patch^2, K % 8 != 0 (a thread writes 8 columns of each half as one 16-byte store), out not 16-byte aligned. */
 #define FFN_IMGPREP_MAX_SIDE 4096
 int ffn_resize_pil_bilinear_u8(void* stream, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int oh, int ow, const int* hbounds,
                                const int* hcoef, int hksize, const int* vbounds, const int* vcoef, int vksize);
 int ffn_vit_patch_rows(void* stream, int dtype, const uint8_t* src, const float* lut, void* out, int B, int H, int W, int patch, int ldo);
+int ffn_vit_patch_rows_pair(void* stream, const uint8_t* src, const float* lut, void* out, int B, int H, int W, int patch, int K);
 
 /* ---- the general PIL resize of the consistency metrics (Background / Subject Consistency; ABI version 6) -----------------------------------------
  * Reference: evaluation/metrics/VBench/background_consistency.py:18-28 (image * keep mask, then CLIP's transform: PIL BICUBIC resize, centre crop),
