@@ -1359,7 +1359,7 @@ extern "C" int ffn_gn_stats(void* stream, int dtype, const void* x, const float*
     else
         LAUNCH(gn_partial_kernel<bf16>, dim3(nchunk, B), dim3(256), lds, s, (const bf16*)x, partial_ws, HW, C, ppc);
     if (int rc = check_launch("gn_partial")) return rc;      // the next LAUNCH clears the error state: check before it
-    LAUNCH(gn_finalize_kernel, dim3(G, B), dim3(64), 0, s, partial_ws, gamma, beta, scale, shift, HW, C, G, nchunk, eps);
+    LAUNCH(gn_finalize_kernel, dim3(G, B), dim3(64), 0, s, partial_ws, gamma, beta, scale, shift, HW, C, G, nchunk, ppc, eps);
     return check_launch("gn_stats");
 }
 extern "C" int ffn_gn_apply(void* stream, int dtype, const void* x, void* y, const float* scale, const float* shift, int B, int HW,

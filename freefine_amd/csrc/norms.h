@@ -1,7 +1,7 @@
 // GroupNorm / LayerNorm / row-softmax for [B, HW, C] (channel-contiguous) activations, gfx950.
 // HBM-bound kernels: 16-byte vector accesses, fp32 statistics (final group reduction in fp64).
 //
-// GroupNorm(32 groups) is split into (1) per-channel partial sums over pixel chunks, (2) a tiny finalize
+// GroupNorm(32 groups) is split into (1) per-channel partial statistics (mean, M2) over pixel chunks, (2) a tiny finalize
 // that turns them into per-(batch, channel) scale/shift, (3) an elementwise apply with optional SiLU.
 // Replaces torch.nn.GroupNorm + SiLU inside diffusers ResnetBlock2D / Transformer2DModel / conv_norm_out
 // (reached from /root/reference/src/utils/attention.py:105-214).
@@ -21,14 +21,20 @@ __device__ __forceinline__ void store_pair4(bf16* yp, long row, int C, int c, co
     *reinterpret_cast<u32x2*>(q + pair_lo(C)) = lo;
 }
 
-// ---- (1) partial sums: grid (nchunk, B), 256 threads ------------------------------------------------------
-// partial[b][chunk][c][2] = (sum, sumsq) over the chunk's pixels
+// ---- (1) partial statistics: grid (nchunk, B), 256 threads ------------------------------------------------------
+// partial[b][chunk][c][2] = (mean, M2) of channel c over the chunk's pixels, M2 = sum (x - mean)^2.  (sum, sum of squares) in fp32 loses the variance to
+// the cancellation in E[x^2] - mean^2 once |mean| is a few times the standard deviation (tests/test_norms_gpu.py: 3.3e-5 of the output at mean = 16 std,
+// 1.9e-3 at 256 std), so every thread sums x - pivot and (x - pivot)^2 (pivot = its first pixel: within a few std of its mean) and the pieces are merged
+// as (count, mean, M2) in fp64.  The number of pixels of a piece follows from its index, so it is not stored.
+__device__ __forceinline__ int gn_row_count(int p0, int p1, int row, int ppi) {      // pixels p0 + row, p0 + row + ppi, ... below p1
+    return p0 + row < p1 ? (p1 - p0 - row + ppi - 1) / ppi : 0;
+}
 template <typename T>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, float* __restrict__ partial, int HW,
                                                          int C, int pix_per_chunk) {
     constexpr int EPC = DT<T>::EPC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* ls = reinterpret_cast<float*>(smem);  // [ppi][C][2] per-thread-row partials (round 2: no LDS atomics -- 16 contended atomic
+    float* ls = reinterpret_cast<float*>(smem);  // [ppi][C][2] per-thread-row (mean, M2) (round 2: no LDS atomics -- 16 contended atomic
                                                  // adds per thread made this HBM-bound kernel run at 2.7 TB/s)
     const int b = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
     const int cch = C / EPC;                 // 16-byte chunks per pixel
@@ -41,25 +47,32 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
         const int ppi = max(1, 256 / cols);       // pixel rows of threads
         const int cc = cbase + tid % cols, pp = tid / cols;
         const bool active = pp < ppi;
-        float s[EPC], ss[EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) s[e] = ss[e] = 0.f;
         if (active) {
+            float s[EPC], ss[EPC], pv[EPC];
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) s[e] = ss[e] = pv[e] = 0.f;
             // eight pixels in flight per thread: a single dependent load per iteration made this kernel latency bound
             const T* src = x + ((long)b * HW) * C + cc * EPC;
             int px = p0 + pp;
+            const int cnt = gn_row_count(p0, p1, pp, ppi), first = px;      // the pivot is the thread's first pixel, taken from the first batch of loads (a load of its own would add a round trip to memory)
             for (; px + 7 * ppi < p1; px += 8 * ppi) {
                 u32x4 v[8];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const u32x4*>(src + (long)(px + u * ppi) * C);
+                // all eight loads before any arithmetic.  Without this barrier the compiler issues three (bf16) of the loads up front and the other five one at a
+                // time, each behind an s_waitcnt vmcnt(0), between the sums.  tools/bench_kernels.py --only norm, B = 4, GroupNorm + SiLU without -> with it:
+                // bf16 64x64 C=960 38.6 -> 29.9 us, 32x32 C=1920 47.1 -> 28.8 us; fp32 45.0 -> 42.1 and 45.0 -> 38.5 us
+                __builtin_amdgcn_sched_barrier(0);
+                if (px == first) DT<T>::unpack(v[0], pv);
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     float f[EPC];
                     DT<T>::unpack(v[u], f);
 #pragma unroll
                     for (int e = 0; e < EPC; ++e) {
-                        s[e] += f[e];
-                        ss[e] += f[e] * f[e];
+                        const float d = f[e] - pv[e];
+                        s[e] += d;
+                        ss[e] += d * d;
                     }
                 }
             }
@@ -67,24 +80,37 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
                 const u32x4 v = *reinterpret_cast<const u32x4*>(src + (long)px * C);
                 float f[EPC];
                 DT<T>::unpack(v, f);
+                if (px == first) DT<T>::unpack(v, pv);
 #pragma unroll
                 for (int e = 0; e < EPC; ++e) {
-                    s[e] += f[e];
-                    ss[e] += f[e] * f[e];
+                    const float d = f[e] - pv[e];
+                    s[e] += d;
+                    ss[e] += d * d;
                 }
             }
+            const float inv = cnt > 0 ? 1.0f / (float)cnt : 0.f;
 #pragma unroll
             for (int e = 0; e < EPC; ++e) {
-                ls[(pp * cols + (cc - cbase)) * 2 * EPC + 2 * e] = s[e];
-                ls[(pp * cols + (cc - cbase)) * 2 * EPC + 2 * e + 1] = ss[e];
+                const float m = s[e] * inv;                                                // mean of x - pivot
+                ls[(pp * cols + (cc - cbase)) * 2 * EPC + 2 * e] = pv[e] + m;
+                ls[(pp * cols + (cc - cbase)) * 2 * EPC + 2 * e + 1] = fmaxf(ss[e] - s[e] * m, 0.f);
             }
         }
         __syncthreads();
-        // fixed-order sum over the pixel rows of threads (deterministic)
-        for (int i = tid; i < cols * 2 * EPC; i += 256) {
-            float acc = 0.f;
-            for (int r = 0; r < ppi; ++r) acc += ls[r * cols * 2 * EPC + i];
-            dst[cbase * 2 * EPC + i] = acc;      // [c][2] with c = (cbase + column) * EPC + e: same interleaving as ls
+        // fixed-order merge of the pixel rows of threads (deterministic): mean = sum n_r mean_r / n, M2 = sum (M2_r + n_r mean_r^2) - n mean^2 -- in fp64, where
+        // the cancellation costs 2 log2(|mean| / std) of 53 bits
+        const int n = max(p1 - p0, 0);
+        for (int i = tid; i < cols * EPC; i += 256) {
+            double sm = 0.0, sq = 0.0;
+            for (int r = 0; r < ppi; ++r) {
+                const double nr = (double)gn_row_count(p0, p1, r, ppi), mr = (double)ls[(r * cols * EPC + i) * 2];
+                sm += nr * mr;
+                sq += (double)ls[(r * cols * EPC + i) * 2 + 1] + nr * mr * mr;
+            }
+            const double mean = n > 0 ? sm / (double)n : 0.0;
+            const double m2 = fmax(sq - sm * mean, 0.0);
+            dst[(cbase * EPC + i) * 2] = (float)mean;      // [c][2] with c = (cbase + column) * EPC + e: same interleaving as ls
+            dst[(cbase * EPC + i) * 2 + 1] = (float)m2;
         }
         __syncthreads();
     }
@@ -94,31 +120,31 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
 __global__ __launch_bounds__(64) void gn_finalize_kernel(const float* __restrict__ partial, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float* __restrict__ scale,
                                                          float* __restrict__ shift, int HW, int C, int G, int nchunk,
-                                                         float eps) {
+                                                         int pix_per_chunk, float eps) {
     const int g = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
     const int cg = C / G;
-    double s = 0.0, ss = 0.0;
+    const double n = (double)HW * cg;
+    double s = 0.0, sq = 0.0;
     for (int i = lane; i < nchunk * cg; i += 64) {
         const int ch = i / cg, c = g * cg + (i - ch * cg);
+        const double ni = (double)max(min(HW, (ch + 1) * pix_per_chunk) - ch * pix_per_chunk, 0);      // pixels of chunk ch
         const float* src = partial + (((long)b * nchunk + ch) * C + c) * 2;
-        s += (double)src[0];
-        ss += (double)src[1];
+        const double mi = (double)src[0];
+        s += ni * mi;
+        sq += (double)src[1] + ni * mi * mi;
     }
     for (int off = 32; off > 0; off >>= 1) {
         s += __shfl_xor(s, off);
-        ss += __shfl_xor(ss, off);
+        sq += __shfl_xor(sq, off);
     }
-    const double n = (double)HW * cg;
     const double mean = s / n;
-    double var = ss / n - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float fmean = (float)mean;
+    const double m2 = fmax(sq - s * mean, 0.0);      // M2 of the slice; fp64: the cancellation costs 2 log2(|mean| / std) of 53 bits
+    const float rstd = (float)(1.0 / sqrt(m2 / n + (double)eps));
     for (int i = lane; i < cg; i += 64) {
         const int c = g * cg + i;
         const float sc = rstd * gamma[c];
         scale[(long)b * C + c] = sc;
-        shift[(long)b * C + c] = beta[c] - fmean * sc;
+        shift[(long)b * C + c] = (float)((double)beta[c] - mean * (double)sc);      // one rounding: mean * sc is what x * sc cancels against in the apply pass
     }
 }
 
@@ -235,26 +261,34 @@ __global__ __launch_bounds__(256) void gn_apply_f8_kernel(const bf16* __restrict
 }
 
 // ---- fused GroupNorm for slices that one workgroup can own: grid (G, B), 1024 threads ----------------------------------
-// pass 1: sum / sumsq over the (batch, group) slice [HW][cg] (element pairs, 4 or 8 bytes per load; the slice is L2 resident),
+// pass 1: sum / sumsq of x - pivot over the (batch, group) slice [HW][cg] (element pairs, 4 or 8 bytes per load; the slice is L2 resident),
 // block reduction (fp32 per thread, fp64 across threads), pass 2: y = act((x - mean) * rstd * gamma + beta).
 template <typename T, bool SILU, bool PAIR = false>
 __global__ __launch_bounds__(1024) void gn_fused_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, int HW, int C, int G, float eps) {
     __shared__ double red[2][16];
-    __shared__ float stat[2];
+    __shared__ float stat[3];
     const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cg = C / G, hp = cg / 2;                      // channel pairs per pixel in this group
     const long base = (long)b * HW * C + (long)g * cg;
     const int npair = HW * hp;
-    float s = 0.f, ss = 0.f;
+    // sums of x - pivot (pivot = the thread's first element), moved to the slice's first element P in fp64: E[x^2] - mean^2 of the raw values loses
+    // 2 log2(|mean| / std) bits of fp32 sums to cancellation (1.2e-5 of the output at mean = 16 std on a 50 x 2 slice)
+    const float P = DT<T>::ld(x + base);
+    float s = 0.f, ss = 0.f, pv = 0.f;
+    int cnt = 0;
     for (int i = tid; i < npair; i += 1024) {
         const int px = i / hp, c2 = i - px * hp;
         const T* src = x + base + (long)px * C + 2 * c2;
         const float a = DT<T>::ld(src), c = DT<T>::ld(src + 1);
-        s += a + c;
-        ss += a * a + c * c;
+        if (i == tid) pv = a;
+        const float da = a - pv, dc = c - pv;
+        s += da + dc;
+        ss += da * da + dc * dc;
+        cnt += 2;
     }
-    double ds = s, dss = ss;
+    const double dl = (double)pv - (double)P;
+    double ds = (double)s + cnt * dl, dss = (double)ss + 2.0 * dl * (double)s + cnt * dl * dl;      // sums of x - P and (x - P)^2 (cnt = 0: both 0)
     for (int off = 32; off > 0; off >>= 1) {
         ds += __shfl_xor(ds, off);
         dss += __shfl_xor(dss, off);
@@ -270,21 +304,22 @@ __global__ __launch_bounds__(1024) void gn_fused_kernel(const T* __restrict__ x,
             t += red[0][w];
             tt += red[1][w];
         }
-        const double n = (double)HW * cg, mean = t / n;
-        double var = tt / n - mean * mean;
+        const double n = (double)HW * cg, rel = t / n, mean = (double)P + rel;
+        double var = tt / n - rel * rel;
         if (var < 0) var = 0;
         stat[0] = (float)mean;
         stat[1] = (float)(1.0 / sqrt(var + (double)eps));
+        stat[2] = (float)(mean - (double)stat[0]);           // the mean as hi + lo: rounded to one float it is off by up to 2^-24 |mean|, |mean| / std times the fp32 ulp of the result
     }
     __syncthreads();
-    const float mean = stat[0], rstd = stat[1];
+    const float mean = stat[0], rstd = stat[1], mean_lo = stat[2];
     for (int i = tid; i < npair; i += 1024) {
         const int px = i / hp, c2 = i - px * hp;
         const int c = g * cg + 2 * c2;
         const long off = base + (long)px * C + 2 * c2;
         const float sc0 = rstd * gamma[c], sc1 = rstd * gamma[c + 1];
-        float a = DT<T>::ld(x + off) * sc0 + (beta[c] - mean * sc0);
-        float d = DT<T>::ld(x + off + 1) * sc1 + (beta[c + 1] - mean * sc1);
+        float a = ((DT<T>::ld(x + off) - mean) - mean_lo) * sc0 + beta[c];           // the mean first: x * sc0 and mean * sc0 would each be rounded at |mean| / std times the result
+        float d = ((DT<T>::ld(x + off + 1) - mean) - mean_lo) * sc1 + beta[c + 1];
         if (SILU) {
             a = silu_for<T>(a);
             d = silu_for<T>(d);
