@@ -120,6 +120,7 @@ __global__ __launch_bounds__(256) void splat_render_kernel(const float* __restri
         if ((int)threadIdx.x < m) {
             const int p = list[base + threadIdx.x];
             f32x4 a = *reinterpret_cast<const f32x4*>(proj + 4l * p);
+            if (!(a[2] >= 0.f)) a[0] = __builtin_nanf("");       // behind the camera (or z NaN): d2 < r2 fails for every pixel, whoever built the list
             a[3] = __int_as_float(p);
             s_pt[threadIdx.x] = a;
         }
