@@ -2,7 +2,8 @@
 (/root/reference/depth_anything/dpt.py:143-172 DPT_DINOv2.forward, :22-137 DPTHead, blocks.py:38-153,
 torchhub/facebookresearch_dinov2_main/vision_transformer.py:178-317).
 
-The encoder half (weights, tokens, blocks) is dino.py's HipDinoEncoder, shared with the metrics' feature extractor HipDinoV2; this module adds the DPT head.
+The encoder half (weights, tokens, blocks) is dino.py's HipDinoEncoder, shared with the metrics' feature extractor HipDinoV2, and its blocks are encoder.py's; this
+module adds the DPT head.
 
 Same design as unet.py / vae.py: activations are token / NHWC rows, every Linear, 1x1 conv, 3x3 conv, patch embedding and
 transposed conv is an `ffn_igemm` call, LayerNorm and attention are the UNet's kernels (`ffn_layernorm`, `ffn_attn` with head
@@ -15,19 +16,19 @@ shuffle, the one-off bicubic interpolation of the positional embedding per input
 
 dtype float32 = parity mode (exact-fp32 MFMA), bfloat16 = fast mode.
 """
-import math
 from types import SimpleNamespace
 
 import torch
 
 from . import ops
-from .dino import HipDinoEncoder, _O, dinov2_param_shapes
+from . import encoder
+from .dino import _ENC, HipDinoEncoder, dinov2_param_shapes
 
 
 def depth_config(name="vitl"):
     """encoder = dinov2_{vits,vitb,vitl}14 (hubconf.py: img_size 518, patch 14, LayerScale, mlp ffn, interpolate_offset 0.1); DPT head sizes of
     the released Depth-Anything checkpoints (dpt.py:144: the vitl head)"""
-    enc = dict(vits=(384, 12, 6), vitb=(768, 12, 12), vitl=(1024, 24, 16), tiny=(128, 4, 2), mini=(192, 5, 3))[name]
+    enc = _ENC[name]
     head = dict(vits=(64, (48, 96, 192, 384)), vitb=(128, (96, 192, 384, 768)), vitl=(256, (256, 512, 1024, 1024)),
                 tiny=(32, (16, 32, 64, 64)), mini=(48, (24, 48, 96, 96)))[name]
     return SimpleNamespace(name=name, embed_dim=enc[0], depth=enc[1], num_heads=enc[2], patch=14, img_size=518, mlp_ratio=4,
@@ -60,22 +61,7 @@ def depth_param_shapes(cfg):
 
 def synthetic_state(cfg, seed=0):
     """seeded random weights of a plausible scale for benchmarks without a checkpoint (`tools/bench_depth.py`; there is no network)"""
-    g = torch.Generator().manual_seed(seed)
-    st = {}
-    for k, shp in depth_param_shapes(cfg).items():
-        if k.endswith("norm.weight") or k.endswith("norm1.weight") or k.endswith("norm2.weight"):
-            t = 1.0 + 0.1 * torch.randn(shp, generator=g)
-        elif k.endswith(".gamma"):
-            t = 0.5 + 0.25 * torch.rand(shp, generator=g)
-        elif k.endswith(".bias"):
-            t = 0.05 * torch.randn(shp, generator=g)
-        elif k.endswith("pos_embed") or k.endswith("cls_token") or k.endswith("mask_token"):
-            t = 0.2 * torch.randn(shp, generator=g)
-        else:
-            fan_in = shp[0] if ("resize_layers.0" in k or "resize_layers.1" in k) else math.prod(shp[1:])
-            t = torch.randn(shp, generator=g) / math.sqrt(fan_in)
-        st[k] = t.float()
-    return st
+    return encoder.draw_state(depth_param_shapes(cfg), seed, fan_in_first=("resize_layers.0", "resize_layers.1"))
 
 
 class HipDepthAnything(HipDinoEncoder):
@@ -89,6 +75,14 @@ class HipDepthAnything(HipDinoEncoder):
     # ------------------------------------------------------------------------------------------------------------
     # weights (the encoder's: dino.py HipDinoEncoder._pack_encoder)
     # ------------------------------------------------------------------------------------------------------------
+    def _lin(self, w, b, n_pad=None):
+        """a 1x1 convolution / Linear of the head as a GEMM: [N, K(, 1, 1)] -> (packed weight, fp32 bias), N zero-padded to n_pad rows"""
+        w = w.reshape(w.shape[0], -1)
+        if n_pad and n_pad > w.shape[0]:
+            w = torch.cat([w, torch.zeros(n_pad - w.shape[0], w.shape[1], device=w.device)], 0)
+            b = torch.cat([b, torch.zeros(n_pad - b.shape[0], device=b.device)], 0)
+        return ops.pack_linear(w.contiguous(), self.dtype), b.float().contiguous()
+
     def _conv(self, st, name, bias=True):
         w = st[name + ".weight"]
         return ops.pack_conv3x3(w, self.dtype), (st[name + ".bias"].contiguous() if bias else None), w.shape[1]
@@ -111,7 +105,7 @@ class HipDepthAnything(HipDinoEncoder):
         self.rn = [self._conv(st, h + f"scratch.layer{i + 1}_rn", bias=False) for i in range(4)]
         self.refine = []
         for i in range(1, 5):
-            r, q = _O(), h + f"scratch.refinenet{i}."
+            r, q = SimpleNamespace(), h + f"scratch.refinenet{i}."
             r.u1 = (self._conv(st, q + "resConfUnit1.conv1"), self._conv(st, q + "resConfUnit1.conv2"))
             r.u2 = (self._conv(st, q + "resConfUnit2.conv1"), self._conv(st, q + "resConfUnit2.conv2"))
             r.out = self._lin(st[q + "out_conv.weight"], st[q + "out_conv.bias"])

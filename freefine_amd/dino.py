@@ -18,9 +18,8 @@ run_g15), and the claim that this equals dino_vitb16 rests on the two published 
 dtype float32 = parity mode (exact-fp32 MFMA), float32 with x3=True = split-bf16 (below), bfloat16 = fast mode.  No graph capture, no class-token-only last block.
 
 Split-bf16 (`HipDinoV2(..., x3=True)`, `HipDino` likewise; the depth network passes no x3 and stays as it is): every GEMM and the attention run FFN_BF16X3 --
-operands as hi + lo bf16 pairs, three bf16 MFMAs per product term, fp32 accumulation -- built like text.HipCLIPTextEncoder: weights packed with
-ops.pack_linear(x3=True) (LayerScale folded BEFORE the split), LayerNorms write the pair rows their GEMMs read (`ffn_layernorm_pair`), attention and fc1 write
-pair rows for the GEMM behind them; the residual stream, the positional embedding, the class row and V^T stay fp32.  The patch embedding's contraction length is
+operands as hi + lo bf16 pairs, three bf16 MFMAs per product term, fp32 accumulation -- in the blocks as encoder.py describes it (LayerScale is folded
+BEFORE the split); the positional embedding and the class row stay fp32 like the residual stream.  The patch embedding's contraction length is
 rounded up to a multiple of 32 (608 at patch 14) so that both operands are in the blocked pair form; `features_u8` gets its rows from
 `ffn_vit_patch_rows_pair` (pair rows straight from the bytes), `forward` from fp32 rows that ops.linear splits -- the same operand bytes."""
 import math
@@ -29,7 +28,7 @@ from types import SimpleNamespace
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import encoder, ops
 
 _ENC = dict(vits=(384, 12, 6), vitb=(768, 12, 12), vitl=(1024, 24, 16), tiny=(128, 4, 2), mini=(192, 5, 3))
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # fid_score.py:122-123
@@ -75,51 +74,18 @@ param_shapes = dinov2_param_shapes
 
 def synthetic_state(cfg, seed=0):
     """seeded random weights of a plausible scale in hub layout, for benchmarks without a checkpoint (`tools/bench_dino.py`; there is no network)"""
-    g = torch.Generator().manual_seed(seed)
-    st = {}
-    for k, shp in dinov2_param_shapes(cfg).items():
-        if k.endswith("norm.weight") or k.endswith("norm1.weight") or k.endswith("norm2.weight"):
-            t = 1.0 + 0.1 * torch.randn(shp, generator=g)
-        elif k.endswith(".gamma"):
-            t = 0.5 + 0.25 * torch.rand(shp, generator=g)
-        elif k.endswith(".bias"):
-            t = 0.05 * torch.randn(shp, generator=g)
-        elif k.endswith("pos_embed") or k.endswith("cls_token") or k.endswith("mask_token"):
-            t = 0.2 * torch.randn(shp, generator=g)
-        else:
-            t = torch.randn(shp, generator=g) / math.sqrt(math.prod(shp[1:]))
-        st[k] = t.float()
-    return st
-
-
-class _O:
-    pass
+    return encoder.draw_state(dinov2_param_shapes(cfg), seed)
 
 
 class HipDinoEncoder:
     """The DINOv2 ViT encoder: weights packed from `<prefix>*` of a state dict, tokens, blocks.  Subclasses add what they read off the tokens."""
 
     def _init_encoder(self, cfg, dtype, device, x3=False):
-        assert dtype in (torch.float32, torch.bfloat16)
-        if x3 and dtype != torch.float32:
-            raise ValueError(f"x3=True (split-bf16) takes dtype=torch.float32: operands are split from fp32 values (dtype={dtype})")
+        encoder.check_mode(dtype, x3)
         self.cfg, self.dtype, self.device, self.x3 = cfg, dtype, torch.device(device), bool(x3)
         C = cfg.embed_dim
         assert C % cfg.num_heads == 0 and C % 8 == 0, "channel counts must be whole 16-byte chunks"
         self._pos = {}
-
-    # ------------------------------------------------------------------------------------------------------------
-    # weights
-    # ------------------------------------------------------------------------------------------------------------
-    def _lin(self, w, b=None, scale=None, n_pad=None):
-        w = w.reshape(w.shape[0], -1)
-        if scale is not None:                                 # LayerScale folded: gamma * (W x + b)
-            w = w * scale[:, None]
-            b = None if b is None else b * scale
-        if n_pad and n_pad > w.shape[0]:
-            w = torch.cat([w, torch.zeros(n_pad - w.shape[0], w.shape[1], device=w.device)], 0)
-            b = None if b is None else torch.cat([b, torch.zeros(n_pad - b.shape[0], device=b.device)], 0)
-        return ops.pack_linear(w.contiguous(), self.dtype, x3=self.x3), (None if b is None else b.float().contiguous()), w.shape[1]
 
     def _pack_encoder(self, st, p):
         """st: fp32 tensors on the device; p: the prefix of the ViT's parameters (`pretrained.` inside DPT_DINOv2, empty in hub layout)"""
@@ -134,16 +100,15 @@ class HipDinoEncoder:
         self.pos_embed, self.cls_token = st[p + "pos_embed"], st[p + "cls_token"]
         self.blocks = []
         for i in range(cfg.depth):
-            b, q = _O(), f"{p}blocks.{i}."
-            b.n1 = (st[q + "norm1.weight"].contiguous(), st[q + "norm1.bias"].contiguous())
-            b.n2 = (st[q + "norm2.weight"].contiguous(), st[q + "norm2.bias"].contiguous())
-            wqkv, bqkv = st[q + "attn.qkv.weight"], st[q + "attn.qkv.bias"]
-            b.qk = self._lin(wqkv[:2 * C], bqkv[:2 * C])        # q | k in one GEMM, V^T from its own (transposed-output) GEMM
-            b.v = self._lin(wqkv[2 * C:], bqkv[2 * C:])
-            b.proj = self._lin(st[q + "attn.proj.weight"], st[q + "attn.proj.bias"], scale=st.get(q + "ls1.gamma"))      # no ls*.gamma: no LayerScale
-            b.fc1 = self._lin(st[q + "mlp.fc1.weight"], st[q + "mlp.fc1.bias"])
-            b.fc2 = self._lin(st[q + "mlp.fc2.weight"], st[q + "mlp.fc2.bias"], scale=st.get(q + "ls2.gamma"))
-            self.blocks.append(b)
+            q = f"{p}blocks.{i}."
+
+            def wb(n, gamma=None):                            # LayerScale folded: gamma * (W x + b); no ls*.gamma: no LayerScale
+                w, b = st[q + n + ".weight"], st[q + n + ".bias"]
+                return (w, b) if gamma is None else (w * gamma[:, None], b * gamma)
+            wqkv, bqkv = wb("attn.qkv")                       # q | k in one GEMM, V^T from its own (transposed-output) GEMM
+            self.blocks.append(encoder.pack_block(wb("norm1"), wb("norm2"), (wqkv[:2 * C], bqkv[:2 * C]), (wqkv[2 * C:], bqkv[2 * C:]),
+                                                  wb("attn.proj", st.get(q + "ls1.gamma")), wb("mlp.fc1"), wb("mlp.fc2", st.get(q + "ls2.gamma")),
+                                                  self.dtype, self.x3))
         self.norm = (st[p + "norm.weight"].contiguous(), st[p + "norm.bias"].contiguous())
 
     # ------------------------------------------------------------------------------------------------------------
@@ -173,13 +138,7 @@ class HipDinoEncoder:
         hit = self._pos[key] = (cls_row, patch_pos[0].to(self.dtype).contiguous())
         return hit
 
-    @staticmethod
-    def _im2col(x, ps):
-        """[B, 3, H, W] -> [B * (H/ps) * (W/ps), 3 * ps * ps]: one row per patch (row-major over the patch grid), columns ordered (channel, ky, kx)
-        like patch_embed.proj.weight.reshape(C, -1) (patch_embed.py:75: Conv2d(kernel = stride = patch))"""
-        B, Cc, H, W = x.shape
-        ph, pw = H // ps, W // ps
-        return x.reshape(B, Cc, ph, ps, pw, ps).permute(0, 2, 4, 1, 3, 5).reshape(B * ph * pw, Cc * ps * ps)
+    _im2col = staticmethod(encoder.im2col)
 
     def _patch_rows(self, x):
         """float image [B, 3, H, W] -> the patch-embedding GEMM's operand rows [B * ph * pw, kpe] in the activation dtype (columns >= 3 * 14 * 14 zero)"""
@@ -191,39 +150,24 @@ class HipDinoEncoder:
         return a
 
     def _embed(self, a, B, H, W):
-        """patch embedding of given operand rows (a GEMM, positional embedding added as the GEMM's residual) + class row -> ([B, 1 + ph * pw, C], ph, pw).
-        Split-bf16: a = pair rows (ops.vit_patch_rows_pair) or fp32 rows, which ops.linear splits."""
-        ps = self.cfg.patch
-        ph, pw = H // ps, W // ps
+        """patch embedding of given operand rows + class row -> ([B, 1 + ph * pw, C], ph, pw).  Split-bf16: a = pair rows (ops.vit_patch_rows_pair) or fp32
+        rows, which ops.linear splits."""
         cls_row, pos = self._pos_tokens(H, W)
-        res = pos.unsqueeze(0).expand(B, -1, -1).reshape(B * ph * pw, -1).contiguous()
-        t = ops.linear(a, self.pe[0], self.pe[1], K=self.kpe, residual=res)
-        return torch.cat([cls_row.unsqueeze(0).expand(B, -1, -1), t.view(B, ph * pw, -1)], dim=1).contiguous(), ph, pw
+        return encoder.embed_patches(a, self.pe[0], self.pe[1], self.kpe, pos, cls_row, B), H // self.cfg.patch, W // self.cfg.patch
 
     def _tokens(self, x):
         """patch rows from a float image, embedded"""
         B, _, H, W = x.shape
         return self._embed(self._patch_rows(x), B, H, W)
 
-    def _block(self, b, t, B, S):
-        cfg, x3 = self.cfg, self.x3                  # split-bf16: the norms, the attention and fc1 write the pair rows the GEMM behind them reads
-        C, nh = cfg.embed_dim, cfg.num_heads
-        y = ops.layernorm(t, *b.n1, eps=cfg.ln_eps, pair=x3)
-        qk = ops.linear(y, b.qk[0], b.qk[1], K=C)                                   # [B, S, 2C]: q | k
-        vt = ops.linear(y, b.v[0], b.v[1], K=C, rows_per_batch=S, transposed_ld=(S + 7) // 8 * 8)      # V^T [B, C, S']
-        a = ops.attention(qk, qk[..., C:], vt, nh, (C // nh) ** -0.5, None, Sk=S, C=C, x3=x3, out_pair=x3)
-        t = ops.linear(a, b.proj[0], b.proj[1], K=C, residual=t)                     # x + ls1 * proj(attn)
-        y = ops.layernorm(t, *b.n2, eps=cfg.ln_eps, pair=x3)
-        y = ops.linear(y, b.fc1[0], b.fc1[1], K=C, gelu=True, out_pair=x3)
-        return ops.linear(y, b.fc2[0], b.fc2[1], K=C * cfg.mlp_ratio, residual=t)    # x + ls2 * fc2(gelu(fc1))
-
     def _run_blocks(self, t, keep_last=1):
         """all blocks over tokens [B, S, C] -> the outputs of the last `keep_last` blocks (before the final LayerNorm)"""
-        B, S, _ = t.shape
+        cfg = self.cfg
+        vt = encoder.vt_buffer(t)
         outs = []
         for i, b in enumerate(self.blocks):
-            t = self._block(b, t, B, S)
-            if i >= self.cfg.depth - keep_last:
+            t = encoder.run_block(b, t, vt, heads=cfg.num_heads, eps=cfg.ln_eps, act="gelu", hidden=cfg.embed_dim * cfg.mlp_ratio, x3=self.x3)
+            if i >= cfg.depth - keep_last:
                 outs.append(t)
         return outs
 
@@ -238,11 +182,11 @@ class HipDinoV2(HipDinoEncoder):
         self._pack_encoder({k: v.detach().to(self.device, torch.float32) for k, v in state.items()}, "")
         self._lut = ops.vit_norm_table(IMAGENET_MEAN, IMAGENET_STD).to(self.device)
 
-    def _rows_u8(self, small):
-        """resized uint8 images -> the patch GEMM's operand rows: the activation dtype's, or the pair rows of split-bf16"""
-        if self.x3:
-            return ops.vit_patch_rows_pair(small, self._lut, self.cfg.patch, self.kpe)
-        return ops.vit_patch_rows(small, self._lut, self.cfg.patch, self.kpe, self.dtype)
+    def _cls_u8(self, small):
+        """resized uint8 images [B, H, W, 3] -> patch rows -> tokens -> _cls"""
+        B, H, W, _ = small.shape
+        a = encoder.patch_rows_u8(small, self._lut, self.cfg.patch, self.kpe, self.dtype, self.x3)
+        return self._cls(self._embed(a, B, H, W)[0])
 
     def _cls(self, t):
         """tokens -> blocks -> final LayerNorm on the class rows only (fp32 in split-bf16 mode too) -> fp32 [B, C]"""
@@ -261,12 +205,9 @@ class HipDinoV2(HipDinoEncoder):
     def features_u8(self, images, size=224):
         """images uint8 [B, H, W, 3] of ONE size (numpy or torch, host or device) -> fp32 [B, C]: the transform of fid_score.py:124 -- Resize((size, size)) of the
         PIL image, ToTensor, Normalize(imagenet) -- and the network, all on the device: resize -> patch rows -> encoder."""
-        img = torch.as_tensor(images)
-        assert img.dtype == torch.uint8 and img.ndim == 4 and img.shape[-1] == 3 and size % self.cfg.patch == 0
-        img = img.to(self.device).contiguous()
-        small = ops.resize_pil_bilinear_u8(img, size, size)
-        a = self._rows_u8(small)
-        return self._cls(self._embed(a, img.shape[0], size, size)[0])
+        img, _ = encoder.u8_batch(images, None, self.device)
+        assert size % self.cfg.patch == 0
+        return self._cls_u8(ops.resize_pil_bilinear_u8(img, size, size))
 
 
 class HipDino(HipDinoV2):
@@ -279,14 +220,8 @@ class HipDino(HipDinoV2):
     def features_u8(self, images, keep=None, size=224):
         """images uint8 [B, H, W, 3] of ONE size (numpy or torch, host or device); keep = None or (rule, m1, m2) as in ops.resize_pil_u8 (uint8 [B, H, W], host or
         device) -> fp32 [B, C]"""
-        img = torch.as_tensor(images)
-        assert img.dtype == torch.uint8 and img.ndim == 4 and img.shape[-1] == 3
-        img = img.to(self.device).contiguous()
-        if keep is not None:
-            keep = (keep[0],) + tuple(None if m is None else torch.as_tensor(m).to(self.device).contiguous() for m in keep[1:])
+        img, keep = encoder.u8_batch(images, keep, self.device)
         ps = self.cfg.patch
         oh, ow = ops.torchvision_resize_size(img.shape[1], img.shape[2], size)
         H, W = oh // ps * ps, ow // ps * ps
-        small = ops.resize_pil_u8(img, oh, ow, "bilinear", crop=(0, 0, H, W), keep=keep)
-        a = self._rows_u8(small)
-        return self._cls(self._embed(a, img.shape[0], H, W)[0])
+        return self._cls_u8(ops.resize_pil_u8(img, oh, ow, "bilinear", crop=(0, 0, H, W), keep=keep))

@@ -5,12 +5,15 @@ No CLIP weights exist in this environment, so synthetic runs use a deterministic
 interface pair (tokenizer(prompts, padding=..., max_length=77, return_tensors="pt").input_ids ; text_encoder(ids)[0]
 -> [N,77,D]).  A real HF tokenizer/text-encoder pair can be plugged into FreeFinePipeline unchanged.
 
-HipCLIPTextEncoder (below) is the same interface on the project's own kernels: transformers' CLIPTextModel arithmetic without a library GEMM.
+HipCLIPTextEncoder (below) is the same interface on the project's own kernels: transformers' CLIPTextModel arithmetic without a library GEMM; its layers are
+encoder.py's block.
 """
 from types import SimpleNamespace
 
 import numpy as np
 import torch
+
+from . import encoder, ops
 
 
 class ByteTokenizer:
@@ -106,35 +109,20 @@ def text_config(config):
 
 def pack_text_state(cfg, state):
     """CLIPTextModel parameters (names with or without the hub files' `text_model.` prefix; `text_projection` and `position_ids` ignored) -> the fp32 host tensors
-    the tower uploads, in the packing of depth.py: q | k rows of one GEMM, V apart (its GEMM writes V^T).  Missing or mis-shaped parameters raise ValueError."""
+    the tower uploads, the layers in the packing of encoder.py: q | k rows of one GEMM, V apart (its GEMM writes V^T).  Missing or mis-shaped parameters raise
+    ValueError."""
     st = {(k[len("text_model."):] if k.startswith("text_model.") else k): v for k, v in state.items()}
-    C, I = cfg.hidden_size, cfg.intermediate_size
+    C = cfg.hidden_size
     want = {"embeddings.token_embedding.weight": (cfg.vocab_size, C), "embeddings.position_embedding.weight": (cfg.max_position_embeddings, C),
             "final_layer_norm.weight": (C,), "final_layer_norm.bias": (C,)}
-    for i in range(cfg.num_hidden_layers):
-        p = f"encoder.layers.{i}."
-        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-            want[p + f"self_attn.{n}.weight"], want[p + f"self_attn.{n}.bias"] = (C, C), (C,)
-        for n in ("layer_norm1", "layer_norm2"):
-            want[p + n + ".weight"], want[p + n + ".bias"] = (C,), (C,)
-        want[p + "mlp.fc1.weight"], want[p + "mlp.fc1.bias"], want[p + "mlp.fc2.weight"], want[p + "mlp.fc2.bias"] = (I, C), (I,), (C, I), (C,)
+    want.update(encoder.clip_layer_shapes(cfg))
     bad = [k for k, s in want.items() if k not in st or tuple(st[k].shape) != s]
     if bad:
         raise ValueError(f"text encoder state: missing or mis-shaped parameters {bad[:4]}{' ...' if len(bad) > 4 else ''}")
     f = lambda k: st[k].detach().float().cpu().contiguous()
     out = {"tok": f("embeddings.token_embedding.weight"), "pos": f("embeddings.position_embedding.weight"),
            "lnf.w": f("final_layer_norm.weight"), "lnf.b": f("final_layer_norm.bias")}
-    for i in range(cfg.num_hidden_layers):
-        p, a = f"encoder.layers.{i}.", f"encoder.layers.{i}.self_attn."
-        out[f"{i}.ln1.w"], out[f"{i}.ln1.b"] = f(p + "layer_norm1.weight"), f(p + "layer_norm1.bias")
-        out[f"{i}.ln2.w"], out[f"{i}.ln2.b"] = f(p + "layer_norm2.weight"), f(p + "layer_norm2.bias")
-        out[f"{i}.qk.w"] = torch.cat([f(a + "q_proj.weight"), f(a + "k_proj.weight")], 0).contiguous()
-        out[f"{i}.qk.b"] = torch.cat([f(a + "q_proj.bias"), f(a + "k_proj.bias")], 0).contiguous()
-        out[f"{i}.v.w"], out[f"{i}.v.b"] = f(a + "v_proj.weight"), f(a + "v_proj.bias")
-        out[f"{i}.o.w"], out[f"{i}.o.b"] = f(a + "out_proj.weight"), f(a + "out_proj.bias")
-        out[f"{i}.fc1.w"], out[f"{i}.fc1.b"] = f(p + "mlp.fc1.weight"), f(p + "mlp.fc1.bias")
-        out[f"{i}.fc2.w"], out[f"{i}.fc2.b"] = f(p + "mlp.fc2.weight"), f(p + "mlp.fc2.bias")
-    return out
+    return encoder.pack_clip_layers(cfg, f, out)
 
 
 class NativeTextSpec:
@@ -151,9 +139,9 @@ class NativeTextSpec:
 
 
 class HipCLIPTextEncoder:
-    """transformers' CLIPTextModel (`self.text_encoder(ids)[0]`, /root/reference/src/demo/model.py:536-567, 842-848) on the HIP kernels, the way depth.py runs its
-    ViT: every Linear an `ffn_igemm` (q | k in one GEMM, V^T from a transposed-output GEMM, residuals and the MLP activation in the epilogues), LayerNorm
-    `ffn_layernorm`, the causal self attention `ffn_attn` with FFN_ATT_CAUSAL, the token + position lookup `ffn_embed_tokens`.
+    """transformers' CLIPTextModel (`self.text_encoder(ids)[0]`, /root/reference/src/demo/model.py:536-567, 842-848) on the HIP kernels: the layers are
+    encoder.py's block (every Linear an `ffn_igemm`: q | k in one GEMM, V^T from a transposed-output GEMM, residuals and the MLP activation in the epilogues;
+    LayerNorm `ffn_layernorm`) with the causal self attention (`ffn_attn` with FFN_ATT_CAUSAL), the token + position lookup is `ffn_embed_tokens`.
 
         x = tok[ids] + pos;  per layer: y = LN1(x); q, k, v = Linear(y); a = softmax(q k^T / 8 + causal) v per head; x += out_proj(a);
         y = LN2(x); x += fc2(act(fc1(y)));  result final_layer_norm(x)                         (no padding mask: the reference passes none)
@@ -166,19 +154,13 @@ class HipCLIPTextEncoder:
     GROUP = 4
 
     def __init__(self, config, state, dtype=torch.float32, device="cuda:0", x3=False):
-        from . import ops
-        assert dtype in (torch.float32, torch.bfloat16) and not (x3 and dtype != torch.float32)
+        encoder.check_mode(dtype, x3)
         self.config = config if isinstance(config, SimpleNamespace) else text_config(config)
         self.dtype, self.device, self.x3 = dtype, torch.device(device), bool(x3)
         self.host = pack_text_state(self.config, state)
-        cfg, dev = self.config, self.device
-        up = lambda k: self.host[k].to(dev)
-        lin = lambda k: (ops.pack_linear(up(k + ".w"), dtype, x3=self.x3), up(k + ".b"))
+        up = lambda k: self.host[k].to(self.device)
         self.tok, self.pos, self.lnf = up("tok"), up("pos"), (up("lnf.w"), up("lnf.b"))
-        self.blocks = []
-        for i in range(cfg.num_hidden_layers):
-            self.blocks.append(SimpleNamespace(ln1=(up(f"{i}.ln1.w"), up(f"{i}.ln1.b")), ln2=(up(f"{i}.ln2.w"), up(f"{i}.ln2.b")), qk=lin(f"{i}.qk"), v=lin(f"{i}.v"),
-                                               o=lin(f"{i}.o"), fc1=lin(f"{i}.fc1"), fc2=lin(f"{i}.fc2")))
+        self.blocks = encoder.clip_blocks(self.config, self.host, self.device, dtype, self.x3)
 
     @classmethod
     def from_torch(cls, module, dtype=torch.float32, device="cuda:0", x3=False):
@@ -195,24 +177,12 @@ class HipCLIPTextEncoder:
 
     def _group(self, ids):
         """ids int32 [GROUP, S] on the device -> final_layer_norm output [GROUP, S, C] in the activation type"""
-        from . import ops
-        cfg, x3 = self.config, self.x3
-        C, nh, eps = cfg.hidden_size, cfg.num_attention_heads, cfg.layer_norm_eps
-        S = ids.shape[1]
-        quick = cfg.hidden_act == "quick_gelu"
+        cfg = self.config
+        eps, act = cfg.layer_norm_eps, {"quick_gelu": "qgelu", "gelu": "gelu"}[cfg.hidden_act]
         x = ops.embed_tokens(ids, self.tok, self.pos, self.dtype)
-        ld = (S + 7) // 8 * 8
-        # V^T [P, C, S'] of every layer goes through one buffer: its padding columns (S' > S) are zeroed once and no GEMM writes them
-        vt = torch.zeros(ids.shape[0], C, ld, dtype=self.dtype, device=self.device)
+        vt = encoder.vt_buffer(x)
         for b in self.blocks:
-            y = ops.layernorm(x, *b.ln1, eps=eps, pair=x3)
-            qk = ops.linear(y, b.qk[0], b.qk[1], K=C, splitk=1)                                               # [P, S, 2C]: q | k
-            ops.linear(y, b.v[0], b.v[1], K=C, rows_per_batch=S, transposed_ld=ld, splitk=1, out=vt)
-            a = ops.attention(qk, qk[..., C:], vt, nh, 0.125, None, Sk=S, C=C, x3=x3, out_pair=x3, causal=True)
-            x = ops.linear(a, b.o[0], b.o[1], K=C, residual=x, splitk=1)
-            y = ops.layernorm(x, *b.ln2, eps=eps, pair=x3)
-            h = ops.linear(y, b.fc1[0], b.fc1[1], K=C, gelu=not quick, qgelu=quick, out_pair=x3, splitk=1)
-            x = ops.linear(h, b.fc2[0], b.fc2[1], K=cfg.intermediate_size, residual=x, splitk=1)
+            x = encoder.run_block(b, x, vt, heads=cfg.num_attention_heads, eps=eps, act=act, hidden=cfg.intermediate_size, x3=self.x3, causal=True, splitk=1)
         return ops.layernorm(x, *self.lnf, eps=eps)
 
     @torch.no_grad()

@@ -39,7 +39,7 @@ def test_layerscale_is_folded_into_the_projection_rows():
     C = ocfg.embed_dim
     y = torch.randn(5, C, generator=torch.Generator().manual_seed(1))
     b = net.blocks[1]
-    got = y @ b.proj[0][:, :C].t() + b.proj[1]
+    got = y @ b.o[0][:, :C].t() + b.o[1]
     ref = st["pretrained.blocks.1.ls1.gamma"] * F.linear(y, st["pretrained.blocks.1.attn.proj.weight"], st["pretrained.blocks.1.attn.proj.bias"])
     assert (got - ref).abs().max() < 1e-5
     h = torch.randn(5, 4 * C, generator=torch.Generator().manual_seed(2))
