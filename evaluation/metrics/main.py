@@ -3,14 +3,16 @@
     python evaluation/metrics/main.py --path <generated_results.json> [--task 100111111] [--level 0..3] [--no_rotate] [--3d]
            [--use_relative_path --base_dir <GeoBenchMeta>] [--fid_path <real images>] [--gen_img_key gen_img_path]
            [--clip_weights <file>] [--dino_weights <file>] [--dinov2_weights <file>] [--model <SD folder | synthetic:sd21-base>] [--precision f32|x3]
+           [--hps_weights <file> --hps_tokenizer <folder>]
 
 --task is nine digits (1 = compute): FID, IRS, HPS, BGC, SUBC, WRAP_E, MD, FID_DINO, FID_KD.  The reference downloads its extractors (clip.load, torch.hub); there
 is no download here, the weights are local files: --clip_weights (CLIP ViT-B/32: a transformers CLIPVisionModelWithProjection state dict or the OpenAI
 checkpoint's visual.* names), --dino_weights (dino_vitb16), --dinov2_weights (dinov2_vitb14), each a .safetensors file or a torch.save'd state dict;
---model is the Stable-Diffusion checkpoint whose features Mean Distance matches.  FID (Inception-v3), IRS (ImageReward) and HPS (HPSv2) have no model code in the
-reference tree to pin an implementation to: they are reported as `not built`, and the other metrics still run.  A metric whose weights were not given is
-reported as such, likewise.  --precision is the arithmetic of the networks: f32 (default: exact-fp32 MFMA) or x3 (split-bf16: hi + lo bf16 operand pairs, fp32
-accumulation; the three ViT towers are built with x3=True and the MD pipeline with from_pretrained(..., x3=True))."""
+--model is the Stable-Diffusion checkpoint whose features Mean Distance matches; --hps_weights is `HPS_v2.1_compressed.pt` (its state_dict in open_clip's layout,
+or transformers' CLIPModel layout) and --hps_tokenizer a folder with CLIP's vocab.json and merges.txt (HPS: OpenCLIP ViT-H/14, freefine_amd/hps.py).  FID
+(Inception-v3 needs torchvision) and IRS (ImageReward and BLIP) need packages that are not installed, so there is nothing to pin an implementation to: they are
+reported as `not built`, and the other metrics still run.  A metric whose weights were not given is reported as such, likewise.  --precision is the arithmetic of the networks: f32 (default: exact-fp32 MFMA) or x3 (split-bf16: hi + lo bf16 operand pairs, fp32
+accumulation; the ViT towers, HPS's two among them, are built with x3=True and the MD pipeline with from_pretrained(..., x3=True))."""
 import argparse
 import json
 import os
@@ -19,8 +21,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
 NAMES = ("FID", "IRS", "HPS", "BGC", "SUBC", "WRAP_E", "MD", "FID_DINO", "FID_KD")
-NOT_BUILT = {"FID": "not built (Inception-v3: no model code to pin it to)", "IRS": "not built (ImageReward: no model code to pin it to)",
-             "HPS": "not built (HPSv2: no model code to pin it to)"}
+NOT_BUILT = {"FID": "not built (Inception-v3: torchvision is not installed, nothing to pin it to)",
+             "IRS": "not built (ImageReward and BLIP are not installed, nothing to pin it to)"}
 LEVEL_WORDS = {1: ("lightly", "slightly", "gently", "mildly"), 2: ("moderately", "markedly", "appreciably"), 3: ("heavily", "intensely", "significantly", "strongly")}
 PATH_KEYS = ("ori_img_path", "coarse_input_path", "ori_mask_path", "tgt_mask_path")
 
@@ -84,9 +86,12 @@ def main(argv=None):
     ap.add_argument("--dino_weights", default=None, help="DINO ViT-B/16 weights (SUBC)")
     ap.add_argument("--dinov2_weights", default=None, help="DINOv2 ViT-B/14 weights (FID_DINO, FID_KD)")
     ap.add_argument("--model", default=None, help="Stable-Diffusion folder or synthetic:<name> (MD)")
+    ap.add_argument("--hps_weights", default=None, help="HPS_v2.1_compressed.pt: OpenCLIP ViT-H/14 weights, open_clip or transformers layout (HPS)")
+    ap.add_argument("--hps_tokenizer", default=None, help="folder with CLIP's vocab.json and merges.txt (HPS)")
     ap.add_argument("--precision", default="f32", choices=("f32", "x3"), help="arithmetic of the networks: f32 = exact fp32, x3 = split-bf16")
     ap.add_argument("--clip_config", default="vitb32", help=argparse.SUPPRESS)        # "tiny": the test sizes
     ap.add_argument("--dino_config", default="vitb16", help=argparse.SUPPRESS)
+    ap.add_argument("--hps_config", default="vith14", choices=("vith14", "tiny"), help=argparse.SUPPRESS)      # with "tiny", --hps_tokenizer bytes: text.ByteTokenizer
     args = ap.parse_args(argv)
     if len(args.task) != len(NAMES) or set(args.task) - set("01"):
         ap.error(f"--task takes {len(NAMES)} digits of 0 / 1")
@@ -106,6 +111,13 @@ def main(argv=None):
         from freefine_amd import metrics as FM
         if name in NOT_BUILT:
             return NOT_BUILT[name]
+        if name == "HPS":
+            if not args.hps_weights or not args.hps_tokenizer:
+                return "not built into this run (--hps_weights / --hps_tokenizer missing)"
+            from freefine_amd import hps
+            vcfg, tcfg = ("tiny14", "tiny") if args.hps_config == "tiny" else ("vith14", "vith14")
+            model = hps.HipHPSv2.from_state(load_state(args.hps_weights), hps.load_tokenizer(args.hps_tokenizer), vcfg, tcfg, dtype=torch.float32, x3=x3)
+            return FM.calculate_hps(data, label, model)
         if name == "BGC":
             if not args.clip_weights:
                 return "not run (--clip_weights missing)"

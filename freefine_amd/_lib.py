@@ -127,6 +127,8 @@ SYMBOLS = {
     "ffn_layernorm": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _f]),
     "ffn_layernorm_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f]),
     "ffn_softmax_rows": (_i, [_vp, _i, _vp, _vp, _l, _i, _f]),
+    "ffn_pool_layernorm": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i]),
+    "ffn_cosine_rows": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
     "ffn_cfg_masked": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _l, _i]),
     "ffn_ddim_inv_step": (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _l]),
     "ffn_ddim_ctrl_step": (_i, [_vp, C.POINTER(CtrlStepDesc)]),

@@ -14,6 +14,10 @@ ffn_resize_pil_u8 with a crop window, PIL's bicubic bit for bit -- then ToTensor
 
 dtype float32 = parity mode (exact-fp32 MFMA), float32 with x3=True = split-bf16, bfloat16 = fast mode.
 
+hps.py's OpenCLIP ViT-H/14 image tower is this class under another configuration check (`_config`), so what differs between the two is read from the
+configuration here: the MLP activation (`_ACT`), the head dim, and the patch embedding's contraction length, zero-padded to whole chunks where 3 p p is none
+(patch 14; nothing at patch 32).  `_pool` is the class rows' norm, which that tower replaces by one launch.
+
 Split-bf16 (`HipCLIPVision(..., x3=True)`): every GEMM (the 768 -> 512 projection included) and the attention run FFN_BF16X3 -- operands as hi + lo bf16 pairs,
 three bf16 MFMAs per product term, fp32 accumulation -- in the layers as encoder.py describes it; post_layernorm too writes the pair rows its GEMM reads; the
 residual stream (pre_layrnorm writes it: fp32), the positional embedding and the class row stay fp32.  `features_u8` gets the patch GEMM's rows from
@@ -150,17 +154,24 @@ class HipCLIPVision:
     """CLIPVisionModelWithProjection(pixel_values).image_embeds = clip's encode_image on the HIP kernels (module docstring).  forward: float [B, 3, 224, 224]
     (normalised) -> fp32 [B, projection_dim]; features_u8: decoded uint8 images of any one size -> the same, the transform on the device."""
 
+    _config = staticmethod(clip_vision_config)      # the checked configuration of this tower (hps.py's ViT-H/14 tower has its own)
+    _ACT = {"quick_gelu": "qgelu", "gelu": "gelu"}    # hidden_act -> fc1's GEMM epilogue
+
     def __init__(self, config, state, dtype=torch.float32, device="cuda:0", x3=False):
         encoder.check_mode(dtype, x3)
-        self.config = clip_vision_config(config)
+        self.config = self._config(config)
         self.dtype, self.device, self.x3 = dtype, torch.device(device), bool(x3)
         self.host = pack_vision_state(self.config, state)
         cfg, dev = self.config, self.device
         up = lambda k: self.host[k].to(dev)
-        self.kpe = 3 * cfg.patch_size ** 2                       # 3072 at patch 32: whole 16-byte chunks
-        if self.x3 and (self.kpe % 32 or cfg.hidden_size % 32 or cfg.intermediate_size % 32):
-            raise ValueError(f"HipCLIPVision x3: contraction lengths {self.kpe}, {cfg.hidden_size}, {cfg.intermediate_size} must be multiples of 32 (blocked pair rows)")
-        self.pe, self.proj = ops.pack_linear(up("pe.w"), dtype, x3=self.x3), ops.pack_linear(up("proj.w"), dtype, x3=self.x3)
+        K, e = 3 * cfg.patch_size ** 2, 32 if self.x3 else 8     # split-bf16: whole 32-column blocks, so that both operands are in the blocked pair form
+        self.kpe = (K + e - 1) // e * e                          # 3072 at patch 32: whole chunks as it is; patch 14: 588 -> 592, split-bf16 608 (zero columns, as dino.py)
+        if self.x3 and (cfg.hidden_size % 32 or cfg.intermediate_size % 32):
+            raise ValueError(f"{type(self).__name__} x3: contraction lengths {cfg.hidden_size}, {cfg.intermediate_size} must be multiples of 32 (blocked pair rows)")
+        wpe = up("pe.w")
+        if self.kpe != K:
+            wpe = torch.nn.functional.pad(wpe, (0, self.kpe - K))
+        self.pe, self.proj = ops.pack_linear(wpe, dtype, x3=self.x3), ops.pack_linear(up("proj.w"), dtype, x3=self.x3)
         self.cls, self.pos = up("cls").to(dtype)[None].contiguous(), up("pos").to(dtype).contiguous()
         self.pre, self.post = (up("pre.w"), up("pre.b")), (up("post.w"), up("post.b"))
         self.blocks = encoder.clip_blocks(cfg, self.host, dev, dtype, self.x3)
@@ -180,17 +191,23 @@ class HipCLIPVision:
         x = ops.layernorm(x, *self.pre, eps=eps)
         vt = encoder.vt_buffer(x)
         for b in self.blocks:
-            x = encoder.run_block(b, x, vt, heads=cfg.num_attention_heads, eps=eps, act="qgelu", hidden=cfg.intermediate_size, x3=x3)
-        pooled = ops.layernorm(x[:, 0].contiguous(), *self.post, eps=eps, pair=x3)                  # the class rows only
-        return ops.linear(pooled, self.proj, None, K=C).float()
+            x = encoder.run_block(b, x, vt, heads=cfg.num_attention_heads, eps=eps, act=self._ACT[cfg.hidden_act], hidden=cfg.intermediate_size, x3=x3)
+        return ops.linear(self._pool(x), self.proj, None, K=C).float()
+
+    def _pool(self, x):
+        """post_layernorm of the class rows only (split-bf16: as the pair rows the projection reads)"""
+        return ops.layernorm(x[:, 0].contiguous(), *self.post, eps=self.config.layer_norm_eps, pair=self.x3)
 
     @torch.no_grad()
     def forward(self, x):
         """x float [B, 3, image_size, image_size] (normalised image) -> fp32 [B, projection_dim]"""
         cfg = self.config
         if tuple(x.shape[1:]) != (3, cfg.image_size, cfg.image_size):
-            raise ValueError(f"HipCLIPVision: input {tuple(x.shape)}; the tower takes [B, 3, {cfg.image_size}, {cfg.image_size}] (no positional interpolation)")
-        a = im2col(x.to(self.device, torch.float32), cfg.patch_size).to(self.dtype).contiguous()
+            raise ValueError(f"{type(self).__name__}: input {tuple(x.shape)}; the tower takes [B, 3, {cfg.image_size}, {cfg.image_size}] (no positional interpolation)")
+        a = im2col(x.to(self.device, torch.float32), cfg.patch_size).to(self.dtype)
+        if self.kpe != a.shape[1]:
+            a = torch.nn.functional.pad(a, (0, self.kpe - a.shape[1]))
+        a = a.contiguous()
         return self._tower(a, x.shape[0])
 
     __call__ = forward

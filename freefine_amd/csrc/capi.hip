@@ -70,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 7; }      // 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
+extern "C" int ffn_version(void) { return 8; }      // 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -1129,6 +1129,34 @@ extern "C" int ffn_embed_tokens(void* stream, int dtype, const int* ids, const f
     REQUIRE(M > 0 && S > 0 && V > 0 && C > 0 && C % 4 == 0 && M < (1l << 31), "embed_tokens: bad shape M=%ld S=%d C=%d V=%d (C %% 4 == 0)", M, S, C, V);
     fembed_launch(reinterpret_cast<hipStream_t>(stream), dtype == FFN_BF16, ids, table, pos, out, M, S, C, V);
     return check_launch("embed_tokens");
+}
+
+// ---- pooled LayerNorm and cosine of the CLIP towers' projections (kernels: attn_causal.hip) ------------------------------------------------
+extern "C" __attribute__((visibility("hidden"))) void fpool_ln_launch(hipStream_t s, int bf16_in, int pair, const void* x, const int* ids, void* y,
+                                                                      const float* gamma, const float* beta, int N, int S, int C, float eps);
+extern "C" __attribute__((visibility("hidden"))) void fcosine_launch(hipStream_t s, const float* a, const float* b, float* out, int B, int P, int b_rows);
+
+extern "C" int ffn_pool_layernorm(void* stream, int dtype, const void* x, const int* ids, void* y, const float* gamma, const float* beta, int N, int S, int C,
+                                  float eps, int pair) {
+    REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16, "pool_layernorm: bad dtype %d", dtype);
+    REQUIRE(pair == 0 || (pair == 1 && dtype == FFN_F32), "pool_layernorm: pair output takes fp32 input (dtype %d, pair %d)", dtype, pair);
+    REQUIRE(x && y && gamma && beta, "pool_layernorm: null pointer");
+    REQUIRE(aligned16(x) && aligned16(y) && (reinterpret_cast<uintptr_t>(ids) & 3) == 0, "pool_layernorm: x, y must be 16-byte aligned, ids 4-byte aligned");
+    const int epc = dtype == FFN_F32 ? 4 : 8;
+    REQUIRE(N > 0 && S > 0 && C > 0 && C % epc == 0 && C / epc <= 64 * 6, "pool_layernorm: bad shape N=%d S=%d C=%d (C %% %d == 0, C <= %d)", N, S, C, epc,
+            64 * 6 * epc);
+    REQUIRE(!ids || S <= 96, "pool_layernorm: S=%d ids per sequence (at most 96)", S);
+    fpool_ln_launch(reinterpret_cast<hipStream_t>(stream), dtype == FFN_BF16, pair, x, ids, y, gamma, beta, N, S, C, eps);
+    return check_launch("pool_layernorm");
+}
+
+extern "C" int ffn_cosine_rows(void* stream, const float* a, const float* b, float* out, int B, int P, int b_rows) {
+    REQUIRE(a && b && out, "cosine_rows: null pointer");
+    REQUIRE(aligned16(a) && aligned16(b) && (reinterpret_cast<uintptr_t>(out) & 3) == 0, "cosine_rows: a, b must be 16-byte aligned, out 4-byte aligned");
+    REQUIRE(B > 0 && P > 0 && P % 4 == 0, "cosine_rows: bad shape B=%d P=%d (P %% 4 == 0)", B, P);
+    REQUIRE(b_rows == 1 || b_rows == B, "cosine_rows: b has %d rows (1 or B=%d)", b_rows, B);
+    fcosine_launch(reinterpret_cast<hipStream_t>(stream), a, b, out, B, P, b_rows);
+    return check_launch("cosine_rows");
 }
 
 // ---- DIFT correspondence search (kernels and launch sequence: dift.hip / dift_match.h) -----------------------------------------------------------

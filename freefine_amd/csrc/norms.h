@@ -7,19 +7,7 @@
 // (reached from /root/reference/src/utils/attention.py:105-214).
 #pragma once
 #include "common.h"
-
-// PAIR output (split-bf16 mode, T = float): the normalised row is written in the bf16 pair form an FFN_BF16X3 GEMM reads as its A operand
-// (hi = bf16(v), lo = bf16(v - hi); blocked layout: common.h pair_pos) instead of fp32 -- same bytes, and the separate ffn_split_pair pass disappears.
-__device__ __forceinline__ void store_pair4(bf16* yp, long row, int C, int c, const float* f) {
-    u32x2 hi, lo;
-    hi[0] = pack_bf16x2(f[0], f[1]);
-    hi[1] = pack_bf16x2(f[2], f[3]);
-    lo[0] = pack_bf16x2(f[0] - __uint_as_float(hi[0] << 16), f[1] - __uint_as_float(hi[0] & 0xffff0000u));
-    lo[1] = pack_bf16x2(f[2] - __uint_as_float(hi[1] << 16), f[3] - __uint_as_float(hi[1] & 0xffff0000u));
-    bf16* q = yp + row * 2 * C + pair_pos(c, C);
-    *reinterpret_cast<u32x2*>(q) = hi;
-    *reinterpret_cast<u32x2*>(q + pair_lo(C)) = lo;
-}
+#include "layernorm_row.h"      // store_pair4, layernorm_row
 
 // ---- (1) partial statistics: grid (nchunk, B), 256 threads ------------------------------------------------------
 // partial[b][chunk][c][2] = (mean, M2) of channel c over the chunk's pixels, M2 = sum (x - mean)^2.  (sum, sum of squares) in fp32 loses the variance to
@@ -338,57 +326,14 @@ __global__ __launch_bounds__(1024) void gn_fused_kernel(const T* __restrict__ x,
 }
 
 // ---- LayerNorm over C per row; one wave per row, two-pass in registers --------------------------------------
-template <typename T, int MAXCH, bool PAIR = false>  // MAXCH = max 16-byte chunks per lane
+template <typename T, int MAXCH, bool PAIR = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         int M, int C, float eps) {
-    constexpr int EPC = DT<T>::EPC;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
     if (row >= M) return;
-    const int cch = C / EPC;
-    float f[MAXCH][EPC];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-        const int cc = lane + 64 * i;
-        if (cc < cch) {
-            const u32x4 v = *reinterpret_cast<const u32x4*>(x + (long)row * C + cc * EPC);
-            DT<T>::unpack(v, f[i]);
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) s += f[i][e];
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    const float mean = s / (float)C;
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-        const int cc = lane + 64 * i;
-        if (cc < cch) {
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) {
-                const float d = f[i][e] - mean;
-                ss += d * d;
-            }
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
-    const float rstd = 1.0f / sqrtf(ss / (float)C + eps);
-#pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-        const int cc = lane + 64 * i;
-        if (cc < cch) {
-            float o[EPC];
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) {
-                const int c = cc * EPC + e;
-                o[e] = (f[i][e] - mean) * rstd * gamma[c] + beta[c];
-            }
-            if constexpr (PAIR) store_pair4(reinterpret_cast<bf16*>(y), row, C, cc * EPC, o);
-            else *reinterpret_cast<u32x4*>(y + (long)row * C + cc * EPC) = DT<T>::pack(o);
-        }
-    }
+    layernorm_row<T, MAXCH, PAIR>(x, (long)row, y, (long)row, gamma, beta, C, eps, lane);
 }
 
 // ---- row softmax (VAE mid-block single-head attention path: scores materialised once, 2 calls per image) ----

@@ -17,8 +17,12 @@ CLIPVisionModelWithProjection (the arithmetic of clip's encode_image), freefine_
 LayerScale (tests/golden/g15_dino16_cls.npz).  Masking, resizing (PIL bicubic / bilinear bit for bit) and cropping run on the device in one entry
 (ops.resize_pil_u8).  consistency_pairs / calculate_bgc / calculate_subc below are the drivers; weights from the caller.
 
-The remaining extractors of the suite (Inception-v3 for FID, HPSv2, ImageReward) have no model code in the reference tree, nothing to pin them to, and are NOT
-built; evaluation/metrics/main.py reports them as such.
+The Human Preference Score (human_preference_score.py) is the cosine between OpenCLIP ViT-H/14 embeddings of a generated image and of its source image's
+caption.  freefine_amd/hps.py HipHPSv2 runs both towers and the cosine on the project's kernels, pinned to transformers' CLIP*ModelWithProjection (the same
+arithmetic; hpsv2 and open_clip exist nowhere this is tested).  calculate_hps below is the driver; weights and tokenizer files from the caller.
+
+The remaining extractors of the suite (Inception-v3 for FID, ImageReward for IRS) need packages that are not installed (torchvision; ImageReward and BLIP), so
+there is nothing to pin them to and they are NOT built; evaluation/metrics/main.py reports them as such.
 
 Mean Distance (MD/mean_distance.py), the one metric of the suite that measures the GEOMETRY of an edit, needs no foreign network: its feature extractor is
 DIFT, i.e. Stable Diffusion itself, and runs on the project's kernels (freefine_amd/dift.py: HipVAE + HipUNet.features; the correspondence search is
@@ -277,6 +281,41 @@ def calculate_subc(data, image_label, model, batch_size=32, reader=None, x3=Fals
     calculate_bgc."""
     scores = consistency_scores(consistency_pairs(data, image_label), _dino16_model(model, x3), "subc", batch_size, reader)
     return sum(scores) / len(scores)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# Human Preference Score (human_preference_score.py)
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+def calculate_hps(data, image_label, model, reader=None, batch_size=32):
+    """human_preference_score.py:calculate_hps (:65-83): for every image entry the prompt is image["4v_caption"] and every sample's data[...][image_label] file is
+    scored against it; the result is the sum of the scores over the number of samples.  model: a freefine_amd.hps.HipHPSv2 (anything with
+    score_u8(uint8 [B, H, W, 3], prompt) -> [B]).  The files of one entry are grouped by size so that one launch sees one size, batched by `batch_size`
+    within a group.  `reader` maps a path to a uint8 HWC array (default: PIL, as decoded); RGB only -- open_clip's transform converts other modes, this
+    driver refuses them.  No samples: ValueError (the reference divides by zero)."""
+    if reader is None:
+        from PIL import Image
+        reader = lambda p: np.array(Image.open(p))
+    total, number = 0.0, 0
+    for image in data.values():
+        files = [sample[image_label] for instance in image["instances"].values() for sample in instance.values()]
+        if not files:
+            continue
+        prompt = image["4v_caption"]
+        groups = {}
+        for p in files:
+            a = np.asarray(reader(p))
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"{p}: RGB images only (8 bits, 3 channels); got dtype {a.dtype}, shape {a.shape}")
+            groups.setdefault(a.shape[:2], []).append(np.ascontiguousarray(a))
+        for imgs in groups.values():
+            for s in range(0, len(imgs), batch_size):
+                sc = model.score_u8(np.stack(imgs[s:s + batch_size]), prompt)
+                sc = sc.detach().cpu().numpy() if hasattr(sc, "detach") else np.asarray(sc)
+                total += float(sc.astype(np.float64).sum())
+        number += len(files)
+    if number == 0:
+        raise ValueError(f"calculate_hps: no samples with {image_label!r} in the data")
+    return total / number
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------

@@ -762,6 +762,47 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None, pair=False):
     return out
 
 
+def pool_layernorm(x, ids, gamma, beta, eps=1e-5, out=None, pair=False):
+    """LayerNorm of one row per sequence of x [N, S, C] -> [N, C] (pair: the pair rows [N, 2C], fp32 x only): row 0 (ids None: a ViT's class token) or the first
+    position holding the sequence's largest id (ids int32 [N, S] on the device, S <= 96: open_clip's text pooling).  ffn_layernorm's routine on the gathered
+    row, bit for bit (ffn_pool_layernorm)."""
+    lib = L.load()
+    assert x.ndim == 3 and x.is_contiguous()
+    N, S, Cc = x.shape
+    if ids is not None:
+        assert ids.dtype == torch.int32 and tuple(ids.shape) == (N, S) and ids.is_contiguous() and ids.device == x.device
+    if pair:
+        assert x.dtype == torch.float32
+        if out is None:
+            out = torch.empty(N, 2 * Cc, dtype=torch.bfloat16, device=x.device)
+        assert out.dtype == torch.bfloat16 and tuple(out.shape) == (N, 2 * Cc) and out.is_contiguous()
+        out = _mark_pair(out, Cc)
+    elif out is None:
+        out = torch.empty(N, Cc, dtype=x.dtype, device=x.device)
+    else:
+        assert out.dtype == x.dtype and tuple(out.shape) == (N, Cc) and out.is_contiguous()
+    L.check(_timed(f"pool_layernorm_kernel<{_tname(x)}>", 0.0, 2.0 * N * Cc * x.element_size(),
+                   lambda: lib.ffn_pool_layernorm(_stream(), _dt(x), x.data_ptr(), _p(ids), out.data_ptr(), gamma.data_ptr(), beta.data_ptr(), N, S, Cc, eps,
+                                                  int(pair))), "ffn_pool_layernorm")
+    return out
+
+
+def cosine_rows(a, b, out=None):
+    """a fp32 [B, P], b fp32 [B, P] or [1, P] -> fp32 [B]: <a_i, b_i> / (max(|a_i|, 1e-12) max(|b_i|, 1e-12)), the cosine of F.normalize'd rows
+    (ffn_cosine_rows; deterministic)"""
+    lib = L.load()
+    assert a.dtype == b.dtype == torch.float32 and a.ndim == b.ndim == 2 and a.is_contiguous() and b.is_contiguous() and a.device == b.device
+    B, P = a.shape
+    assert b.shape[1] == P
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=a.device)
+    else:
+        assert out.dtype == torch.float32 and tuple(out.shape) == (B,) and out.is_contiguous()
+    L.check(_timed("cosine_rows_kernel", 6.0 * B * P, 4.0 * (B * P + b.shape[0] * P + B),
+                   lambda: lib.ffn_cosine_rows(_stream(), a.data_ptr(), b.data_ptr(), out.data_ptr(), B, P, b.shape[0])), "ffn_cosine_rows")
+    return out
+
+
 def softmax_rows(x, scale=1.0, out=None):
     lib = L.load()
     N = x.shape[-1]

@@ -285,6 +285,17 @@ int ffn_layernorm(void* stream, int dtype, const void* x, void* y, const float* 
                   float eps);
 int ffn_layernorm_pair(void* stream, const float* x, void* y, const float* gamma, const float* beta, int M, int C, float eps);
 int ffn_softmax_rows(void* stream, int dtype, const void* x, void* y, long M, int N, float scale);
+/* ABI version 8.  LayerNorm of ONE row per sequence of x [N][S][C] (activation type of `dtype`: FFN_F32 / FFN_BF16) -> y [N][C] in the same type, or
+ * (pair = 1, FFN_F32 only) the pair rows [N][2C] of ffn_layernorm_pair.  ids == NULL: row 0 of every sequence (the class token of a ViT); otherwise ids int32
+ * [N][S] in device memory, S <= 96, and the row is the FIRST position holding the sequence's largest id (open_clip's text pooling: end-of-text has the largest
+ * id).  The statistics and the affine step are ffn_layernorm's routine: bit-identical to ffn_layernorm on the gathered rows.  C as ffn_layernorm (a multiple of
+ * 4 fp32 / 8 bf16 values, at most 384 16-byte chunks); x, y 16-byte aligned.  Anything else: FFN_EINVAL before any launch. */
+int ffn_pool_layernorm(void* stream, int dtype, const void* x, const int* ids, void* y, const float* gamma, const float* beta, int N, int S, int C, float eps,
+                       int pair);
+/* ABI version 8.  out[i] = <a_i, b_j> / (max(|a_i|, 1e-12) max(|b_j|, 1e-12)), a fp32 [B][P], b fp32 [b_rows][P] with b_rows = B (j = i) or 1 (j = 0): the
+ * cosine of torch.nn.functional.normalize'd rows (the Human Preference Score: evaluation/metrics/human_preference_score.py).  Three fp32 sums per row, summed
+ * in a fixed order: deterministic.  P % 4 == 0; a, b 16-byte aligned. */
+int ffn_cosine_rows(void* stream, const float* a, const float* b, float* out, int B, int P, int b_rows);
 
 /* ---- scheduler / guidance elementwise (fp32, NCHW like the reference) ------------------------------------------ */
 /* eps = eu + cfg*(ec-eu)*mask   (src/demo/model.py:605-611; mask NULL -> :608) */
