@@ -715,7 +715,8 @@ static int igemm_validate(int dtype, const ffn_igemm_desc& d) {
         REQUIRE(d.stride == 1 || d.stride == 2, "igemm(fp8): stride %d", d.stride);
         int ex = 0;
         REQUIRE(d.alpha > 0.f && frexpf(d.alpha, &ex) == 0.5f, "igemm(fp8): alpha must be a power of two (the un-scaling of two power-of-two operand scales)");
-        if (d.residual) REQUIRE(d.ldr % 4 == 0, "igemm(fp8): ldr=%d must be a multiple of 4", d.ldr);
+        if (d.residual) REQUIRE(d.ldr % 4 == 0 && d.ldr >= d.N, "igemm(fp8): ldr=%d must be a multiple of 4 and >= N=%d", d.ldr, d.N);
+        REQUIRE(d.ldo >= d.N, "igemm(fp8): ldo=%d must be >= N=%d", d.ldo, d.N);
         return FFN_OK;
     }
     const int epc = dtype == FFN_F32 ? 4 : 8;
@@ -784,6 +785,16 @@ static int igemm_validate(int dtype, const ffn_igemm_desc& d) {
     const int act = d.flags & (FFN_IG_OUT_SILU | FFN_IG_OUT_GELU | FFN_IG_OUT_RELU | FFN_IG_OUT_QGELU);
     REQUIRE((act & (act - 1)) == 0, "igemm: SILU / GELU / QGELU / RELU are mutually exclusive");
     REQUIRE(d.splitk >= 0, "igemm: splitk must be >= 0");
+    // row strides cover what a row holds (no kernel looks at them for overlap: a short stride would make neighbouring rows share memory)
+    if (!d.conv && dtype != FFN_BF16X3) REQUIRE(d.lda >= d.K, "igemm: lda=%d must be >= K=%d", d.lda, d.K);
+    if (d.flags & FFN_IG_OUT_TRANSPOSED) {
+        const int cols = d.rows_per_batch < d.M ? d.rows_per_batch : d.M;
+        REQUIRE(d.ldo >= cols, "igemm: transposed ldo=%d must be >= the %d rows of a batch", d.ldo, cols);
+    } else if (!(d.flags & FFN_IG_OUT_PAIR)) {
+        const int nout = (d.flags & FFN_IG_GEGLU) ? d.N / 2 : d.N;
+        REQUIRE(d.ldo >= nout, "igemm: ldo=%d must be >= the %d output columns", d.ldo, nout);
+    }
+    if (d.residual) REQUIRE(d.ldr >= d.N, "igemm: ldr=%d must be >= N=%d", d.ldr, d.N);
     return FFN_OK;
 }
 static bool tuned_family(int dtype, const ffn_igemm_desc& d) { return dtype != FFN_F32 && !(d.flags & FFN_IG_OUT_TRANSPOSED); }
@@ -846,7 +857,10 @@ extern "C" int ffn_igemm(void* stream, int dtype, const ffn_igemm_desc* d0) {
         REQUIRE(d0->A && d0->W && d0->out, "igemm: null A/W/out");
         REQUIRE(aligned16(d0->A) && aligned16(d0->W) && aligned16(d0->out), "igemm: A/W/out must be 16-byte aligned");
     }
-    if (dtype == FFN_BF16X3 && d0->residual) REQUIRE(aligned16(d0->residual), "igemm: fp32 residual must be 16-byte aligned");
+    // the residual is read four columns per lane: 16 bytes of fp32 (FFN_F32, FFN_BF16X3), 8 bytes of bf16 (FFN_BF16, FFN_FP8)
+    if ((dtype == FFN_BF16X3 || dtype == FFN_F32) && d0->residual) REQUIRE(aligned16(d0->residual), "igemm: fp32 residual must be 16-byte aligned");
+    if ((dtype == FFN_BF16 || dtype == FFN_FP8) && d0->residual)
+        REQUIRE((reinterpret_cast<uintptr_t>(d0->residual) & 7) == 0, "igemm%s: bf16 residual must be 8-byte aligned", dtype == FFN_FP8 ? "(fp8)" : "");
     if (d0->ws) REQUIRE(aligned16(d0->ws) && d0->ws_bytes >= 0, "igemm%s: workspace must be 16-byte aligned", dtype == FFN_FP8 ? "(fp8)" : "");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const ffn_igemm_desc d = igemm_view(dtype, *d0);

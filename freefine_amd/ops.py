@@ -363,7 +363,8 @@ class batch_invariant:
 
 def linear(x, w, bias=None, *, K=None, out=None, residual=None, rowbias=None, rows_per_batch=None, silu=False,
            geglu=False, out_f32=False, transposed_ld=None, alpha=1.0, splitk=0, out_pair=False, gelu=False, relu=False, kv64_from=None, qgelu=False):
-    """out = x @ w[:, :K]^T (+bias ...).  x: [..., K] contiguous rows (M = prod of leading dims).
+    """out = x @ w[:, :K]^T (+bias ...).  x: [..., K] rows (M = prod of leading dims).  x, w, out and residual may be column views of wider buffers
+    (contiguous columns, rows one row stride apart: lda, Kpad, ldo, ldr of the descriptor are their row strides).
     kv64_from (split-bf16 only): the projection writes the attention kernels' pre-split K / V^T images itself (FFN_IG_OUT_KV64): row-major output --
     columns >= kv64_from of every row as [hi(64) | lo(64)] blocks per head in the bytes of their fp32 values; transposed output (any value, use 0) --
     every run of 64 positions of a row as one such block.  The caller hands such buffers to ops.attention(kv_images=True)."""
@@ -422,7 +423,8 @@ def linear(x, w, bias=None, *, K=None, out=None, residual=None, rowbias=None, ro
         if out is None:
             out = torch.empty(*x.shape[:-1], n_out, dtype=torch.float32 if out_f32 else odt, device=x.device)
         d.ldo = out.stride(-2) if out.ndim > 1 else n_out          # a column view of a wider buffer (cat_dst) keeps the buffer's row stride
-    d.ldr = residual.shape[-1] if residual is not None else 0
+    assert xa.stride(-1) == 1 and out.stride(-1) == 1 and (residual is None or residual.stride(-1) == 1), "linear: x, out and residual need contiguous columns"
+    d.ldr = (residual.stride(-2) if residual.ndim > 1 else residual.shape[-1]) if residual is not None else 0      # (a column view keeps its buffer's row stride)
     d.out = out.data_ptr()
     if kv64_from is not None:
         assert x3 and residual is None and rowbias is None and not (silu or gelu or relu or qgelu or geglu or out_pair)
@@ -475,8 +477,12 @@ def conv3x3(x, w, bias, B, Hin, Win, Cin, *, stride=1, pad=1, upsample=False, ou
     d.ldrb = (rowbias_ld or rowbias.stride(0)) if rowbias is not None else 0
     if out is None:
         out = torch.empty(B, Hout * Wout, N, dtype=torch.float32 if out_f32 else odt, device=x.device)
-    d.out, d.ldo = out.data_ptr(), out.stride(-2)                   # (a column view of a wider buffer keeps the buffer's row stride)
-    d.ldr = residual.shape[-1] if residual is not None else 0
+    # the conv gather reads pixels of Cin elements from a dense NHWC tensor (no pixel stride in the ABI outside split-bf16): a strided x is refused;
+    # out and residual may be column views of wider buffers, which keep their buffers' row strides
+    assert xa.is_contiguous(), "conv3x3: x must be contiguous (a column view of a wider buffer has no pixel stride the kernels could follow)"
+    assert out.stride(-1) == 1 and (residual is None or residual.stride(-1) == 1), "conv3x3: out and residual need contiguous columns"
+    d.out, d.ldo = out.data_ptr(), out.stride(-2)
+    d.ldr = residual.stride(-2) if residual is not None else 0
     d.Hin, d.Win, d.Cin, d.Hout, d.Wout = Hin, Win, Cin, Hout, Wout
     d.stride, d.pad, d.upsample = stride, pad, 1 if upsample else 0
     d.flags, d.alpha, d.conv = (L.IG_OUT_F32 if out_f32 else 0) | (L.IG_OUT_RELU if relu else 0), (w._ffn_f8[1] if f8 else 1.0), 1

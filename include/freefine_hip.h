@@ -69,6 +69,24 @@ enum {
                                        activations.py QuickGELUActivation).  Same rules as FFN_IG_OUT_GELU, all three dtypes; runs on the generic tiles (the ping-pong
                                        tiles' epilogue does not carry it) */
 };
+/* Strides and alignment of ffn_igemm_desc: what each kernel family relies on, and what ffn_igemm therefore checks before any launch (FFN_EINVAL).
+ * Every operand may be a column view of a wider buffer: only the row strides below and the base pointers enter the addressing.
+ *   A, W    every family stages 16-byte chunks (4 fp32 / 8 bf16 / 16 e4m3) straight into LDS: A, W 16-byte aligned, lda, Kpad (split-bf16: a_lo too)
+ *           multiples of the chunk, lda >= K (dense; pair forms: lda >= 2K blocked, a_lo >= K and a_lo + K <= lda planes), Kpad >= K (2K / 3K).
+ *           Chunks are whole inside K or whole outside it (K a multiple of the chunk): columns [K, lda) of A and [K, Kpad) of W are never read.
+ *           3x3 / 2x2 convolutions gather pixels of Cin (split-bf16: lda) elements from a dense NHWC tensor: there is no pixel stride outside split-bf16.
+ *   out     four columns per lane.  igemm_glds_kernel, igemm_halo_kernel and igemm_splitk_reduce_kernel (igemm.h) store them as ONE naturally aligned
+ *           access: 8 bytes of bf16, 16 bytes of fp32 (also FFN_IG_OUT_F32, the pair form: two 8-byte halves, the transposed form with
+ *           rows_per_batch % 4 == 0; other transposed outputs go element by element) -- out 16-byte aligned, N % 4 == 0, ldo % 4 == 0 suffice.
+ *           igemm_pp_kernel (igemm_p8.h) stores through a buffer resource over [out, out + M * ldo): bf16 rows leave as 16-byte pieces of two
+ *           neighbouring fragments (and one 8-byte piece where the fragment count is odd), fp32 rows as 16-byte pieces, at byte offsets that are
+ *           multiples of 8 (bf16) / 16 (fp32) from a row start.  With ldo % 8 == 4 in bf16 the row starts, and so the 16-byte pieces, are only 8-byte
+ *           aligned: global (buffer) stores of gfx950 need 4-byte alignment, so this is slower, not wrong -- no family is kept off such descriptors.
+ *           Rows >= M fall outside the resource and are dropped; N is whole tiles, so no column >= N is ever addressed.
+ *           ldo >= the columns written: N (GEGLU: N / 2; pair form: ldo / 2 >= them; transposed: min(rows_per_batch, M)).
+ *   residual  read like out is written: 8 bytes of bf16 (FFN_BF16, FFN_FP8) or 16 bytes of fp32 (FFN_F32, FFN_BF16X3) per lane, by plain loads (igemm.h)
+ *           or through a buffer resource over [residual, residual + M * ldr) (igemm_p8.h): residual 8- resp. 16-byte aligned, ldr % 4 == 0, ldr >= N.
+ *   split-K slabs (ws): dense fp32 [splitk][M][N], 16-byte accesses: ws 16-byte aligned. */
 typedef struct ffn_igemm_desc {
     const void* A;        /* dense: [M][lda];  conv: NHWC input [B][Hin][Win][Cin] */
     const void* W;        /* [N][Kpad] */

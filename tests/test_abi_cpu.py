@@ -316,6 +316,54 @@ def test_igemm_kernel_choice_table():
         assert lib.ffn_igemm(None, dtype, ctypes.byref(d)) == -22 and lib.ffn_last_error() == text
 
 
+def test_igemm_strides_and_residual_alignment_are_checked_before_any_launch():
+    """include/freefine_hip.h, "Strides and alignment of ffn_igemm_desc": a row stride shorter than what a row holds (lda < K, ldo < the columns written, ldr < N)
+    and a residual pointer off the alignment its loads need are refused with FFN_EINVAL by ffn_igemm (the strides by ffn_igemm_kernel_name too) -- nothing is
+    launched, no GPU needed.  Control rows: the same descriptors with the smallest admitted values are accepted, among them ldo % 8 == 4 and ldr % 8 == 4 in bf16 (row starts
+    8 bytes apart)."""
+    import ctypes
+    from freefine_amd import _lib
+    lib = _lib.load()
+    F32, BF16, X3, F8 = _lib.FFN_F32, _lib.FFN_BF16, _lib.FFN_BF16X3, _lib.FFN_FP8
+    TR, GEGLU = _lib.IG_OUT_TRANSPOSED, _lib.IG_GEGLU
+
+    def desc(M=584, N=320, K=320, **kw):
+        d = _lib.IgemmDesc()
+        d.A = d.W = d.out = 0x10000                   # never dereferenced
+        d.M, d.N, d.K, d.Kpad, d.lda, d.ldo, d.rows_per_batch, d.alpha, d.splitk = M, N, K, K, K, N, M, 1.0, 1
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def conv8(**kw):                                  # an fp8 3x3 convolution, 3 images of 32 x 32 x 128
+        return desc(3072, 320, 1152, conv=1, Cin=128, lda=128, Hin=32, Win=32, Hout=32, Wout=32, stride=1, pad=1, rows_per_batch=1024, alpha=0.25, **kw)
+
+    def name_rc(dtype, d):
+        return lib.ffn_igemm_kernel_name(dtype, ctypes.byref(d), ctypes.create_string_buffer(200), 200)
+    lib.ffn_igemm_force_config(-1)
+    refused = [(BF16, desc(lda=312), b"lda=312"), (F32, desc(lda=316), b"lda=316"),
+               (BF16, desc(ldo=316), b"ldo=316"), (F32, desc(ldo=316), b"ldo=316"), (X3, desc(x3=2, a_lo=32, lda=640, Kpad=640, ldo=316), b"ldo=316"),
+               (BF16, desc(N=640, flags=GEGLU, ldo=316), b"ldo=316"),
+               (BF16, desc(M=216, rows_per_batch=72, flags=TR, ldo=68), b"transposed ldo=68"), (F32, desc(M=216, rows_per_batch=72, flags=TR, ldo=68), b"transposed ldo=68"),
+               (BF16, desc(residual=0x20000, ldr=316), b"ldr=316"), (X3, desc(x3=2, a_lo=32, lda=640, Kpad=640, residual=0x20000, ldr=316), b"ldr=316"),
+               (F8, conv8(ldo=316), b"igemm(fp8): ldo=316"), (F8, conv8(residual=0x20000, ldr=316), b"igemm(fp8): ldr=316")]
+    for dtype, d, msg in refused:
+        assert name_rc(dtype, d) == -22 and msg in lib.ffn_last_error(), (dtype, msg, lib.ffn_last_error())
+        assert lib.ffn_igemm(None, dtype, ctypes.byref(d)) == -22 and msg in lib.ffn_last_error(), (dtype, msg, lib.ffn_last_error())
+    accepted = [(BF16, desc()), (F32, desc()), (BF16, desc(lda=328, Kpad=384, ldo=324, residual=0x20000, ldr=324)), (BF16, desc(N=640, flags=GEGLU, ldo=320)),
+                (BF16, desc(M=216, rows_per_batch=72, flags=TR, ldo=72)), (BF16, desc(M=40, rows_per_batch=72, flags=TR, ldo=40)),
+                (F8, conv8(ldo=324, residual=0x20000, ldr=324))]
+    for dtype, d in accepted:
+        assert name_rc(dtype, d) == 0, (dtype, lib.ffn_last_error())
+    # pointer alignment is ffn_igemm's own check (ffn_igemm_kernel_name looks at no buffer): it comes after the shape checks and before the launch
+    for dtype, d, msg in [(BF16, desc(residual=0x20004, ldr=320), b"bf16 residual must be 8-byte aligned"),
+                          (F8, conv8(residual=0x20004, ldr=320), b"igemm(fp8): bf16 residual must be 8-byte aligned"),
+                          (F32, desc(residual=0x20008, ldr=320), b"fp32 residual must be 16-byte aligned"),
+                          (X3, desc(x3=2, a_lo=32, lda=640, Kpad=640, residual=0x20008, ldr=320), b"fp32 residual must be 16-byte aligned")]:
+        assert name_rc(dtype, d) == 0
+        assert lib.ffn_igemm(None, dtype, ctypes.byref(d)) == -22 and msg in lib.ffn_last_error(), (dtype, msg, lib.ffn_last_error())
+
+
 def test_attention_row_split_minimises_resident_rounds():
     """ops.attn_row_split: rows per launch of a self-attention call on the one-workgroup-per-CU kernels (256 CUs): never more than FFN_ATT_MAXB, never more rounds
     than the fixed 16-row split, the documented cases, every row covered once."""
