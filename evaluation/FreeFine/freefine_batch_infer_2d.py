@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--variant", default="2d", choices=["2d", "3d_depth", "3d_rgb"],
                     help="3d_rgb: the GeoBench-3D edit with the coarse input rendered here (DepthAnything depth + point-cloud warp) instead of read from disk")
     ap.add_argument("--depth-model", default="synthetic:vitl", help="3d_rgb: a Depth-Anything state dict (.pth) or synthetic:<vits|vitb|vitl>")
+    ap.add_argument("--device-prep", action="store_true", help="resize and coarse-edit every case on the device (csrc/caseprep.h) instead of in numpy on the host: "
+                                                               "the same bytes, the prefetch thread only decodes the PNG files")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank, local = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
@@ -58,7 +60,8 @@ def main():
             dstate = torch.load(args.depth_model, map_location="cpu", weights_only=True)
             dcfg = FDp.depth_config({384: "vits", 768: "vitb", 1024: "vitl"}[dstate["pretrained.cls_token"].shape[-1]])
         depth_model = FDp.HipDepthAnything(dcfg, dstate, dtype=dtype, device=device)
-    geobench.run(model, args.base_dir, batch=args.batch, rank=rank, world=world, variant=args.variant, depth_model=depth_model)
+    geobench.run(model, args.base_dir, batch=args.batch, rank=rank, world=world, variant=args.variant, depth_model=depth_model,
+                 device_prep=args.device_prep)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--no-blending", action="store_true")
     ap.add_argument("--bench", default="2D", choices=["2D", "3D"])
     ap.add_argument("--batch", type=int, default=4, help="cases processed together in one UNet batch")
+    ap.add_argument("--device-prep", action="store_true", help="resize the image and resize + dilate the mask on the device (csrc/caseprep.h) instead of on the host: the same bytes")
     args = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank, local = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
@@ -38,7 +39,8 @@ def main():
     model.modify_unet_forward()
     model.unet.use_graph = True
     from freefine_amd import geobench
-    geobench.run_bggen(model, args.base_dir, blending=not args.no_blending, rank=rank, world=world, batch=args.batch, bench=args.bench)
+    geobench.run_bggen(model, args.base_dir, blending=not args.no_blending, rank=rank, world=world, batch=args.batch, bench=args.bench,
+                       device_prep=args.device_prep)
     if world > 1:
         torch.distributed.destroy_process_group()
 

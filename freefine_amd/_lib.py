@@ -93,6 +93,14 @@ class ResizePilDesc(C.Structure):
     ]
 
 
+class CoarseEditDesc(C.Structure):
+    _fields_ = [
+        ("src_img", C.c_void_p), ("src_mask", C.c_void_p), ("bg", C.c_void_p), ("hole_img", C.c_void_p), ("hole_mask", C.c_void_p), ("inv", C.c_void_p),
+        ("final_img", C.c_void_p), ("tmask", C.c_void_p), ("trans_hole", C.c_void_p),
+        ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("mask_c", C.c_int), ("hole_mask_c", C.c_int),
+    ]
+
+
 # every symbol include/freefine_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _f, _l = C.c_void_p, C.c_int, C.c_float, C.c_long
 SYMBOLS = {
@@ -149,6 +157,11 @@ SYMBOLS = {
     "ffn_dift_workspace_bytes": (_l, [_i, _i, _i, _i]),
     "ffn_resize_pil_bilinear_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i]),
     "ffn_resize_pil_u8": (_i, [_vp, C.POINTER(ResizePilDesc)]),
+    "ffn_resize_taps8_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ffn_resize_gather_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i]),
+    "ffn_dilate_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "ffn_mask_bbox_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    "ffn_coarse_edit_2d": (_i, [_vp, C.POINTER(CoarseEditDesc)]),
     "ffn_vit_patch_rows": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "ffn_vit_patch_rows_pair": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "ffn_image_to_nhwc": (_i, [_vp, _i, _vp, _vp, _l, _i]),

@@ -70,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 8; }      // 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
+extern "C" int ffn_version(void) { return 9; }      // 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -1268,6 +1268,67 @@ extern "C" int ffn_vit_patch_rows_pair(void* stream, const uint8_t* src, const f
     REQUIRE(aligned16(out), "vit_patch_rows_pair: out must be 16-byte aligned");
     fimgprep_patch_rows_pair(reinterpret_cast<hipStream_t>(stream), src, lut, out, B, H, W, patch, K);
     return check_launch("vit_patch_rows_pair");
+}
+
+// ---- device case preparation of the GeoBench harness (kernels: caseprep.h, launches: imgprep.hip) ---------------------------------------------------
+extern "C" __attribute__((visibility("hidden"))) void fcaseprep_taps8(hipStream_t s, const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int oh, int ow,
+                                                                      const int* iy, const double* wy, const int* ix, const double* wx);
+extern "C" __attribute__((visibility("hidden"))) void fcaseprep_gather(hipStream_t s, const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int oh, int ow,
+                                                                       const int* iy, const int* ix, int binarise);
+extern "C" __attribute__((visibility("hidden"))) void fcaseprep_dilate(hipStream_t s, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int C, int k);
+extern "C" __attribute__((visibility("hidden"))) hipError_t fcaseprep_bbox(hipStream_t s, const uint8_t* mask, int* box, int B, int H, int W, int C);
+extern "C" __attribute__((visibility("hidden"))) void fcaseprep_edit(hipStream_t s, const ffn_coarse_edit_desc* d);
+
+// the common rules of the case-preparation entries: batch, channels, one image's sides
+#define CASEPREP_IMAGE(what, B, H, W, C)                                                                                                                  \
+    do {                                                                                                                                                  \
+        REQUIRE((B) >= 1 && (B) <= 65535, what ": B=%d outside 1 .. 65535", (B));                                                                       \
+        REQUIRE((C) == 1 || (C) == 3, what ": C=%d channels (1 or 3)", (C));                                                                            \
+        REQUIRE((H) >= 1 && (W) >= 1 && (H) <= FFN_IMGPREP_MAX_SIDE && (W) <= FFN_IMGPREP_MAX_SIDE, what ": image %d x %d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE)", (H), (W), \
+                FFN_IMGPREP_MAX_SIDE);                                                                                                                    \
+    } while (0)
+
+extern "C" int ffn_resize_taps8_u8(void* stream, const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int oh, int ow, const int* iy, const double* wy,
+                                   const int* ix, const double* wx) {
+    REQUIRE(src && dst && iy && wy && ix && wx, "resize_taps8_u8: null pointer");
+    CASEPREP_IMAGE("resize_taps8_u8", B, H, W, C);
+    CASEPREP_IMAGE("resize_taps8_u8", B, oh, ow, C);
+    fcaseprep_taps8(reinterpret_cast<hipStream_t>(stream), src, dst, B, H, W, C, oh, ow, iy, wy, ix, wx);
+    return check_launch("resize_taps8_u8");
+}
+
+extern "C" int ffn_resize_gather_u8(void* stream, const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int oh, int ow, const int* iy, const int* ix, int binarise) {
+    REQUIRE(src && dst && iy && ix, "resize_gather_u8: null pointer");
+    CASEPREP_IMAGE("resize_gather_u8", B, H, W, C);
+    CASEPREP_IMAGE("resize_gather_u8", B, oh, ow, C);
+    fcaseprep_gather(reinterpret_cast<hipStream_t>(stream), src, dst, B, H, W, C, oh, ow, iy, ix, binarise);
+    return check_launch("resize_gather_u8");
+}
+
+extern "C" int ffn_dilate_u8(void* stream, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int C, int k) {
+    REQUIRE(src && dst && scratch, "dilate_u8: null pointer");
+    CASEPREP_IMAGE("dilate_u8", B, H, W, C);
+    REQUIRE(k >= 1 && k <= 255, "dilate_u8: k=%d outside 1 .. 255", k);
+    REQUIRE(dst != src && dst != scratch && scratch != src, "dilate_u8: src, scratch and dst must be three buffers");
+    fcaseprep_dilate(reinterpret_cast<hipStream_t>(stream), src, dst, scratch, B, H, W, C, k);
+    return check_launch("dilate_u8");
+}
+
+extern "C" int ffn_mask_bbox_u8(void* stream, const uint8_t* mask, int* box, int B, int H, int W, int C) {
+    REQUIRE(mask && box, "mask_bbox_u8: null pointer");
+    CASEPREP_IMAGE("mask_bbox_u8", B, H, W, C);
+    hipError_t e = fcaseprep_bbox(reinterpret_cast<hipStream_t>(stream), mask, box, B, H, W, C);
+    if (e != hipSuccess) return fail(FFN_EHIP, "mask_bbox_u8: hipMemsetAsync: %s", hipGetErrorString(e));
+    return check_launch("mask_bbox_u8");
+}
+
+extern "C" int ffn_coarse_edit_2d(void* stream, const ffn_coarse_edit_desc* d) {
+    REQUIRE(d, "coarse_edit_2d: null descriptor");
+    REQUIRE(d->src_img && d->src_mask && d->bg && d->inv && d->final_img && d->tmask && d->trans_hole, "coarse_edit_2d: null pointer");
+    CASEPREP_IMAGE("coarse_edit_2d", d->B, d->H, d->W, d->mask_c);
+    REQUIRE(!d->hole_mask || d->hole_mask_c == 1 || d->hole_mask_c == 3, "coarse_edit_2d: hole_mask_c=%d channels (1 or 3)", d->hole_mask_c);
+    fcaseprep_edit(reinterpret_cast<hipStream_t>(stream), d);
+    return check_launch("coarse_edit_2d");
 }
 
 // ---- elementwise / resampling helpers of the depth front end ----------------------------------------------------------

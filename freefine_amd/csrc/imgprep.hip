@@ -1,10 +1,12 @@
-// Fifth translation unit of libfreefine_hip.so: the device image preparation of the DINOv2 feature metrics (imgprep.h).  A unit of its own, like dift.hip, so
-// that it compiles beside capi.hip; default code generation.  capi.o validates the arguments (ffn_resize_pil_bilinear_u8, ffn_resize_pil_u8, ffn_vit_patch_rows, ffn_vit_patch_rows_pair) and calls the
-// hidden functions below; nothing here is exported.
+// Fifth translation unit of libfreefine_hip.so: the device image preparation of the DINOv2 feature metrics (imgprep.h) and the device case preparation of the
+// GeoBench harness (caseprep.h).  A unit of its own, like dift.hip, so that it compiles beside capi.hip; default code generation.  capi.o validates the arguments
+// (ffn_resize_pil_bilinear_u8, ffn_resize_pil_u8, ffn_vit_patch_rows, ffn_vit_patch_rows_pair; ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8,
+// ffn_mask_bbox_u8, ffn_coarse_edit_2d) and calls the hidden functions below; nothing here is exported.
 #include <hip/hip_runtime.h>
 
 #include "../../include/freefine_hip.h"
 #include "imgprep.h"
+#include "caseprep.h"      // last: it turns floating-point contraction off for what follows
 
 extern "C" __attribute__((visibility("hidden"))) void fimgprep_resize(hipStream_t s, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int oh, int ow,
                                                                       const int* hb, const int* hk, int hks, const int* vb, const int* vk, int vks) {
@@ -44,4 +46,41 @@ extern "C" __attribute__((visibility("hidden"))) void fimgprep_patch_rows_pair(h
     long g = (total + IMGPREP_THREADS - 1) / IMGPREP_THREADS;
     const unsigned grid = (unsigned)(g > 8192 ? 8192 : g);
     hipLaunchKernelGGL(patch_rows_pair_kernel, dim3(grid), dim3(IMGPREP_THREADS), 0, s, src, lut, static_cast<bf16*>(out), total, H, W, ps, K);
+}
+
+// ---- case preparation of the GeoBench harness (caseprep.h) -----------------------------------------------------------------------------------------
+static inline unsigned caseprep_blocks(long n) { return (unsigned)((n + CASEPREP_THREADS - 1) / CASEPREP_THREADS); }
+
+extern "C" __attribute__((visibility("hidden"))) void fcaseprep_taps8(hipStream_t s, const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int oh, int ow,
+                                                                      const int* iy, const double* wy, const int* ix, const double* wx) {
+    (void)hipGetLastError();
+    const dim3 grid(caseprep_blocks(ow), (unsigned)oh, (unsigned)B), blk(CASEPREP_THREADS);
+    if (C == 1) hipLaunchKernelGGL(lanczos8_kernel<1>, grid, blk, 0, s, src, dst, H, W, oh, ow, iy, wy, ix, wx);
+    else hipLaunchKernelGGL(lanczos8_kernel<3>, grid, blk, 0, s, src, dst, H, W, oh, ow, iy, wy, ix, wx);
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fcaseprep_gather(hipStream_t s, const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int oh, int ow,
+                                                                       const int* iy, const int* ix, int binarise) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(gather_kernel, dim3(caseprep_blocks((long)ow * C), (unsigned)oh, (unsigned)B), dim3(CASEPREP_THREADS), 0, s, src, dst, H, W, C, oh, ow, iy, ix, binarise);
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fcaseprep_dilate(hipStream_t s, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int C, int k) {
+    (void)hipGetLastError();
+    const dim3 grid(caseprep_blocks((long)W * C), (unsigned)H, (unsigned)B), blk(CASEPREP_THREADS);
+    hipLaunchKernelGGL(dilate_h_kernel, grid, blk, 0, s, src, scratch, W, C, k);
+    hipLaunchKernelGGL(dilate_v_kernel, grid, blk, 0, s, scratch, dst, H, W * C, k);
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t fcaseprep_bbox(hipStream_t s, const uint8_t* mask, int* box, int B, int H, int W, int C) {
+    (void)hipGetLastError();
+    hipError_t e = hipMemsetAsync(box, 0x80, (size_t)B * 4 * sizeof(int), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(mask_bbox_kernel, dim3((unsigned)(H < 64 ? H : 64), (unsigned)B), dim3(CASEPREP_THREADS), 0, s, mask, box, H, W, C);
+    return hipSuccess;
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fcaseprep_edit(hipStream_t s, const ffn_coarse_edit_desc* d) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(coarse_edit_kernel, dim3(caseprep_blocks(d->W), (unsigned)d->H, (unsigned)d->B), dim3(CASEPREP_THREADS), 0, s, *d);
 }

@@ -7,6 +7,9 @@ Differences from the reference driver, all outside the arithmetic of an edit:
     all_gather_object -- as the reference does -- but the process group is optional (single process when WORLD_SIZE is unset);
   * `batch` cases are edited together through FreeFine_generation_batch (the reference must use batch size 1, :170);
   * host pre-processing (PNG decode, resize, the affine coarse edit) runs in a prefetch thread so it overlaps the GPU;
+  * with device_prep=True the prefetch thread only reads and decodes files, and the resizes, the coarse edit and the dilation run on the HIP kernels of
+    csrc/caseprep.h on the consumer thread, between batches (HostPrep / DevicePrep below: the one switch every loader goes through).  The bytes are those of
+    the host path, which stays the default and the reference;
   * the reference reads `ori_mask` after using it in re_edit_2d (:196 vs :198, a NameError on the first case); here it is read first.
 """
 import os
@@ -16,7 +19,7 @@ import threading
 
 import numpy as np
 
-from src.utils.vis_utils import load_json, re_edit_2d, read_and_resize_img, read_and_resize_mask, save_img, save_json
+from src.utils.vis_utils import _imread_bgr, _resize_lanczos4, _resize_nearest, dilate_mask, load_json, re_edit_2d, save_img, save_json
 
 # the GeoBench-2D call parameters (freefine_batch_infer_2d.py:212-230)
 GEOBENCH_2D = dict(guidance_scale=7.5, eta=1.0, end_scale=0.0, end_step=50, num_step=50, start_step=35, seed=42)
@@ -63,23 +66,145 @@ class CaseList:
         return self.cases[i]
 
 
-def load_case(case, dst_base, dsize=(512, 512)):
-    """host pre-processing of one case (:187-210): inputs of FreeFine_generation"""
-    inp_bg = read_and_resize_img(osp.join(dst_base, INP_SUBDIR, str(case["da_n"]), str(case["ins_id"]), "inp_img.png"), dsize)
-    ori_img = read_and_resize_img(case["ori_img_path"], dsize)
-    ori_mask = read_and_resize_mask(case["ori_mask_path"], dsize)
-    coarse, target_mask = re_edit_2d(ori_img, ori_mask, case["edit_param"], inp_bg)[:2]
+class HostPrep:
+    """the resize / edit / dilation calls of every loader on the host: the numpy restatements of src/utils/vis_utils.py (the default, and the reference of the
+    device path).  Arrays are numpy; up / down are the identity."""
+    device = None
+
+    @staticmethod
+    def up(a):
+        return a
+
+    @staticmethod
+    def down(a):
+        return a
+
+    @staticmethod
+    def resize_img(rgb, dsize):
+        return _resize_lanczos4(rgb, dsize)
+
+    @staticmethod
+    def resize_mask(m, dsize):
+        m = _resize_nearest(m, dsize)
+        m[m > 0] = 1
+        return m
+
+    @staticmethod
+    def dilate(m, k):
+        return dilate_mask(m, k)
+
+    @staticmethod
+    def edit_2d(img, mask, edit_param, bg):
+        return re_edit_2d(img, mask, edit_param, bg)[:2]
+
+
+class DevicePrep:
+    """the same calls on the HIP kernels (freefine_amd.ops: resize_lanczos4_u8, resize_nearest_u8, dilate_u8, coarse_edit_2d), byte for byte what HostPrep gives.
+    Arrays are uint8 device tensors between up (host -> device) and down (device -> host); every call is issued on the caller's thread and current stream, so
+    it belongs on the thread that owns the device -- never on the prefetch thread."""
+
+    def __init__(self, device=None):
+        import torch
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+
+    def up(self, a):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+
+    @staticmethod
+    def down(t):
+        return t.cpu().numpy()
+
+    @staticmethod
+    def resize_img(rgb, dsize):
+        from . import ops
+        return ops.resize_lanczos4_u8(rgb, dsize)
+
+    @staticmethod
+    def resize_mask(m, dsize):
+        from . import ops
+        return ops.resize_nearest_u8(m, dsize, binarise=True)
+
+    @staticmethod
+    def dilate(m, k):
+        from . import ops
+        return ops.dilate_u8(m, k)
+
+    @staticmethod
+    def edit_2d(img, mask, edit_param, bg):
+        from . import ops
+        return ops.coarse_edit_2d(img, mask, edit_param, bg)[:2]
+
+
+def _decode_img(path):
+    """uint8 RGB [H,W,3] at the file's own size: the decode half of read_and_resize_img"""
+    return np.ascontiguousarray(_imread_bgr(path)[:, :, ::-1])
+
+
+def _decode_mask(path):
+    """uint8 [H,W,3] at the file's own size: the decode half of read_and_resize_mask"""
+    return _imread_bgr(path)
+
+
+def _prep_img(raw, dsize, prep):
+    return prep.down(prep.resize_img(prep.up(raw), dsize))
+
+
+def _prep_mask(raw, dsize, prep, dilation_factor=None, forbit_area=None):
+    """read_and_resize_mask / read_and_resize_mask_with_dilation after the decode"""
+    m = prep.resize_mask(prep.up(raw), dsize)
+    if dilation_factor is not None:
+        m = prep.dilate(m, dilation_factor)
+    m = prep.down(m)
+    if forbit_area is not None:
+        m = np.where(forbit_area, 0, m)
+    return m
+
+
+def read_case_2d(case, dst_base, dsize=(512, 512)):
+    """FILE half of load_case (reads and decodes only: safe on the prefetch thread)"""
+    return dict(_raw="2d", dsize=tuple(dsize), edit_param=case["edit_param"],
+                bg=_decode_img(osp.join(dst_base, INP_SUBDIR, str(case["da_n"]), str(case["ins_id"]), "inp_img.png")),
+                ori_img=_decode_img(case["ori_img_path"]), ori_mask=_decode_mask(case["ori_mask_path"]))
+
+
+def finish_case_2d(raw, prep=HostPrep):
+    """PREPARATION half of load_case (:187-210): two Lanczos resizes, the mask's nearest resize, the coarse edit -- on the host or, with a DevicePrep, on
+    the device (then: on the thread that owns it), where the resized images stay until the edit has used them."""
+    dsize = raw["dsize"]
+    inp_bg, ori_img = prep.resize_img(prep.up(raw["bg"]), dsize), prep.resize_img(prep.up(raw["ori_img"]), dsize)
+    ori_mask = prep.resize_mask(prep.up(raw["ori_mask"]), dsize)
+    coarse, target_mask = prep.edit_2d(ori_img, ori_mask, raw["edit_param"], inp_bg)
+    ori_img, ori_mask, coarse, target_mask = (prep.down(a) for a in (ori_img, ori_mask, coarse, target_mask))
     return dict(ori_img=ori_img, ori_mask=ori_mask, coarse_input=coarse, target_mask=target_mask, guidance_text="",
                 draw_mask=np.ones_like(ori_mask), use_auto_draw=True, reduce_inp_artifacts=True, cons_area=target_mask)
 
 
-def load_case_3d_depth(case, dst_base, dsize=(512, 512)):
-    """host pre-processing of one GeoBench-3D case (freefine_batch_infer_3d_depth.py:127-143)"""
-    coarse = read_and_resize_img(osp.join(dst_base, "coarse3d_depth_anything", str(case["da_n"]), str(case["ins_id"]), f'{case["edit_ins"]}.png'), dsize)
-    target_mask = read_and_resize_mask(case["target_mask_0"], dsize)
-    return dict(ori_img=read_and_resize_img(case["ori_img_path"], dsize), ori_mask=read_and_resize_mask(case["ori_mask_path"], dsize),
-                coarse_input=coarse, target_mask=target_mask, guidance_text=case["obj_label"],
-                draw_mask=read_and_resize_mask(case["draw_mask"], dsize), use_auto_draw=False, reduce_inp_artifacts=True, cons_area=target_mask)
+def load_case(case, dst_base, dsize=(512, 512), prep=HostPrep):
+    """pre-processing of one case (:187-210): inputs of FreeFine_generation.  = read_case_2d (files) + finish_case_2d (host or device)"""
+    return finish_case_2d(read_case_2d(case, dst_base, dsize), prep)
+
+
+def read_case_3d_depth(case, dst_base, dsize=(512, 512)):
+    """FILE half of load_case_3d_depth"""
+    return dict(_raw="3d_depth", dsize=tuple(dsize), guidance_text=case["obj_label"],
+                coarse=_decode_img(osp.join(dst_base, "coarse3d_depth_anything", str(case["da_n"]), str(case["ins_id"]), f'{case["edit_ins"]}.png')),
+                target_mask=_decode_mask(case["target_mask_0"]), ori_img=_decode_img(case["ori_img_path"]), ori_mask=_decode_mask(case["ori_mask_path"]),
+                draw_mask=_decode_mask(case["draw_mask"]))
+
+
+def finish_case_3d_depth(raw, prep=HostPrep):
+    """PREPARATION half of load_case_3d_depth (freefine_batch_infer_3d_depth.py:127-143): resizes only"""
+    dsize = raw["dsize"]
+    target_mask = _prep_mask(raw["target_mask"], dsize, prep)
+    return dict(ori_img=_prep_img(raw["ori_img"], dsize, prep), ori_mask=_prep_mask(raw["ori_mask"], dsize, prep),
+                coarse_input=_prep_img(raw["coarse"], dsize, prep), target_mask=target_mask, guidance_text=raw["guidance_text"],
+                draw_mask=_prep_mask(raw["draw_mask"], dsize, prep), use_auto_draw=False, reduce_inp_artifacts=True, cons_area=target_mask)
+
+
+def load_case_3d_depth(case, dst_base, dsize=(512, 512), prep=HostPrep):
+    """pre-processing of one GeoBench-3D case (freefine_batch_infer_3d_depth.py:127-143)"""
+    return finish_case_3d_depth(read_case_3d_depth(case, dst_base, dsize), prep)
 
 
 def monocular_depth(img, depth_model, translate_factor=0.0, side=518):
@@ -106,17 +231,29 @@ def monocular_depth(img, depth_model, translate_factor=0.0, side=518):
     return d.clamp_min(0).cpu().numpy().astype(np.float32)
 
 
-def read_case_3d_rgb(case, dst_base, dsize=(512, 512)):
-    """HOST half of the 3d_rgb loader (files only: safe on the prefetch thread): image, mask, inpainted background, edit parameters"""
-    return dict(_raw_3d_rgb=True, ori_img=read_and_resize_img(case["ori_img_path"], dsize), ori_mask=read_and_resize_mask(case["ori_mask_path"], dsize),
-                bg=read_and_resize_img(osp.join(dst_base, INP_SUBDIR, str(case["da_n"]), str(case["ins_id"]), "inp_img.png"), dsize),
-                edit_param=[float(v) for v in case["edit_param"]], obj_label=case.get("obj_label", ""), dsize=tuple(dsize))
+def read_case_3d_rgb(case, dst_base, dsize=(512, 512), prep=HostPrep):
+    """HOST half of the 3d_rgb loader (files only: safe on the prefetch thread): image, mask, inpainted background, edit parameters.  prep=None: decode only,
+    the three resizes are left to finish_case_3d_rgb (the device_prep route, where they run on the device)."""
+    raw = dict(_raw_3d_rgb=True, ori_img=_decode_img(case["ori_img_path"]), ori_mask=_decode_mask(case["ori_mask_path"]),
+               bg=_decode_img(osp.join(dst_base, INP_SUBDIR, str(case["da_n"]), str(case["ins_id"]), "inp_img.png")),
+               edit_param=[float(v) for v in case["edit_param"]], obj_label=case.get("obj_label", ""), dsize=tuple(dsize), _resized=False)
+    return raw if prep is None else _resize_case_3d_rgb(raw, prep)
 
 
-def finish_case_3d_rgb(raw, depth_model, focal_length=550.0):
+def _resize_case_3d_rgb(raw, prep):
+    if raw.get("_resized", True):
+        return raw
+    dsize = raw["dsize"]
+    return dict(raw, _resized=True, ori_img=_prep_img(raw["ori_img"], dsize, prep), ori_mask=_prep_mask(raw["ori_mask"], dsize, prep),
+                bg=_prep_img(raw["bg"], dsize, prep))
+
+
+def finish_case_3d_rgb(raw, depth_model, focal_length=550.0, prep=HostPrep):
     """DEVICE half of the 3d_rgb loader (depth network + point-cloud warp on the HIP kernels): call it on the thread that owns the device
-    and the stream -- geobench.run does so on its consumer thread, between batches, never concurrently with a graph capture."""
+    and the stream -- geobench.run does so on its consumer thread, between batches, never concurrently with a graph capture.  A raw case that was only
+    decoded (read_case_3d_rgb(prep=None)) is resized here first, through `prep`."""
     from . import warp3d
+    raw = _resize_case_3d_rgb(raw, prep)
     assert depth_model is not None, "the 3d_rgb variant needs a depth model (freefine_amd.depth.HipDepthAnything or depth_anything.dpt.DepthAnything)"
     ori_img, ori_mask, bg, dsize = raw["ori_img"], raw["ori_mask"], raw["bg"], raw["dsize"]
     depth = monocular_depth(ori_img, depth_model, translate_factor=0.1)      # this variant's own choice: no point of the cloud at z = 0
@@ -206,9 +343,11 @@ def warm_and_sync(model, batch, params, dsize=(512, 512), variant="2d", src=0):
     return FD.sync_tune_table(src)
 
 
-def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True, verbose=True, dsize=(512, 512), variant="2d", depth_model=None):
+def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True, verbose=True, dsize=(512, 512), variant="2d", depth_model=None,
+        device_prep=False):
     """edit every case of the variant's annotation file that this rank owns; rank 0 writes the variant's result JSON
     (2d: annotations_2d.json -> generated_results_freefine_2d.json; 3d_depth: annotations.json -> generated_results_freefine_depth.json).
+    device_prep: the prefetch thread only reads and decodes; resizes and the coarse edit run on the device (DevicePrep) on this thread, between batches.
     Returns the merged result list (on every rank)."""
     from . import dist as FD
     V = VARIANTS[variant]
@@ -248,12 +387,21 @@ def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True
 
     # the prefetch thread is HOST-ONLY (file reads, resizes): a new Python thread starts on device 0 with its own current stream, and device
     # work issued from it would also race the consumer's graph captures; the 3d_rgb variant's depth network + warp run HERE, per case
-    loader = {"2d": load_case, "3d_depth": load_case_3d_depth, "3d_rgb": read_case_3d_rgb}[variant]
+    # device_prep: the same rule -- the thread decodes files (read_case_*), the resizes / coarse edit run HERE through a DevicePrep
+    if device_prep:
+        prep = DevicePrep(getattr(model, "device", None))
+        loader = {"2d": read_case_2d, "3d_depth": read_case_3d_depth, "3d_rgb": lambda c, b, d: read_case_3d_rgb(c, b, d, prep=None)}[variant]
+    else:
+        prep = HostPrep
+        loader = {"2d": load_case, "3d_depth": load_case_3d_depth, "3d_rgb": read_case_3d_rgb}[variant]
     try:
         for case, inputs, err in _prefetch(mine, dst_base, 2 * batch, dsize, loader):
-            if err is None and inputs.get("_raw_3d_rgb"):
+            if err is None and (inputs.get("_raw_3d_rgb") or inputs.get("_raw")):
                 try:
-                    inputs = finish_case_3d_rgb(inputs, depth_model)
+                    if inputs.get("_raw_3d_rgb"):
+                        inputs = finish_case_3d_rgb(inputs, depth_model, prep=prep)
+                    else:
+                        inputs = {"2d": finish_case_2d, "3d_depth": finish_case_3d_depth}[inputs["_raw"]](inputs, prep)
                 except Exception as e:  # noqa: BLE001 -- reported with the case attached, like a failed read
                     err = e
             if err is not None:
@@ -321,14 +469,22 @@ def blend_with_original(ori_img, hole_mask, generated):
     return (ori_img * (1 - mask_np) + generated * mask_np).astype(generated.dtype)
 
 
+def bggen_inputs(group, dsize=(512, 512), prep=HostPrep):
+    """the two reads of run_bggen for one group of cases: (images, hole masks) = read_and_resize_img, read_and_resize_mask_with_dilation(dilation_factor=30)"""
+    imgs = [_prep_img(_decode_img(c["ori_img_path"]), dsize, prep) for c in group]
+    holes = [_prep_mask(_decode_mask(c["ori_mask_path"]), dsize, prep, dilation_factor=30) for c in group]
+    return imgs, holes
+
+
 def run_bggen(model, dst_base, blending=True, params=None, rank=0, world=1, check_exist=True, verbose=True, dsize=(512, 512), seed=None,
-              batch=4, bench="2D"):
+              batch=4, bench="2D", device_prep=False):
     """remove the annotated object of every (image, instance) with FreeFine_background_generation (model must carry the bg-gen hook:
-    register_attention_control_4bggen), `batch` cases per UNet batch.  seed=None draws a fresh seed per case like the reference (:162)."""
+    register_attention_control_4bggen), `batch` cases per UNet batch.  seed=None draws a fresh seed per case like the reference (:162).
+    device_prep: the Lanczos resize, the mask's nearest resize and its k = 30 dilation run on the device (DevicePrep) instead of the host."""
     import random
     from PIL import Image
-    from src.utils.vis_utils import read_and_resize_mask_with_dilation
     from . import dist as FD
+    prep = DevicePrep(getattr(model, "device", None)) if device_prep else HostPrep
     params = dict(GEOBENCH_BGGEN, **(params or {}))
     # bench = "2D" | "3D": annotations_2d.json -> Geo-Bench-2D/..., annotations_3d.json -> Geo-Bench-3D/... (freefine_batch_infer_bggen_3d.py)
     ann = f"annotations_{bench.lower()}.json"
@@ -344,8 +500,7 @@ def run_bggen(model, dst_base, blending=True, params=None, rank=0, world=1, chec
               verbose=False)
     for b0 in range(0, len(mine), batch):
         group = mine[b0:b0 + batch]
-        imgs = [read_and_resize_img(c["ori_img_path"], dsize) for c in group]
-        holes = [read_and_resize_mask_with_dilation(c["ori_mask_path"], dsize, dilation_factor=30, forbit_area=None) for c in group]
+        imgs, holes = bggen_inputs(group, dsize, prep)
         seeds = [(random.randint(0, 10 ** 16) if seed is None else seed) % (2 ** 63) for _ in group]
         if len(group) == 1:
             gens = [model.FreeFine_background_generation(imgs[0], holes[0], params["guidance_text"], params["guidance_scale"], params["eta"],

@@ -1241,6 +1241,170 @@ def resize_pil_u8(img, oh, ow, filter, crop=None, keep=None, out=None, scratch=N
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# device case preparation of the GeoBench harness (csrc/caseprep.h): the cv2 restatements of src/utils/vis_utils.py, byte for byte what the numpy functions
+# give.  Like them, the interpolating paths are pinned to the numpy restatement, not to OpenCV.  Tables are built on the host in float64.
+# ---------------------------------------------------------------------------------------------------------------
+def lanczos4_taps(n_dst, n_src):
+    """(idx int32 [n_dst, 8], wgt float64 [n_dst, 8]): the taps of cv2's INTER_LANCZOS4 exactly as src.utils.vis_utils._lanczos4_matrix computes them before it
+    scatters them into a dense matrix -- 8 taps around floor(x), x = (d + 0.5) * scale - 0.5, kernel sinc(t) sinc(t / 4), normalised, indices clamped."""
+    import numpy as np
+    scale = n_src / n_dst
+    x = (np.arange(n_dst) + 0.5) * scale - 0.5
+    x0 = np.floor(x).astype(np.int64)
+    fx = x - x0
+    taps = np.arange(-3, 5)
+    t = fx[:, None] - taps[None, :]
+    wgt = np.sinc(t) * np.sinc(t / 4.0)
+    wgt /= wgt.sum(axis=1, keepdims=True)
+    idx = np.clip(x0[:, None] + taps[None, :], 0, n_src - 1)
+    return np.ascontiguousarray(idx.astype(np.int32)), np.ascontiguousarray(wgt)
+
+
+def nearest_indices(n_dst, n_src):
+    """int32 [n_dst]: the source index of cv2's INTER_NEAREST as src.utils.vis_utils._resize_nearest computes it: min(int(d * n_src / n_dst), n_src - 1)"""
+    import numpy as np
+    return np.minimum((np.arange(n_dst) * (n_src / n_dst)).astype(np.int64), n_src - 1).astype(np.int32)
+
+
+_CASEPREP_DEV = {}
+
+
+def _caseprep_tables_dev(kind, n_dst, n_src, device):
+    key = (kind, int(n_dst), int(n_src), torch.device(device))
+    hit = _CASEPREP_DEV.get(key)
+    if hit is None:
+        if len(_CASEPREP_DEV) > 64:
+            _CASEPREP_DEV.clear()
+        tabs = lanczos4_taps(n_dst, n_src) if kind == "lanczos4" else (nearest_indices(n_dst, n_src),)
+        hit = _CASEPREP_DEV[key] = tuple(torch.from_numpy(t).to(device) for t in tabs)
+    return hit
+
+
+def _as_bhwc(img):
+    """uint8 [H, W], [H, W, C] or [B, H, W, C] (device, contiguous) -> (B, H, W, C)"""
+    assert img.dtype == torch.uint8 and img.ndim in (2, 3, 4) and img.is_contiguous()
+    if img.ndim == 2:
+        return (1,) + tuple(img.shape) + (1,)
+    return ((1,) if img.ndim == 3 else ()) + tuple(img.shape)
+
+
+def resize_lanczos4_u8(img, dsize):
+    """src.utils.vis_utils._resize_lanczos4 on the device, byte for byte: uint8 [H, W, C] or [B, H, W, C], C in (1, 3); dsize = (w, h) like cv2
+    (ffn_resize_taps8_u8).  Equal sizes: a copy."""
+    lib = L.load()
+    assert img.ndim in (3, 4)
+    B, H, W, C = _as_bhwc(img)
+    ow, oh = int(dsize[0]), int(dsize[1])
+    if (H, W) == (oh, ow):
+        return img.clone()
+    iy, wy = _caseprep_tables_dev("lanczos4", oh, H, img.device)
+    ix, wx = _caseprep_tables_dev("lanczos4", ow, W, img.device)
+    out = torch.empty(tuple(img.shape[:-3]) + (oh, ow, C), dtype=torch.uint8, device=img.device)
+    L.check(_timed("resize_taps8_u8", 128.0 * B * oh * ow * C, float(C) * B * (H * W + oh * ow),
+                   lambda: lib.ffn_resize_taps8_u8(_stream(), img.data_ptr(), out.data_ptr(), B, H, W, C, oh, ow, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(),
+                                                   wx.data_ptr())), "ffn_resize_taps8_u8")
+    return out
+
+
+def resize_nearest_u8(img, dsize, binarise=False):
+    """src.utils.vis_utils._resize_nearest on the device: uint8 [H, W], [H, W, C] or [B, H, W, C]; dsize = (w, h).  binarise: nonzero bytes become 1, the
+    m[m > 0] = 1 of read_and_resize_mask (ffn_resize_gather_u8)."""
+    lib = L.load()
+    B, H, W, C = _as_bhwc(img)
+    ow, oh = int(dsize[0]), int(dsize[1])
+    iy, = _caseprep_tables_dev("nearest", oh, H, img.device)
+    ix, = _caseprep_tables_dev("nearest", ow, W, img.device)
+    shape = (oh, ow) if img.ndim == 2 else tuple(img.shape[:-3]) + (oh, ow, C)
+    out = torch.empty(shape, dtype=torch.uint8, device=img.device)
+    L.check(_timed("resize_gather_u8", 0.0, 2.0 * C * B * oh * ow,
+                   lambda: lib.ffn_resize_gather_u8(_stream(), img.data_ptr(), out.data_ptr(), B, H, W, C, oh, ow, iy.data_ptr(), ix.data_ptr(), int(bool(binarise)))),
+            "ffn_resize_gather_u8")
+    return out
+
+
+def dilate_u8(mask, k):
+    """src.utils.vis_utils.dilate_mask on the device: the k x k maximum with anchor k // 2, zeros outside; uint8 [H, W], [H, W, C] or [B, H, W, C] (ffn_dilate_u8)"""
+    lib = L.load()
+    B, H, W, C = _as_bhwc(mask)
+    out, scratch = torch.empty_like(mask), torch.empty_like(mask)
+    L.check(_timed("dilate_u8", 0.0, 4.0 * C * B * H * W,
+                   lambda: lib.ffn_dilate_u8(_stream(), mask.data_ptr(), out.data_ptr(), scratch.data_ptr(), B, H, W, C, int(k))), "ffn_dilate_u8")
+    return out
+
+
+def mask_bbox_u8(mask):
+    """int64 numpy [B, 4] = (top, bottom, left, right) of the pixels whose channel 0 is nonzero, mask uint8 [B, H, W] or [B, H, W, C] on the device
+    (ffn_mask_bbox_u8: one reduction, 16 bytes per case read back -- this call synchronises).  ValueError on an empty mask, like numpy's ys.min()."""
+    lib = L.load()
+    assert mask.dtype == torch.uint8 and mask.ndim in (3, 4) and mask.is_contiguous()
+    B, H, W = mask.shape[:3]
+    C = 1 if mask.ndim == 3 else mask.shape[3]
+    box = torch.empty((B, 4), dtype=torch.int32, device=mask.device)
+    L.check(_timed("mask_bbox_u8", 0.0, float(B) * H * W, lambda: lib.ffn_mask_bbox_u8(_stream(), mask.data_ptr(), box.data_ptr(), B, H, W, C)), "ffn_mask_bbox_u8")
+    b = box.cpu().numpy().astype("int64")
+    if (b[:, 1] < 0).any():
+        raise ValueError("zero-size array to reduction operation minimum which has no identity (empty mask)")
+    b[:, 0] *= -1
+    b[:, 2] *= -1
+    return b
+
+
+def edit_inverse_affine(box, edit_param):
+    """float64 [6]: rows 0 and 1 of the inverse of the forward matrix src.utils.vis_utils._affine_for_edit builds from the mask's bounding box
+    (top, bottom, left, right) and edit_param = (dx, dy, rz, sx, sy) or the 9-tuple (dx, dy, dz, rx, ry, rz, sx, sy, sz); inverted as _warp_affine does."""
+    import numpy as np
+    if len(edit_param) == 9:
+        dx, dy, _, _, _, rz, sx, sy, _ = edit_param
+    else:
+        dx, dy, rz, sx, sy = edit_param
+    top, bottom, left, right = (np.int64(v) for v in box)
+    cx, cy = (right + left) / 2, (top + bottom) / 2
+    a = np.deg2rad(-rz)                                       # _rotation_matrix_2d((cx, cy), -rz, 1)
+    al, be = 1 * np.cos(a), 1 * np.sin(a)
+    M = np.array([[al, be, (1 - al) * cx - be * cy], [-be, al, be * cx + (1 - al) * cy]], dtype=np.float64)
+    M[0, 2] += dx + (1 - sx) * cx
+    M[1, 2] += dy + (1 - sy) * cy
+    M[0, 0] *= sx
+    M[1, 1] *= sy
+    return np.ascontiguousarray(np.linalg.inv(np.vstack([M, [0, 0, 1]]))[:2].reshape(6))
+
+
+def coarse_edit_2d(src_img, src_mask, edit_param, inp_cur, hole_img=None, hole_mask=None):
+    """src.utils.vis_utils.re_edit_2d (hole_img / hole_mask None) or re_edit_3d (the other view's image and mask given) on the device, byte for byte
+    (ffn_coarse_edit_2d).  uint8 device tensors: src_img, inp_cur, hole_img [H, W, 3]; src_mask [H, W] or [H, W, 3] (channel 0 is used, any nonzero value is
+    set); hole_mask [H, W], [H, W, 1] or [H, W, 3] (per channel, numpy's broadcast).  Batched: a leading dimension on every tensor and a list of edit_params.
+    The mask's bounding box comes from a device reduction with one 16-byte read-back per case; the matrix is inverted on the host in float64.
+    -> (final, target mask in {0, 255}, trans_hole).  ValueError on an empty mask, before the edit kernel is launched."""
+    import numpy as np
+    lib = L.load()
+    batched = src_img.ndim == 4
+    if not batched:
+        src_img, src_mask, inp_cur = src_img[None], src_mask[None], inp_cur[None]
+        hole_img = None if hole_img is None else hole_img[None]
+        hole_mask = None if hole_mask is None else hole_mask[None]
+        edit_param = [edit_param]
+    B, H, W = src_img.shape[:3]
+    assert len(edit_param) == B and (hole_img is None) == (hole_mask is None)
+    for t in (src_img, inp_cur, hole_img):
+        assert t is None or (t.dtype == torch.uint8 and tuple(t.shape) == (B, H, W, 3) and t.is_contiguous() and t.device == src_img.device)
+    for t in (src_mask, hole_mask):
+        assert t is None or (t.dtype == torch.uint8 and t.ndim in (3, 4) and tuple(t.shape[:3]) == (B, H, W) and t.is_contiguous() and t.device == src_img.device)
+    boxes = mask_bbox_u8(src_mask)
+    inv = torch.from_numpy(np.stack([edit_inverse_affine(boxes[b], edit_param[b]) for b in range(B)])).to(src_img.device)
+    final, trans_hole = torch.empty_like(src_img), torch.empty_like(src_img)
+    tmask = torch.empty((B, H, W), dtype=torch.uint8, device=src_img.device)
+    d = L.CoarseEditDesc()
+    d.src_img, d.src_mask, d.bg, d.inv = src_img.data_ptr(), src_mask.data_ptr(), inp_cur.data_ptr(), inv.data_ptr()
+    d.hole_img, d.hole_mask = (None if hole_img is None else hole_img.data_ptr()), (None if hole_mask is None else hole_mask.data_ptr())
+    d.final_img, d.tmask, d.trans_hole = final.data_ptr(), tmask.data_ptr(), trans_hole.data_ptr()
+    d.B, d.H, d.W = B, H, W
+    d.mask_c = 1 if src_mask.ndim == 3 else src_mask.shape[3]
+    d.hole_mask_c = 1 if hole_mask is None or hole_mask.ndim == 3 else hole_mask.shape[3]
+    L.check(_timed("coarse_edit_2d", 0.0, 14.0 * B * H * W, lambda: lib.ffn_coarse_edit_2d(_stream(), CT.byref(d))), "ffn_coarse_edit_2d")
+    return (final, tmask, trans_hole) if batched else (final[0], tmask[0], trans_hole[0])
+
+
 def vit_norm_table(mean, std):
     """[3, 256] fp32: ToTensor + Normalize(mean, std) of every byte value per channel, evaluated by the very torch expressions the transform runs on an image
     (float32(byte) / 255, then in place - float32(mean[c]), / float32(std[c])) -- the kernel only looks values up."""

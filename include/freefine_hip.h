@@ -444,6 +444,59 @@ typedef struct {
 } ffn_resize_pil_desc;
 int ffn_resize_pil_u8(void* stream, const ffn_resize_pil_desc* d);
 
+/* ---- device case preparation of the GeoBench harness (ABI version 9; csrc/caseprep.h) ------------------------------------------------------------
+ * Reference: the cv2 restatements of src/utils/vis_utils.py (_resize_lanczos4, _resize_nearest, dilate_mask, re_edit_2d / re_edit_3d), which stay the
+ * reference: every entry gives the bytes the numpy function gives.  Like the numpy functions, the interpolating paths are pinned to that restatement, NOT to
+ * OpenCV (whose 8-bit paths use fixed-point coefficient tables).  Images are [B][H][W][C] uint8, contiguous, any byte alignment, C in {1, 3}, 1 <= B <= 65535,
+ * sides 1 .. FFN_IMGPREP_MAX_SIDE; null pointers and anything outside these limits are refused with FFN_EINVAL before any launch.  All floating point is fp64
+ * with contraction off: every product and every sum below is rounded on its own.
+ *
+ * ffn_resize_taps8_u8: an 8-tap separable resize (cv2.INTER_LANCZOS4 as _lanczos4_matrix states it).  Tables built by the caller on the host in float64
+ * (freefine_amd.ops.lanczos4_taps): iy [oh][8] / ix [ow][8] int32 source indices, already clamped to the border (the kernel clamps again), wy [oh][8] /
+ * wx [ow][8] fp64 weights, already normalised.  v[y][X][c] = sum_j wy[y][j] * src[iy[y][j]][X][c]; out[y][x][c] = sum_j wx[x][j] * v[y][ix[x][j]][c]; each
+ * sum starts at 0 and adds its taps in ascending j; then rint (round half to even) and clamp to 0 .. 255.  v is recomputed per output pixel: no scratch.
+ * Equal source and destination size is the caller's plain copy (the tables of that case are not the identity).
+ *
+ * ffn_resize_gather_u8: dst[y][x][c] = src[iy[y]][ix[x]][c] through two int32 tables (cv2.INTER_NEAREST: min(int(d * src / dst), src - 1) in float64, built
+ * by the caller; clamped again by the kernel).  binarise != 0: every nonzero byte is written as 1 (the m[m > 0] = 1 of read_and_resize_mask).
+ *
+ * ffn_dilate_u8: the k x k maximum with anchor k / 2 (cv2.dilate(ones(k, k)) = scipy.ndimage.maximum_filter(size = (k, k), mode = "constant", cval = 0)):
+ * 1 <= k <= 255, separable, scratch is a uint8 image of the source's size; the window of output x covers inputs x - k / 2 .. x + k - k / 2 - 1 (for even k one
+ * more to the left than to the right); pixels outside the image read as 0.  dst may not alias src or scratch.
+ *
+ * ffn_mask_bbox_u8: box [B][4] int32 = (-top, bottom, -left, right): the first / last row and column of mask [B][H][W][C] whose CHANNEL 0 is nonzero -- the
+ * bounding box _affine_for_edit takes from np.where.  An empty mask leaves bottom < 0.  The launch presets box (hipMemsetAsync), then reduces with integer
+ * atomics.  The caller reads 16 bytes per case back.
+ *
+ * ffn_coarse_edit_2d: re_edit_2d / re_edit_3d in one kernel.  inv [B][6] fp64 on the device: rows 0 and 1 (a00 a01 a02 / a10 a11 a12) of the INVERSE affine,
+ * computed by the caller as _warp_affine does (np.linalg.inv of the matrix of _affine_for_edit).  Per destination pixel (x, y):
+ *   sx = (a00 x + a01 y) + a02, sy = (a10 x + a11 y) + a12        in this bracketing
+ *   target mask = 255 iff src_mask[floor(sy + 0.5)][floor(sx + 0.5)] channel 0 is nonzero (0 outside the source), else 0
+ *   q = floor(s * 32 + 0.5) / 32 per axis, (x0, y0) = floor(q), (fx, fy) = q - floor(q); four taps, a tap outside the source is 0;
+ *   warped = rint((t00 (1 - fx) + t01 fx)(1 - fy) + (t10 (1 - fx) + t11 fx) fy), round half to even (the blend is exact: 8 x 5 x 5 bits)
+ *   final = target ? warped : bg;   trans_hole = target ? warped : (hole_mask ? 0 : hole_img)
+ * src_img, bg, hole_img, final_img, trans_hole: [B][H][W][3]; src_mask [B][H][W][mask_c], channel 0 read; tmask [B][H][W].  hole_img null: src_img;
+ * hole_mask null: src_mask's channel 0; else hole_mask [B][H][W][hole_mask_c], with 3 channels applied per channel (numpy's broadcast in re_edit_3d).
+ * The warped image and the warped mask are never written to memory.  Outputs may not alias inputs. */
+typedef struct {
+    const uint8_t* src_img;
+    const uint8_t* src_mask;
+    const uint8_t* bg;
+    const uint8_t* hole_img;
+    const uint8_t* hole_mask;
+    const double* inv;
+    uint8_t* final_img;
+    uint8_t* tmask;
+    uint8_t* trans_hole;
+    int B, H, W, mask_c, hole_mask_c;
+} ffn_coarse_edit_desc;
+int ffn_resize_taps8_u8(void* stream, const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int oh, int ow, const int* iy, const double* wy, const int* ix,
+                        const double* wx);
+int ffn_resize_gather_u8(void* stream, const uint8_t* src, uint8_t* dst, int B, int H, int W, int C, int oh, int ow, const int* iy, const int* ix, int binarise);
+int ffn_dilate_u8(void* stream, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int C, int k);
+int ffn_mask_bbox_u8(void* stream, const uint8_t* mask, int* box, int B, int H, int W, int C);
+int ffn_coarse_edit_2d(void* stream, const ffn_coarse_edit_desc* d);
+
 #ifdef __cplusplus
 }
 #endif
