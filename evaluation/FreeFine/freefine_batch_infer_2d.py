@@ -31,7 +31,12 @@ def main():
     ap.add_argument("--depth-model", default="synthetic:vitl", help="3d_rgb: a Depth-Anything state dict (.pth) or synthetic:<vits|vitb|vitl>")
     ap.add_argument("--device-prep", action="store_true", help="resize and coarse-edit every case on the device (csrc/caseprep.h) instead of in numpy on the host: "
                                                                "the same bytes, the prefetch thread only decodes the PNG files")
+    ap.add_argument("--save-correspondence", action="store_true",
+                    help="3d_rgb: also write every case's correspondence map (Geo-Bench-3D/correspondence/<da>/<ins>/<edit>.npy, where Mean Distance looks "
+                         "for it) and the visibility image beside it (Geo-Bench-3D/correspondence_visible/...png)")
     args = ap.parse_args()
+    if args.save_correspondence and args.variant != "3d_rgb":
+        ap.error("--save-correspondence needs --variant 3d_rgb (the other variants do not build the warp)")
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank, local = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local)
@@ -61,7 +66,7 @@ def main():
             dcfg = FDp.depth_config({384: "vits", 768: "vitb", 1024: "vitl"}[dstate["pretrained.cls_token"].shape[-1]])
         depth_model = FDp.HipDepthAnything(dcfg, dstate, dtype=dtype, device=device)
     geobench.run(model, args.base_dir, batch=args.batch, rank=rank, world=world, variant=args.variant, depth_model=depth_model,
-                 device_prep=args.device_prep)
+                 device_prep=args.device_prep, save_correspondence=args.save_correspondence)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -3,7 +3,7 @@
     python evaluation/metrics/main.py --path <generated_results.json> [--task 100111111] [--level 0..3] [--no_rotate] [--3d]
            [--use_relative_path --base_dir <GeoBenchMeta>] [--fid_path <real images>] [--gen_img_key gen_img_path]
            [--clip_weights <file>] [--dino_weights <file>] [--dinov2_weights <file>] [--model <SD folder | synthetic:sd21-base>] [--precision f32|x3]
-           [--hps_weights <file> --hps_tokenizer <folder>]
+           [--hps_weights <file> --hps_tokenizer <folder>] [--md_visible_only]
 
 --task is nine digits (1 = compute): FID, IRS, HPS, BGC, SUBC, WRAP_E, MD, FID_DINO, FID_KD.  The reference downloads its extractors (clip.load, torch.hub); there
 is no download here, the weights are local files: --clip_weights (CLIP ViT-B/32: a transformers CLIPVisionModelWithProjection state dict or the OpenAI
@@ -12,7 +12,11 @@ checkpoint's visual.* names), --dino_weights (dino_vitb16), --dinov2_weights (di
 or transformers' CLIPModel layout) and --hps_tokenizer a folder with CLIP's vocab.json and merges.txt (HPS: OpenCLIP ViT-H/14, freefine_amd/hps.py).  FID
 (Inception-v3 needs torchvision) and IRS (ImageReward and BLIP) need packages that are not installed, so there is nothing to pin an implementation to: they are
 reported as `not built`, and the other metrics still run.  A metric whose weights were not given is reported as such, likewise.  --precision is the arithmetic of the networks: f32 (default: exact-fp32 MFMA) or x3 (split-bf16: hi + lo bf16 operand pairs, fp32
-accumulation; the ViT towers, HPS's two among them, are built with x3=True and the MD pipeline with from_pretrained(..., x3=True))."""
+accumulation; the ViT towers, HPS's two among them, are built with x3=True and the MD pipeline with from_pretrained(..., x3=True)).
+For an edit that is neither a translation, a 2-D rotation nor a uniform scale, MD reads the case's correspondence map: <tree>/correspondence/<da>/<ins>/<edit>.npy
+beside the folder of generated images (the 3d_rgb variant of evaluation/FreeFine/freefine_batch_infer_2d.py writes it with --save-correspondence).
+--md_visible_only (an extension of the reference's metric, off by default: values compare with the reference's only without it) drops the keypoints the
+sibling correspondence_visible/....png marks as hidden in the coarse edit."""
 import argparse
 import json
 import os
@@ -89,6 +93,8 @@ def main(argv=None):
     ap.add_argument("--hps_weights", default=None, help="HPS_v2.1_compressed.pt: OpenCLIP ViT-H/14 weights, open_clip or transformers layout (HPS)")
     ap.add_argument("--hps_tokenizer", default=None, help="folder with CLIP's vocab.json and merges.txt (HPS)")
     ap.add_argument("--precision", default="f32", choices=("f32", "x3"), help="arithmetic of the networks: f32 = exact fp32, x3 = split-bf16")
+    ap.add_argument("--md_visible_only", action="store_true", help="MD: drop keypoints hidden in the coarse 3-D edit (needs correspondence_visible images; "
+                                                                   "not the reference's metric)")
     ap.add_argument("--clip_config", default="vitb32", help=argparse.SUPPRESS)        # "tiny": the test sizes
     ap.add_argument("--dino_config", default="vitb16", help=argparse.SUPPRESS)
     ap.add_argument("--hps_config", default="vith14", choices=("vith14", "tiny"), help=argparse.SUPPRESS)      # with "tiny", --hps_tokenizer bytes: text.ByteTokenizer
@@ -134,7 +140,8 @@ def main(argv=None):
             if not args.model:
                 return "not run (--model missing)"
             from freefine_amd.pipeline import FreeFinePipeline
-            return FM.calculate_md(data, label, FreeFinePipeline.from_pretrained(args.model, torch_dtype=torch.float32, device=torch.device("cuda:0"), x3=x3))
+            return FM.calculate_md(data, label, FreeFinePipeline.from_pretrained(args.model, torch_dtype=torch.float32, device=torch.device("cuda:0"), x3=x3),
+                                   visible_only=args.md_visible_only)
         if not args.dinov2_weights or not args.fid_path:
             return "not run (--dinov2_weights or --fid_path missing)"
         return (FM.calculate_fid_dino if name == "FID_DINO" else FM.calculate_fid_kd)(data, label, args.fid_path, dinov2(), x3=x3)

@@ -70,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 9; }      // 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
+extern "C" int ffn_version(void) { return 10; }      // 10: the correspondence map of the point-cloud warp (ffn_splat_ids, ffn_splat_correspond); 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -1663,4 +1663,25 @@ extern "C" int ffn_splat_render(void* stream, const float* proj, const float* rg
     else if (K <= 16) LAUNCH(splat_render_kernel<16>, dim3(tiles), dim3(256), 0, s, proj, rgb, offs, list, radius, K, W, H, image, idx_sum, covered);
     else LAUNCH(splat_render_kernel<32>, dim3(tiles), dim3(256), 0, s, proj, rgb, offs, list, radius, K, W, H, image, idx_sum, covered);
     return check_launch("splat_render");
+}
+extern "C" int ffn_splat_ids(void* stream, const float* proj, const int* offs, const int* list, float radius, int K, int W, int H, int* ids) {
+    REQUIRE(proj && offs && list && ids, "splat_ids: null operand");
+    REQUIRE(K >= 1 && K <= 32, "splat_ids: points per pixel K=%d out of range (1 .. 32)", K);
+    REQUIRE(W > 0 && H > 0 && radius > 0.f, "splat_ids: bad shape / radius");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int tiles = ((W + 15) / 16) * ((H + 15) / 16);
+    if (K <= 8) LAUNCH(splat_ids_kernel<8>, dim3(tiles), dim3(256), 0, s, proj, offs, list, radius, K, W, H, ids);
+    else if (K <= 16) LAUNCH(splat_ids_kernel<16>, dim3(tiles), dim3(256), 0, s, proj, offs, list, radius, K, W, H, ids);
+    else LAUNCH(splat_ids_kernel<32>, dim3(tiles), dim3(256), 0, s, proj, offs, list, radius, K, W, H, ids);
+    return check_launch("splat_ids");
+}
+extern "C" int ffn_splat_correspond(void* stream, const float* proj, const int* idx, int n, int W, int H, const int* ids, int K, float* map,
+                                    uint8_t* visible) {
+    REQUIRE(proj && idx && map, "splat_correspond: null operand");
+    REQUIRE(!visible || ids, "splat_correspond: the visibility output needs the ids of ffn_splat_ids");
+    REQUIRE(n >= 0 && W > 0 && H > 0 && (long)W * H < (1l << 31), "splat_correspond: bad shape");
+    REQUIRE(K >= 1 && K <= 32, "splat_correspond: points per pixel K=%d out of range (1 .. 32)", K);
+    if (n == 0) return FFN_OK;
+    LAUNCH(splat_correspond_kernel, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), proj, idx, n, W, H, ids, K, map, visible);
+    return check_launch("splat_correspond");
 }

@@ -17,6 +17,10 @@
 // disc's bounding box touches (two launches around one exclusive scan), then one workgroup per tile streams its list through LDS in chunks
 // of 256 points while each lane keeps the top-K of ITS pixel in registers (fully unrolled compare-exchange chain: no dynamic register
 // indexing).  HBM-bound in the points (16 B each, read once per touched tile); the compare chain is the issue cost.
+//
+// Correspondence (what Mean Distance reads for a 3-D edit; the reference's step 2 writes it, evaluation/FreeFine/get_3d_transform_correspondence.py): the same
+// tiles and the same selection routine (splat_select_topk) write the K point ids of every pixel instead of compositing them (splat_ids_kernel), and one lane
+// per point turns its projection into the continuous pixel it was drawn at and looks itself up among the ids of the nearest pixel (splat_correspond_kernel).
 #pragma once
 #include "common.h"
 
@@ -93,27 +97,18 @@ __global__ __launch_bounds__(256) void splat_bin_kernel(const float* __restrict_
     }
 }
 
-// one workgroup per tile, one lane per pixel
+// The top-K selection both tile kernels below run (one routine: render's compositing and ids' write-out cannot drift): the workgroup streams its
+// tile's list through LDS in chunks of 256 points; each lane keeps the K covering points of smallest depth of ITS pixel (xf, yf), ties by point id,
+// in qz / qd (squared distance) / qi (point id; 0x7fffffff = empty slot), sorted.  Called by all 256 lanes of the workgroup (barriers inside).
 template <int KMAX>
-__global__ __launch_bounds__(256) void splat_render_kernel(const float* __restrict__ proj, const float* __restrict__ rgb, const int* __restrict__ offs,
-                                                           const int* __restrict__ list, float radius, int K, int W, int H,
-                                                           float* __restrict__ image, int* __restrict__ idx_sum, uint8_t* __restrict__ covered) {
-    __shared__ f32x4 s_pt[256];
-    const int TW = (W + 15) >> 4;
-    const int tile = blockIdx.x, ty = tile / TW, tx = tile - ty * TW;
-    const int row = ty * 16 + (threadIdx.x >> 4), col = tx * 16 + (threadIdx.x & 15);
-    const bool live = row < H && col < W;
-    const float xf = splat_pix_to_ndc(W - 1 - col, W, H), yf = splat_pix_to_ndc(H - 1 - row, H, W);
-    const float r2 = radius * radius;
-    float qz[KMAX], qd[KMAX];
-    int qi[KMAX];
+__device__ __forceinline__ void splat_select_topk(const float* __restrict__ proj, const int* __restrict__ list, int beg, int end, int K, bool live,
+                                                  float xf, float yf, float r2, f32x4* s_pt, float (&qz)[KMAX], float (&qd)[KMAX], int (&qi)[KMAX]) {
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
         qz[k] = __builtin_inff();
         qd[k] = 0.f;
         qi[k] = 0x7fffffff;
     }
-    const int beg = offs[tile], end = offs[tile + 1];
     for (int base = beg; base < end; base += 256) {
         const int m = end - base < 256 ? end - base : 256;
         __syncthreads();
@@ -146,6 +141,23 @@ __global__ __launch_bounds__(256) void splat_render_kernel(const float* __restri
             }
         }
     }
+}
+
+// one workgroup per tile, one lane per pixel
+template <int KMAX>
+__global__ __launch_bounds__(256) void splat_render_kernel(const float* __restrict__ proj, const float* __restrict__ rgb, const int* __restrict__ offs,
+                                                           const int* __restrict__ list, float radius, int K, int W, int H,
+                                                           float* __restrict__ image, int* __restrict__ idx_sum, uint8_t* __restrict__ covered) {
+    __shared__ f32x4 s_pt[256];
+    const int TW = (W + 15) >> 4;
+    const int tile = blockIdx.x, ty = tile / TW, tx = tile - ty * TW;
+    const int row = ty * 16 + (threadIdx.x >> 4), col = tx * 16 + (threadIdx.x & 15);
+    const bool live = row < H && col < W;
+    const float xf = splat_pix_to_ndc(W - 1 - col, W, H), yf = splat_pix_to_ndc(H - 1 - row, H, W);
+    const float r2 = radius * radius;
+    float qz[KMAX], qd[KMAX];
+    int qi[KMAX];
+    splat_select_topk<KMAX>(proj, list, offs[tile], offs[tile + 1], K, live, xf, yf, r2, s_pt, qz, qd, qi);
     if (!live) return;
     float cum = 1.f, o0 = 0.f, o1 = 0.f, o2 = 0.f;
     int sum = 0;
@@ -173,4 +185,61 @@ __global__ __launch_bounds__(256) void splat_render_kernel(const float* __restri
     image[3 * o + 2] = o2;
     idx_sum[o] = sum;
     covered[o] = any ? 1 : 0;
+}
+
+// ids[H][W][K]: the point ids splat_render_kernel composites at each pixel, in compositing order (depth, ties by id); -1 = empty slot.  Same tiling,
+// same selection routine; the K registers are written out by an unrolled chain (no dynamic register indexing).
+template <int KMAX>
+__global__ __launch_bounds__(256) void splat_ids_kernel(const float* __restrict__ proj, const int* __restrict__ offs, const int* __restrict__ list,
+                                                        float radius, int K, int W, int H, int* __restrict__ ids) {
+    __shared__ f32x4 s_pt[256];
+    const int TW = (W + 15) >> 4;
+    const int tile = blockIdx.x, ty = tile / TW, tx = tile - ty * TW;
+    const int row = ty * 16 + (threadIdx.x >> 4), col = tx * 16 + (threadIdx.x & 15);
+    const bool live = row < H && col < W;
+    const float xf = splat_pix_to_ndc(W - 1 - col, W, H), yf = splat_pix_to_ndc(H - 1 - row, H, W);
+    const float r2 = radius * radius;
+    float qz[KMAX], qd[KMAX];
+    int qi[KMAX];
+    splat_select_topk<KMAX>(proj, list, offs[tile], offs[tile + 1], K, live, xf, yf, r2, s_pt, qz, qd, qi);
+    if (!live) return;
+    int* o = ids + ((long)row * W + col) * K;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+        if (k < K) o[k] = qi[k] == 0x7fffffff ? -1 : qi[k];
+}
+
+// The correspondence map of the warp (the reference's step 2 writes one per case, evaluation/FreeFine/get_3d_transform_correspondence.py:21-54;
+// Mean Distance reads it, mean_distance.py:108,122): map[idx[p]] = the continuous target pixel (x, y) = (W - 1 - u, H - 1 - v) of source pixel
+// idx[p], with u, v the inverse of splat_pix_to_ndc exactly as splat_tile_box writes it -- a point drawn on a pixel centre maps to that pixel's
+// integer coordinates.  NaN for points the renderer does not draw (behind the camera / not finite).  visible[idx[p]] = 1 iff the point's nearest
+// pixel lies inside the image and p is among that pixel's K ids (it contributes to the rendered image where it lands).  One lane per point, one
+// writer per source pixel; pixels idx does not name are left as the host filled them.
+__global__ __launch_bounds__(256) void splat_correspond_kernel(const float* __restrict__ proj, const int* __restrict__ idx, int n, int W, int H,
+                                                               const int* __restrict__ ids, int K, float* __restrict__ map,
+                                                               uint8_t* __restrict__ visible) {
+    float rx = 2.f, ry = 2.f;
+    if (W > H) rx = ((float)W / (float)H) * 2.f;
+    if (H > W) ry = ((float)H / (float)W) * 2.f;
+    const float ox = rx * 0.5f, oy = ry * 0.5f;
+    const int HW = W * H;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < n; p += gridDim.x * 256) {
+        const int f = idx[p];
+        if (f < 0 || f >= HW) continue;                      // not a pixel of this image: nothing of the caller's is written
+        const f32x4 a = *reinterpret_cast<const f32x4*>(proj + 4l * p);
+        float x = __builtin_nanf(""), y = __builtin_nanf("");
+        bool vis = false;
+        if (a[2] >= 0.f && fabsf(a[0]) < 1e30f && fabsf(a[1]) < 1e30f) {
+            const float u = ((a[0] + ox) * (float)W - ox) / rx, v = ((a[1] + oy) * (float)H - oy) / ry;
+            x = (float)(W - 1) - u;
+            y = (float)(H - 1) - v;
+            const float cf = floorf(x + 0.5f), rf = floorf(y + 0.5f);
+            if (visible && cf >= 0.f && cf < (float)W && rf >= 0.f && rf < (float)H) {
+                const int* q = ids + ((long)(int)rf * W + (int)cf) * K;
+                for (int k = 0; k < K; ++k) vis = vis || q[k] == p;
+            }
+        }
+        *reinterpret_cast<f32x2_t*>(map + 2l * f) = f32x2_t{x, y};
+        if (visible) visible[f] = vis ? 1 : 0;
+    }
 }

@@ -19,7 +19,7 @@ import threading
 
 import numpy as np
 
-from src.utils.vis_utils import _imread_bgr, _resize_lanczos4, _resize_nearest, dilate_mask, load_json, re_edit_2d, save_img, save_json
+from src.utils.vis_utils import _imread_bgr, _resize_lanczos4, _resize_nearest, dilate_mask, load_json, re_edit_2d, save_img, save_json, save_mask
 
 # the GeoBench-2D call parameters (freefine_batch_infer_2d.py:212-230)
 GEOBENCH_2D = dict(guidance_scale=7.5, eta=1.0, end_scale=0.0, end_step=50, num_step=50, start_step=35, seed=42)
@@ -248,10 +248,12 @@ def _resize_case_3d_rgb(raw, prep):
                 bg=_prep_img(raw["bg"], dsize, prep))
 
 
-def finish_case_3d_rgb(raw, depth_model, focal_length=550.0, prep=HostPrep):
+def finish_case_3d_rgb(raw, depth_model, focal_length=550.0, prep=HostPrep, correspondence=False):
     """DEVICE half of the 3d_rgb loader (depth network + point-cloud warp on the HIP kernels): call it on the thread that owns the device
     and the stream -- geobench.run does so on its consumer thread, between batches, never concurrently with a graph capture.  A raw case that was only
-    decoded (read_case_3d_rgb(prep=None)) is resized here first, through `prep`."""
+    decoded (read_case_3d_rgb(prep=None)) is resized here first, through `prep`.  correspondence (off: today's keys only): the dict also carries
+    `correspondence` (float32 [H, W, 2], (x, y): where the warp sent every source pixel) and `correspondence_visible` (uint8 [H, W] x 255) of
+    warp3d.coarse_edit_3d -- not inputs of the edit: run() takes them out and saves them."""
     from . import warp3d
     raw = _resize_case_3d_rgb(raw, prep)
     assert depth_model is not None, "the 3d_rgb variant needs a depth model (freefine_amd.depth.HipDepthAnything or depth_anything.dpt.DepthAnything)"
@@ -261,11 +263,17 @@ def finish_case_3d_rgb(raw, depth_model, focal_length=550.0, prep=HostPrep):
     sc = dsize[0] / 512.0                                    # edit_param translations are pixels at the 512 reference size
     tf = [ep[0] * sc, ep[1] * sc, ep[2] * sc, ep[3], ep[4], ep[5], ep[6], ep[7], ep[8]]
     m2 = ori_mask if ori_mask.ndim == 2 else ori_mask[:, :, 0]
-    coarse, target_mask = warp3d.coarse_edit_3d(ori_img, m2, depth, tf, bg, focal_length=focal_length * dsize[0] / 512.0)
+    extra = {}
+    if correspondence:
+        coarse, target_mask, corr, visible = warp3d.coarse_edit_3d(ori_img, m2, depth, tf, bg, focal_length=focal_length * dsize[0] / 512.0,
+                                                                   return_correspondence=True)
+        extra = dict(correspondence=corr, correspondence_visible=visible)
+    else:
+        coarse, target_mask = warp3d.coarse_edit_3d(ori_img, m2, depth, tf, bg, focal_length=focal_length * dsize[0] / 512.0)
     draw = ndimage_max(np.maximum(target_mask, (m2 > 0).astype(np.uint8) * 255), 9)
     return dict(ori_img=ori_img, ori_mask=ori_mask, coarse_input=coarse, target_mask=target_mask, guidance_text=raw["obj_label"],
                 draw_mask=(draw > 0).astype(np.uint8), use_auto_draw=False, reduce_inp_artifacts=True,
-                cons_area=np.maximum(target_mask, (m2 > 0).astype(np.uint8) * 255))
+                cons_area=np.maximum(target_mask, (m2 > 0).astype(np.uint8) * 255), **extra)
 
 
 def load_case_3d_rgb(case, dst_base, dsize=(512, 512), depth_model=None, focal_length=550.0):
@@ -344,12 +352,18 @@ def warm_and_sync(model, batch, params, dsize=(512, 512), variant="2d", src=0):
 
 
 def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True, verbose=True, dsize=(512, 512), variant="2d", depth_model=None,
-        device_prep=False):
+        device_prep=False, save_correspondence=False):
     """edit every case of the variant's annotation file that this rank owns; rank 0 writes the variant's result JSON
     (2d: annotations_2d.json -> generated_results_freefine_2d.json; 3d_depth: annotations.json -> generated_results_freefine_depth.json).
     device_prep: the prefetch thread only reads and decodes; resizes and the coarse edit run on the device (DevicePrep) on this thread, between batches.
+    save_correspondence (variant 3d_rgb only): every case's correspondence map and visibility image are written under <dst_base>/Geo-Bench-3D/
+    (warp3d.save_correspondence: correspondence/<da>/<ins>/<edit>.npy -- the path metrics.calculate_md derives from the case's gen_img_path -- and
+    correspondence_visible/...png) on this thread, next to where the result is saved.
     Returns the merged result list (on every rank)."""
     from . import dist as FD
+    from . import warp3d
+    if save_correspondence and variant != "3d_rgb":
+        raise ValueError(f"save_correspondence: only the 3d_rgb variant builds its own warp (variant = {variant!r})")
     V = VARIANTS[variant]
     params = dict(V["params"], **(params or {}))
     seed = params.pop("seed")
@@ -370,6 +384,7 @@ def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True
             return
         cases = [p[0] for p in pending]
         inputs = [p[1] for p in pending]
+        maps = [(i.pop("correspondence", None), i.pop("correspondence_visible", None)) for i in inputs]      # not inputs of the edit
         if len(inputs) == 1:
             kw = {k: v for k, v in inputs[0].items() if k not in ("ori_img", "ori_mask", "coarse_input", "target_mask", "guidance_text")}
             imgs = [model.FreeFine_generation(inputs[0]["ori_img"], inputs[0]["ori_mask"], inputs[0]["coarse_input"], inputs[0]["target_mask"],
@@ -380,8 +395,10 @@ def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True
             imgs = model.FreeFine_generation_batch(inputs, params["guidance_scale"], params["eta"], end_step=params["end_step"],
                                                    num_step=params["num_step"], start_step=params["start_step"], seeds=seed,
                                                    end_scale=params["end_scale"], verbose=False)
-        for c, img in zip(cases, imgs):
+        for c, img, (corr, visible) in zip(cases, imgs, maps):
             path = save_img(img, dst_gen, c["da_n"], c["ins_id"], c["edit_ins"])
+            if corr is not None:
+                warp3d.save_correspondence(osp.dirname(dst_gen), c["da_n"], c["ins_id"], c["edit_ins"], corr, visible)
             results.append(dict(c, gen_img_path=path, key=f'{c["da_n"]}/{c["ins_id"]}/{c["edit_ins"]}'))
         pending.clear()
 
@@ -399,7 +416,7 @@ def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True
             if err is None and (inputs.get("_raw_3d_rgb") or inputs.get("_raw")):
                 try:
                     if inputs.get("_raw_3d_rgb"):
-                        inputs = finish_case_3d_rgb(inputs, depth_model, prep=prep)
+                        inputs = finish_case_3d_rgb(inputs, depth_model, prep=prep, correspondence=save_correspondence)
                     else:
                         inputs = {"2d": finish_case_2d, "3d_depth": finish_case_3d_depth}[inputs["_raw"]](inputs, prep)
                 except Exception as e:  # noqa: BLE001 -- reported with the case attached, like a failed read
@@ -426,6 +443,44 @@ def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True
         if verbose:
             print(f"Total images processed: {len(final)}")
     return merged
+
+
+def prepare_3d(dst_base, depth_model, rank=0, world=1, dsize=(512, 512), check_exist=True, verbose=True):
+    """Step 2 of the 3-D run without the diffusion edit (run_script_3D.sh "Step2", evaluation/FreeFine/get_3d_transform_correspondence.py:207-289): for
+    every case of annotations.json that this rank owns (sharded like run) the coarse image Geo-Bench-3D/coarse3d_depth_anything_rgb/<da>/<ins>/<edit>.png,
+    the target mask Geo-Bench-3D/mesh_mask/... and the correspondence map (warp3d.save_correspondence: Geo-Bench-3D/correspondence/....npy and
+    correspondence_visible/....png).  A case whose three files exist is skipped (check_exist).  A NON-PARITY EXTENSION, not a restatement of the
+    dataset's generator, in the words of load_case_3d_rgb: the reference renders these files through the GeoDiffuser warp, whose modules are not in the
+    reference tree (hence the folder's own name: coarse3d_depth_anything is the dataset's); its md_mask is not written.  -> the list of
+    dict(key, coarse_input_path, target_mask_path, correspondence_path) this rank wrote."""
+    from . import dist as FD
+    from . import warp3d
+    root = osp.join(dst_base, "Geo-Bench-3D")
+    coarse_dir, mask_dir = osp.join(root, "coarse3d_depth_anything_rgb"), osp.join(root, "mesh_mask")
+    data = load_json(osp.join(dst_base, VARIANTS["3d_rgb"]["annotations"]))
+    if data is None:
+        raise FileNotFoundError(osp.join(dst_base, VARIANTS["3d_rgb"]["annotations"]))
+    cl = CaseList(data, coarse_dir, check_exist=False)
+    done = []
+    for i in FD.shard_indices(len(cl), rank, world):
+        c = cl[i]
+        sub = (str(c["da_n"]), str(c["ins_id"]), f'{c["edit_ins"]}')
+        paths = [osp.join(coarse_dir, *sub) + ".png", osp.join(mask_dir, *sub) + ".png", osp.join(root, "correspondence", *sub) + ".npy"]
+        if check_exist and all(osp.exists(p) for p in paths):
+            continue
+        try:
+            inputs = finish_case_3d_rgb(read_case_3d_rgb(c, dst_base, dsize), depth_model, correspondence=True)
+        except Exception as e:  # noqa: BLE001 -- reported with the case attached, like run
+            if verbose:
+                print(f'[geobench] skipped {"/".join(sub)}: {e}')
+            continue
+        save_img(inputs["coarse_input"], coarse_dir, *sub)
+        save_mask(inputs["target_mask"] > 0, mask_dir, *sub)
+        warp3d.save_correspondence(root, *sub, inputs["correspondence"], inputs["correspondence_visible"])
+        done.append(dict(key="/".join(sub), coarse_input_path=paths[0], target_mask_path=paths[1], correspondence_path=paths[2]))
+    if verbose:
+        print(f"[geobench] prepare_3d: {len(done)} cases written")
+    return done
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -325,7 +325,8 @@ def transform_coordinates(edit_param, size, mask, path_3D=None):
     """mean_distance.py:get_transform_coordinates (:81-108): [size[0], size[1], 2] float64, where the edit should have moved every pixel (row, col).  Quirks kept:
     the translation branch (edit_param[0] = dx or edit_param[1] = dy non-zero) is (row + dy, col + dx); the rotation (edit_param[5], degrees) / uniform scale
     (edit_param[6] == edit_param[7]) branch works about scipy.ndimage.center_of_mass(mask), a (row, col) pair passed UNCHANGED as the centre of a matrix that
-    is applied to (row, col, 1) points; otherwise the correspondence file `path_3D` (.npy) with its last axis reversed.  The rotation matrix is
+    is applied to (row, col, 1) points; otherwise the correspondence file `path_3D` (.npy, [size[0], size[1], 2] with last axis (x, y): warp3d.save_correspondence
+    writes it) with its last axis reversed -- a map of another size raises ValueError (it was an IndexError or a silently wrong lookup).  The rotation matrix is
     cv2.getRotationMatrix2D as restated by src/utils/vis_utils.py::_rotation_matrix_2d (pinned to that formula only: no cv2 here to record a golden)."""
     if edit_param[0] != 0 or edit_param[1] != 0:
         rows, cols = np.meshgrid(np.arange(size[0]), np.arange(size[1]), indexing="ij")
@@ -343,7 +344,11 @@ def transform_coordinates(edit_param, size, mask, path_3D=None):
         rows, cols = np.meshgrid(np.arange(size[0]), np.arange(size[1]), indexing="ij")
         points = np.stack((rows, cols, np.ones_like(rows)), axis=-1).reshape(-1, 3)
         return np.dot(points, matrix.T).reshape(size[0], size[1], 2)
-    return np.load(path_3D)[..., ::-1].copy()
+    corr = np.load(path_3D)
+    if corr.ndim != 3 or tuple(corr.shape[:2]) != (int(size[0]), int(size[1])) or corr.shape[2] != 2:
+        raise ValueError(f"{path_3D}: the correspondence map is {corr.shape[0]} x {corr.shape[1]} (shape {corr.shape}), the source image "
+                         f"{size[0]} x {size[1]}: a map describes the image it was made from, pixel by pixel")
+    return corr[..., ::-1].copy()
 
 
 def default_keypoints(mask, max_points=30):
@@ -357,26 +362,37 @@ def default_keypoints(mask, max_points=30):
     return pts[::step]
 
 
-def mean_distance(featurizer, src_img, gen_img, mask, edit_param, prompt, keypoints, path_3D=None, max_points=30, **featurizer_kw):
+def mean_distance(featurizer, src_img, gen_img, mask, edit_param, prompt, keypoints, path_3D=None, max_points=30, visible=None, **featurizer_kw):
     """One case of mean_distance.py:calculate_md (:119-165) -> the list of distances of its keypoints.  src_img / gen_img: uint8 HWC arrays; mask: HW array in
     [0, 255]; keypoints: [[row, col], ...] on the source image (the first max_points are used).  The generated image and the mask are resized to the source
     size with PIL BILINEAR and the mask divided by 255 (the reference passes shape[:-1] = (H, W) where PIL wants (W, H): the same for the square images of
     GeoBench; here the source size is meant).  featurizer: freefine_amd.dift.HipSDFeaturizer; featurizer_kw (t, up_ft_index, ensemble_size, noise,
     noise_edited, generator) go to its pair().  Per keypoint: the best cosine match of the source feature among the edited image's features, both upsampled
-    bilinearly to the image size (ops.dift_match), and its distance to where the edit should have moved the keypoint."""
+    bilinearly to the image size (ops.dift_match), and its distance to where the edit should have moved the keypoint.  Keypoints whose target is not finite
+    (a correspondence map holds NaN where the warp drew nothing) are dropped.  visible (extension, None = the reference's metric): an [H, W] array of the
+    source image's size; keypoints on its zero pixels are dropped BEFORE the max_points cut."""
     from PIL import Image
     from . import ops
     src_img = np.asarray(src_img)
     H, W = src_img.shape[:2]
     gen_img = np.array(Image.fromarray(np.asarray(gen_img)).resize((W, H), Image.BILINEAR))
     mask = np.array(Image.fromarray(np.asarray(mask)).resize((W, H), Image.BILINEAR)) / 255.0
-    kps = np.asarray(keypoints(src_img, gen_img, mask) if callable(keypoints) else keypoints).reshape(-1, 2)[:max_points].astype(np.int64)
+    kps = np.asarray(keypoints(src_img, gen_img, mask) if callable(keypoints) else keypoints).reshape(-1, 2).astype(np.int64)
+    if visible is not None:
+        visible = np.asarray(visible)
+        if visible.shape[:2] != (H, W):
+            raise ValueError(f"the visibility image is {visible.shape[0]} x {visible.shape[1]}, the source image {H} x {W}")
+        kps = kps[visible.reshape(H, W, -1)[kps[:, 0], kps[:, 1], 0] > 0]
+    kps = kps[:max_points]
+    if len(kps) == 0:
+        return []
+    t_coords = transform_coordinates(edit_param, (H, W), mask, path_3D)
+    kps = kps[np.isfinite(t_coords[kps[:, 0], kps[:, 1]]).all(-1)]
     if len(kps) == 0:
         return []
     rows_s, rows_e, hw = featurizer.pair(src_img, gen_img, prompt, **featurizer_kw)
     rc, _ = ops.dift_match(rows_s, rows_e, hw, (H, W), kps)
     rc = rc.cpu().numpy()
-    t_coords = transform_coordinates(edit_param, (H, W), mask, path_3D)
     out = []
     for k, m in zip(kps, rc):
         d = (t_coords[k[0], k[1]] - m.astype(np.float64)).astype(np.float32)      # (tp - max_rc).float().norm()
@@ -384,12 +400,26 @@ def mean_distance(featurizer, src_img, gen_img, mask, edit_param, prompt, keypoi
     return out
 
 
-def calculate_md(data, image_label, pipe, keypoints=None, reader=None, max_points=30, **featurizer_kw):
+def correspondence_path(gen_path):
+    """Where the reference looks for the correspondence file of a generated image (mean_distance.py:121-122): <tree>/<results folder>/<da>/<ins>/<edit>.png ->
+    <tree>/correspondence/<da>/<ins>/<edit>.npy (every occurrence of the folder's name is replaced, and "zkl" by "Hszhu", as there).  None for a path with
+    fewer than four components.  warp3d.save_correspondence(<tree>, ...) writes that file."""
+    parts = str(gen_path).split("/")
+    if len(parts) < 4 or not parts[-4]:
+        return None
+    return str(gen_path).replace("zkl", "Hszhu").replace(parts[-4], "correspondence").replace(".png", ".npy")
+
+
+def calculate_md(data, image_label, pipe, keypoints=None, reader=None, max_points=30, visible_only=False, **featurizer_kw):
     """mean_distance.py:calculate_md over a GeoBench result tree data[image]["instances"][instance][sample] with ori_img_path / <image_label> / ori_mask_path /
     edit_param / obj_label (the prompt) -> the mean distance over all keypoints of all cases.  pipe: a FreeFinePipeline (its checkpoint is the feature
     extractor: freefine_amd/dift.py states the two deviations from the reference's SDFeaturizer) or a ready HipSDFeaturizer.  keypoints: a callable
     (src_img, gen_img, mask / 255) -> [[row, col], ...]; None -> the sample's own "keypoints" list when it has one, else default_keypoints(mask).  MD values are
-    comparable to the reference's only when the reference's keypoints are supplied.  `reader` maps a path to an array (default: PIL)."""
+    comparable to the reference's only when the reference's keypoints are supplied.  `reader` maps a path to an array (default: PIL).
+    visible_only (extension of the reference's metric, default off; values compare with the reference's only when it is off): where the sibling
+    `correspondence_visible/....png` of a case's correspondence file exists (warp3d.save_correspondence writes it), keypoints that are not visible in the
+    coarse edit -- self-occluded points have no counterpart in the edited image -- are dropped before the max_points cut."""
+    import os
     from .dift import HipSDFeaturizer
     if reader is None:
         from PIL import Image
@@ -400,12 +430,15 @@ def calculate_md(data, image_label, pipe, keypoints=None, reader=None, max_point
         for instance in image["instances"].values():
             for sample in instance.values():
                 gen_path = sample[image_label]
-                parts = str(gen_path).split("/")
-                # the correspondence file of a 3-D edit, where the reference looks for it (mean_distance.py:121-122)
-                path_3D = str(gen_path).replace("zkl", "Hszhu").replace(parts[-4], "correspondence").replace(".png", ".npy") if len(parts) >= 4 and parts[-4] else None
+                path_3D = correspondence_path(gen_path)          # the correspondence file of a 3-D edit, where the reference looks for it
                 kp = keypoints
                 if kp is None:
                     kp = sample["keypoints"] if "keypoints" in sample else (lambda s, g, m: default_keypoints(m, max_points))
+                visible = None
+                if visible_only and path_3D is not None:
+                    q = path_3D.split("/")
+                    vis_path = "/".join(q[:-4] + ["correspondence_visible"] + q[-3:])[:-len(".npy")] + ".png"
+                    visible = reader(vis_path) if os.path.exists(vis_path) else None
                 dists += mean_distance(feat, reader(sample["ori_img_path"]), reader(gen_path), reader(sample["ori_mask_path"]), sample["edit_param"],
-                                       sample["obj_label"], kp, path_3D, max_points, **featurizer_kw)
+                                       sample["obj_label"], kp, path_3D, max_points, visible=visible, **featurizer_kw)
     return float(np.mean(np.asarray(dists, dtype=np.float32))) if dists else float("nan")

@@ -265,7 +265,17 @@ int ffn_resize_bilinear(void* stream, int dtype, const void* x, void* y, int B, 
  *                      whose bounding box touches the tile; fill = 1 writes the point ids to list[offs[tile] + k] (counts = zeroed cursor,
  *                      offs = exclusive scan of the counting pass with the total at offs[tiles])
  *   ffn_splat_render   image[H][W][3] (fp32, composited colours), idx_sum[H][W] (sum of the K point ids, -1 per empty slot: what the
- *                      reference's mask test reads, geo_utils.py:517) and covered[H][W] (any point)  (geo_utils.py:482-517) */
+ *                      reference's mask test reads, geo_utils.py:517) and covered[H][W] (any point)  (geo_utils.py:482-517)
+ *   ffn_splat_ids      (ABI version 10, with ffn_splat_correspond)  ids[H][W][K] (int32): the ids of the points ffn_splat_render composites at each pixel, in compositing order (depth, ties
+ *                      by id), -1 per empty slot -- pytorch3d's `fragments.idx` (geo_utils.py:491), from the same selection routine as the render
+ *   ffn_splat_correspond  the correspondence map of the warp (evaluation/FreeFine/get_3d_transform_correspondence.py:21-54 writes one per
+ *                      case; Mean Distance reads it, evaluation/metrics/mean_distance.py:108,122): map[H][W][2] (fp32) receives, for source pixel
+ *                      idx[p], the continuous target pixel (x, y) the renderer draws point p at (a point drawn on a pixel centre: that pixel's
+ *                      integer coordinates); NaN in both for a point with !(z >= 0) or non-finite NDC.  Pixels idx does not name are not
+ *                      touched (the host pre-fills them).  visible[H][W] (uint8; may be NULL, and then ids may be NULL too): source pixel
+ *                      idx[p] gets 1 iff the point's nearest pixel (floor(y + 0.5), floor(x + 0.5)) lies inside the image and p is among
+ *                      that pixel's K ids, else 0.  n = 0 is a no-op.  Both: no allocation, no sync, the caller's stream; FFN_EINVAL before
+ *                      any launch on a null required pointer, n < 0, W / H <= 0 or K outside 1 .. 32 */
 typedef struct ffn_splat_xform {
     float center[3], translate[3], rotate[9] /* row-major, applied as p . R */, scale[3];
     float tan_half_fov;
@@ -275,6 +285,8 @@ int ffn_splat_project(void* stream, const float* pts, float* proj, int n, const 
 int ffn_splat_bin(void* stream, int fill, const float* proj, int n, float radius, int W, int H, int* counts, const int* offs, int* list);
 int ffn_splat_render(void* stream, const float* proj, const float* rgb, const int* offs, const int* list, float radius, int K, int W, int H,
                      float* image, int* idx_sum, uint8_t* covered);
+int ffn_splat_ids(void* stream, const float* proj, const int* offs, const int* list, float radius, int K, int W, int H, int* ids);
+int ffn_splat_correspond(void* stream, const float* proj, const int* idx, int n, int W, int H, const int* ids, int K, float* map, uint8_t* visible);
 
 /* ---- normalisation ------------------------------------------------------------------------------------------- */
 /* `silu` of ffn_groupnorm / ffn_gn_apply is a flag word: FFN_NORM_SILU applies SiLU; FFN_NORM_OUT_PAIR (fp32 input only) writes y as the
