@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("FREEFINE_HIP_LIB") or os.path.join(_HERE, "libfreefin
 FFN_F32, FFN_BF16, FFN_BF16X3, FFN_FP8 = 0, 1, 2, 3
 IG_OUT_SILU, IG_OUT_F32, IG_GEGLU, IG_OUT_TRANSPOSED, IG_OUT_PAIR, IG_OUT_GELU, IG_OUT_RELU, IG_OUT_KV64 = 1, 2, 4, 8, 16, 32, 64, 128
 IG_OUT_QGELU = 256
-ELT_RELU, ELT_ADD = 0, 1
+ELT_RELU, ELT_ADD, ELT_GELU = 0, 1, 2
 ATT_MAXP, ATT_MAXB = 4, 16
 ATT_HEAD_RULE, ATT_UNIFORM_SEL1, ATT_UNIFORM_SEL0, ATT_CAUSAL = 1, 2, 4, 8
 NORM_SILU, NORM_OUT_PAIR = 1, 2
@@ -166,6 +166,10 @@ SYMBOLS = {
     "ffn_coarse_edit_2d": (_i, [_vp, C.POINTER(CoarseEditDesc)]),
     "ffn_vit_patch_rows": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "ffn_vit_patch_rows_pair": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "ffn_sam_patch_rows": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ffn_sam_patch_rows_pair": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "ffn_hyper_masks": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "ffn_upsample_bicubic": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "ffn_image_to_nhwc": (_i, [_vp, _i, _vp, _vp, _l, _i]),
     "ffn_nhwc_to_image": (_i, [_vp, _i, _vp, _vp, _i, _i, _i]),
 }

@@ -70,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 10; }      // 10: the correspondence map of the point-cloud warp (ffn_splat_ids, ffn_splat_correspond); 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
+extern "C" int ffn_version(void) { return 11; }      // 11: click-to-mask (ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic, FFN_ELT_GELU); 10: the correspondence map of the point-cloud warp (ffn_splat_ids, ffn_splat_correspond); 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -1331,10 +1331,68 @@ extern "C" int ffn_coarse_edit_2d(void* stream, const ffn_coarse_edit_desc* d) {
     return check_launch("coarse_edit_2d");
 }
 
+// ---- click-to-mask: image preparation, mask product, bicubic upsampling (kernels: sam.h, launches: imgprep.hip) -----------------------------------
+extern "C" __attribute__((visibility("hidden"))) void fsam_patch_rows(hipStream_t s, int dtype, const uint8_t* src, void* out, int B, int H, int W, int side, int ps, int ldo,
+                                                                      const float* mean, const float* std);
+extern "C" __attribute__((visibility("hidden"))) void fsam_patch_rows_pair(hipStream_t s, const uint8_t* src, void* out, int B, int H, int W, int side, int ps, int K,
+                                                                           const float* mean, const float* std);
+extern "C" __attribute__((visibility("hidden"))) void fsam_hyper_masks(hipStream_t s, const float* up, const float* hyper, float* out, int N, int hw, int C, int M);
+extern "C" __attribute__((visibility("hidden"))) void fsam_bicubic(hipStream_t s, const float* src, float* dst, uint8_t* mask, int N, int h, int w, int H, int W);
+
+// the common rules of the two patch-row entries
+#define SAM_PATCH_ROWS(what, cols)                                                                                                                        \
+    do {                                                                                                                                                  \
+        const int lim = FFN_IMGPREP_MAX_SIDE;                                                                                                             \
+        REQUIRE(src && out && mean && std, what ": null pointer");                                                                                       \
+        REQUIRE(B >= 1 && H >= 1 && W >= 1 && H <= lim && W <= lim, what ": bad shape B=%d, %d x %d (sides 1 .. %d, FFN_IMGPREP_MAX_SIDE)", B, H, W, lim); \
+        REQUIRE(side >= 1 && side <= lim, what ": side=%d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE)", side, lim);                                           \
+        REQUIRE(patch >= 1 && patch <= 256 && side % patch == 0, what ": side %d is not whole patches of %d (1 .. 256)", side, patch);                   \
+        REQUIRE((cols) >= 3 * patch * patch, what ": %d columns below the %d of a patch", (cols), 3 * patch * patch);                                    \
+        REQUIRE(std[0] > 0.f && std[1] > 0.f && std[2] > 0.f, what ": std must be positive");                                                            \
+    } while (0)
+
+extern "C" int ffn_sam_patch_rows(void* stream, int dtype, const uint8_t* src, void* out, int B, int H, int W, int side, int patch, int ldo, const float* mean,
+                                  const float* std) {
+    REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16, "sam_patch_rows: bad dtype %d", dtype);
+    SAM_PATCH_ROWS("sam_patch_rows", ldo);
+    fsam_patch_rows(reinterpret_cast<hipStream_t>(stream), dtype, src, out, B, H, W, side, patch, ldo, mean, std);
+    return check_launch("sam_patch_rows");
+}
+
+extern "C" int ffn_sam_patch_rows_pair(void* stream, const uint8_t* src, void* out, int B, int H, int W, int side, int patch, int K, const float* mean, const float* std) {
+    SAM_PATCH_ROWS("sam_patch_rows_pair", K);
+    REQUIRE(K % 8 == 0, "sam_patch_rows_pair: K=%d is not a multiple of 8 (16-byte stores of both halves)", K);
+    REQUIRE(aligned16(out), "sam_patch_rows_pair: out must be 16-byte aligned");
+    fsam_patch_rows_pair(reinterpret_cast<hipStream_t>(stream), src, out, B, H, W, side, patch, K, mean, std);
+    return check_launch("sam_patch_rows_pair");
+}
+
+extern "C" int ffn_hyper_masks(void* stream, const float* up, const float* hyper, float* out, int N, int hw, int C, int M) {
+    REQUIRE(up && hyper && out, "hyper_masks: null pointer");
+    REQUIRE(aligned16(up), "hyper_masks: up must be 16-byte aligned");
+    REQUIRE(N >= 1 && N <= 65535, "hyper_masks: N=%d outside 1 .. 65535", N);
+    REQUIRE(hw >= 1 && hw <= FFN_IMGPREP_MAX_SIDE * FFN_IMGPREP_MAX_SIDE, "hyper_masks: hw=%d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE squared)", hw,
+            FFN_IMGPREP_MAX_SIDE * FFN_IMGPREP_MAX_SIDE);
+    REQUIRE(C >= 4 && C <= 64 && C % 4 == 0, "hyper_masks: C=%d channels (a multiple of 4, at most 64)", C);
+    REQUIRE(M >= 1 && M <= 8, "hyper_masks: M=%d masks outside 1 .. 8", M);
+    fsam_hyper_masks(reinterpret_cast<hipStream_t>(stream), up, hyper, out, N, hw, C, M);
+    return check_launch("hyper_masks");
+}
+
+extern "C" int ffn_upsample_bicubic(void* stream, const float* src, float* dst, uint8_t* mask, int N, int h, int w, int H, int W) {
+    const int lim = FFN_IMGPREP_MAX_SIDE;
+    REQUIRE(src && dst, "upsample_bicubic: null pointer");
+    REQUIRE(N >= 1 && N <= 65535, "upsample_bicubic: N=%d outside 1 .. 65535", N);
+    REQUIRE(h >= 1 && w >= 1 && h <= lim && w <= lim, "upsample_bicubic: source %d x %d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE)", h, w, lim);
+    REQUIRE(H >= 1 && W >= 1 && H <= lim && W <= lim, "upsample_bicubic: destination %d x %d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE)", H, W, lim);
+    fsam_bicubic(reinterpret_cast<hipStream_t>(stream), src, dst, mask, N, h, w, H, W);
+    return check_launch("upsample_bicubic");
+}
+
 // ---- elementwise / resampling helpers of the depth front end ----------------------------------------------------------
 extern "C" int ffn_eltwise(void* stream, int dtype, int op, const void* a, const void* b, void* y, long n) {
     REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16, "eltwise: bad dtype %d", dtype);
-    REQUIRE(op == FFN_ELT_RELU || op == FFN_ELT_ADD, "eltwise: bad op %d", op);
+    REQUIRE(op == FFN_ELT_RELU || op == FFN_ELT_ADD || op == FFN_ELT_GELU, "eltwise: bad op %d", op);
     REQUIRE(a && y && (op != FFN_ELT_ADD || b), "eltwise: null operand");
     REQUIRE(n > 0 && n % 4 == 0, "eltwise: n=%ld must be a positive multiple of 4", n);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -1342,9 +1400,11 @@ extern "C" int ffn_eltwise(void* stream, int dtype, int op, const void* a, const
     const int grid = grid_for(n4);
     if (dtype == FFN_F32) {
         if (op == FFN_ELT_RELU) LAUNCH((eltwise_kernel<float, FFN_ELT_RELU>), dim3(grid), dim3(256), 0, s, (const float*)a, (const float*)b, (float*)y, n4);
+        else if (op == FFN_ELT_GELU) LAUNCH((eltwise_kernel<float, FFN_ELT_GELU>), dim3(grid), dim3(256), 0, s, (const float*)a, (const float*)b, (float*)y, n4);
         else LAUNCH((eltwise_kernel<float, FFN_ELT_ADD>), dim3(grid), dim3(256), 0, s, (const float*)a, (const float*)b, (float*)y, n4);
     } else {
         if (op == FFN_ELT_RELU) LAUNCH((eltwise_kernel<bf16, FFN_ELT_RELU>), dim3(grid), dim3(256), 0, s, (const bf16*)a, (const bf16*)b, (bf16*)y, n4);
+        else if (op == FFN_ELT_GELU) LAUNCH((eltwise_kernel<bf16, FFN_ELT_GELU>), dim3(grid), dim3(256), 0, s, (const bf16*)a, (const bf16*)b, (bf16*)y, n4);
         else LAUNCH((eltwise_kernel<bf16, FFN_ELT_ADD>), dim3(grid), dim3(256), 0, s, (const bf16*)a, (const bf16*)b, (bf16*)y, n4);
     }
     return check_launch("eltwise");

@@ -204,7 +204,8 @@ __global__ __launch_bounds__(256) void nhwc_to_image_kernel(const T* __restrict_
 }
 
 // ---- depth front end ----------------------------------------------------------------------------------------
-// y = max(a, 0) / y = a + b, four elements per thread-iteration (depth_anything/blocks.py:68, 137-139)
+// y = max(a, 0) / y = a + b, four elements per thread-iteration (depth_anything/blocks.py:68, 137-139); y = gelu(a) (erf form; bf16: the fast erf of the
+// GEMM epilogues): the activation behind the GroupNorm of EfficientSAM's mask upscaling
 template <typename T, int OP>
 __global__ __launch_bounds__(256) void eltwise_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ y, long n4) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
@@ -214,6 +215,9 @@ __global__ __launch_bounds__(256) void eltwise_kernel(const T* __restrict__ a, c
             load4(b + 4 * i, vb);
 #pragma unroll
             for (int r = 0; r < 4; ++r) va[r] += vb[r];
+        } else if (OP == FFN_ELT_GELU) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) va[r] = gelu_for<T>(va[r]);
         } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) va[r] = fmaxf(va[r], 0.f);

@@ -1,12 +1,13 @@
 // Fifth translation unit of libfreefine_hip.so: the device image preparation of the DINOv2 feature metrics (imgprep.h) and the device case preparation of the
-// GeoBench harness (caseprep.h).  A unit of its own, like dift.hip, so that it compiles beside capi.hip; default code generation.  capi.o validates the arguments
+// GeoBench harness (caseprep.h) and the image preparation, mask product and upsampling of click-to-mask (sam.h).  A unit of its own, like dift.hip, so that it compiles beside capi.hip; default code generation.  capi.o validates the arguments
 // (ffn_resize_pil_bilinear_u8, ffn_resize_pil_u8, ffn_vit_patch_rows, ffn_vit_patch_rows_pair; ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8,
-// ffn_mask_bbox_u8, ffn_coarse_edit_2d) and calls the hidden functions below; nothing here is exported.
+// ffn_mask_bbox_u8, ffn_coarse_edit_2d; ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic) and calls the hidden functions below; nothing here is exported.
 #include <hip/hip_runtime.h>
 
 #include "../../include/freefine_hip.h"
 #include "imgprep.h"
-#include "caseprep.h"      // last: it turns floating-point contraction off for what follows
+#include "caseprep.h"      // it turns floating-point contraction off for what follows
+#include "sam.h"           // (contraction off as well)
 
 extern "C" __attribute__((visibility("hidden"))) void fimgprep_resize(hipStream_t s, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int oh, int ow,
                                                                       const int* hb, const int* hk, int hks, const int* vb, const int* vk, int vks) {
@@ -83,4 +84,38 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t fcaseprep_bbox(hipSt
 extern "C" __attribute__((visibility("hidden"))) void fcaseprep_edit(hipStream_t s, const ffn_coarse_edit_desc* d) {
     (void)hipGetLastError();
     hipLaunchKernelGGL(coarse_edit_kernel, dim3(caseprep_blocks(d->W), (unsigned)d->H, (unsigned)d->B), dim3(CASEPREP_THREADS), 0, s, *d);
+}
+
+// ---- click-to-mask (sam.h) -----------------------------------------------------------------------------------------------------------------------
+static inline unsigned sam_grid(long n) {
+    const long g = (n + SAM_THREADS - 1) / SAM_THREADS;
+    return (unsigned)(g > 8192 ? 8192 : g);
+}
+static inline sam_norm sam_norm_of(const float* mean, const float* std) { return sam_norm{{mean[0], mean[1], mean[2]}, {std[0], std[1], std[2]}}; }
+
+extern "C" __attribute__((visibility("hidden"))) void fsam_patch_rows(hipStream_t s, int dtype, const uint8_t* src, void* out, int B, int H, int W, int side, int ps, int ldo,
+                                                                      const float* mean, const float* std) {
+    (void)hipGetLastError();
+    const long total = (long)B * (side / ps) * (side / ps) * ldo;
+    if (dtype == FFN_BF16)
+        hipLaunchKernelGGL(sam_patch_rows_kernel<bf16>, dim3(sam_grid(total)), dim3(SAM_THREADS), 0, s, src, static_cast<bf16*>(out), total, H, W, side, ps, ldo, sam_norm_of(mean, std));
+    else
+        hipLaunchKernelGGL(sam_patch_rows_kernel<float>, dim3(sam_grid(total)), dim3(SAM_THREADS), 0, s, src, static_cast<float*>(out), total, H, W, side, ps, ldo, sam_norm_of(mean, std));
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fsam_patch_rows_pair(hipStream_t s, const uint8_t* src, void* out, int B, int H, int W, int side, int ps, int K,
+                                                                           const float* mean, const float* std) {
+    (void)hipGetLastError();
+    const long total = (long)B * (side / ps) * (side / ps) * (K / 8);      // one thread per 8 columns
+    hipLaunchKernelGGL(sam_patch_rows_pair_kernel, dim3(sam_grid(total)), dim3(SAM_THREADS), 0, s, src, static_cast<bf16*>(out), total, H, W, side, ps, K, sam_norm_of(mean, std));
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fsam_hyper_masks(hipStream_t s, const float* up, const float* hyper, float* out, int N, int hw, int C, int M) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(hyper_masks_kernel, dim3((unsigned)((hw + SAM_THREADS - 1) / SAM_THREADS), (unsigned)N), dim3(SAM_THREADS), 0, s, up, hyper, out, hw, C, M);
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fsam_bicubic(hipStream_t s, const float* src, float* dst, uint8_t* mask, int N, int h, int w, int H, int W) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(upsample_bicubic_kernel, dim3((unsigned)((W + SAM_THREADS - 1) / SAM_THREADS), (unsigned)H, (unsigned)N), dim3(SAM_THREADS), 0, s, src, dst, mask, h, w, H, W);
 }

@@ -968,6 +968,15 @@ def relu(x, out=None):
     return out
 
 
+def gelu(x, out=None):
+    """x (1 + erf(x / sqrt 2)) / 2 (fp32 / bf16, numel % 4 == 0)"""
+    lib = L.load()
+    out = torch.empty_like(x) if out is None else out
+    L.check(_timed("eltwise_kernel<gelu>", 0.0, 2.0 * x.numel() * x.element_size(),
+                   lambda: lib.ffn_eltwise(_stream(), _dt(x), L.ELT_GELU, x.data_ptr(), None, out.data_ptr(), x.numel())), "ffn_eltwise")
+    return out
+
+
 def add(a, b, out=None):
     """a + b (same shape and dtype, contiguous)"""
     lib = L.load()
@@ -1445,6 +1454,56 @@ def vit_patch_rows_pair(img, lut, patch, K, out=None):
     L.check(_timed("patch_rows_pair_kernel", 0.0, 3.0 * B * H * W + 4.0 * M * K,
                    lambda: lib.ffn_vit_patch_rows_pair(_stream(), img.data_ptr(), lut.data_ptr(), out.data_ptr(), B, H, W, patch, K)), "ffn_vit_patch_rows_pair")
     return _mark_pair(out, K)
+
+
+def _f3(v):
+    return (CT.c_float * 3)(*[float(x) for x in v])
+
+
+def sam_patch_rows(img, side, patch, ldo, dtype, mean, std, pair=False):
+    """uint8 [B, H, W, 3] (device) of any size -> the patch GEMM's operand rows for a side x side input: ToTensor, bilinear resize (ATen, align_corners=False, no
+    antialiasing) where the size differs, (x - mean) / std, im2col -- [B (side / patch)^2, ldo] of `dtype` (ffn_sam_patch_rows), or with pair the bf16 PAIR rows
+    [.., 2 ldo] of split-bf16 (ffn_sam_patch_rows_pair).  mean, std: three host floats each."""
+    lib = L.load()
+    assert img.dtype == torch.uint8 and img.ndim == 4 and img.shape[-1] == 3 and img.is_contiguous() and img.is_cuda
+    B, H, W, _ = img.shape
+    M = B * (side // patch) ** 2
+    mean, std = _f3(mean), _f3(std)
+    if pair:
+        out = torch.empty(M, 2 * ldo, dtype=torch.bfloat16, device=img.device)
+        L.check(_timed("sam_patch_rows_pair_kernel", 0.0, 3.0 * B * H * W + 4.0 * M * ldo,
+                       lambda: lib.ffn_sam_patch_rows_pair(_stream(), img.data_ptr(), out.data_ptr(), B, H, W, side, patch, ldo, mean, std)), "ffn_sam_patch_rows_pair")
+        return _mark_pair(out, ldo)
+    out = torch.empty(M, ldo, dtype=dtype, device=img.device)
+    L.check(_timed(f"sam_patch_rows_kernel<{_tname(out)}>", 0.0, 3.0 * B * H * W + float(M) * ldo * out.element_size(),
+                   lambda: lib.ffn_sam_patch_rows(_stream(), _dt(out), img.data_ptr(), out.data_ptr(), B, H, W, side, patch, ldo, mean, std)), "ffn_sam_patch_rows")
+    return out
+
+
+def hyper_masks(up, hyper):
+    """up fp32 [N, hw, C] (NHWC rows), hyper fp32 [N, M, C] -> fp32 [N, M, hw]: per pixel and mask the C-long dot product (ffn_hyper_masks)"""
+    lib = L.load()
+    assert up.dtype == hyper.dtype == torch.float32 and up.ndim == 3 and hyper.ndim == 3 and up.is_contiguous() and hyper.is_contiguous()
+    N, hw, Cc = up.shape
+    M = hyper.shape[1]
+    assert hyper.shape[0] == N and hyper.shape[2] == Cc
+    out = torch.empty(N, M, hw, dtype=torch.float32, device=up.device)
+    L.check(_timed("hyper_masks_kernel", 2.0 * N * M * hw * Cc, 4.0 * (up.numel() + out.numel()),
+                   lambda: lib.ffn_hyper_masks(_stream(), up.data_ptr(), hyper.data_ptr(), out.data_ptr(), N, hw, Cc, M)), "ffn_hyper_masks")
+    return out
+
+
+def upsample_bicubic(x, H, W, mask=False):
+    """fp32 [N, h, w] -> fp32 [N, H, W]: ATen's bicubic interpolation (align_corners=False, A = -0.75); mask: also uint8 [N, H, W] = 255 (result >= 0), from the
+    stored values (ffn_upsample_bicubic)"""
+    lib = L.load()
+    assert x.dtype == torch.float32 and x.ndim == 3 and x.is_contiguous()
+    N, h, w = x.shape
+    out = torch.empty(N, H, W, dtype=torch.float32, device=x.device)
+    m = torch.empty(N, H, W, dtype=torch.uint8, device=x.device) if mask else None
+    L.check(_timed("upsample_bicubic_kernel", 0.0, 4.0 * x.numel() + (5.0 if mask else 4.0) * out.numel(),
+                   lambda: lib.ffn_upsample_bicubic(_stream(), x.data_ptr(), out.data_ptr(), _p(m), N, h, w, H, W)), "ffn_upsample_bicubic")
+    return (out, m) if mask else out
 
 
 def image_to_nhwc(img_u8, CP, dtype, out=None):

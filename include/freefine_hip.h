@@ -246,7 +246,9 @@ int ffn_attn_kernel_name(int dtype, const ffn_attn_desc* d, char* buf, int len);
 /* ---- elementwise / resampling helpers of the depth front end ------------------------------------------ */
 /* y = max(a, 0) (FFN_ELT_RELU, b ignored) or y = a + b (FFN_ELT_ADD) over n elements (n % 4 == 0; fp32 or bf16).  Replaces the
  * activation in front of ResidualConvUnit.conv1 and FeatureFusionBlock's skip_add (depth_anything/blocks.py:68, 137-139). */
-enum { FFN_ELT_RELU = 0, FFN_ELT_ADD = 1 };
+/* FFN_ELT_GELU (ABI version 11, b ignored): y = a (1 + erf(a / sqrt 2)) / 2, erff in fp32; in bf16 the fast erf of the GEMM epilogues.  The activation behind
+ * GroupNorm(1, 64) in EfficientSAM's mask upscaling (evaluation/DesignEdit/sam/efficient_sam/efficient_sam_decoder.py:186-197). */
+enum { FFN_ELT_RELU = 0, FFN_ELT_ADD = 1, FFN_ELT_GELU = 2 };
 int ffn_eltwise(void* stream, int dtype, int op, const void* a, const void* b, void* y, long n);
 /* bilinear resampling of an NHWC tensor [B][Hin][Win][C] -> [B][Hout][Wout][C] with align_corners = True (source coordinate
  * y * (Hin - 1) / (Hout - 1), fp32 weights; Hout == 1 reads row 0): torch.nn.functional.interpolate(mode="bilinear",
@@ -508,6 +510,30 @@ int ffn_resize_gather_u8(void* stream, const uint8_t* src, uint8_t* dst, int B, 
 int ffn_dilate_u8(void* stream, const uint8_t* src, uint8_t* dst, uint8_t* scratch, int B, int H, int W, int C, int k);
 int ffn_mask_bbox_u8(void* stream, const uint8_t* mask, int* box, int B, int H, int W, int C);
 int ffn_coarse_edit_2d(void* stream, const ffn_coarse_edit_desc* d);
+
+/* ---- click-to-mask: what surrounds the EfficientSAM network (ABI version 11; csrc/sam.h, freefine_amd/sam.py) -----------------------------------------
+ * Reference: evaluation/DesignEdit/sam/efficient_sam/efficient_sam.py (preprocess :223-234, predict_masks :126-129) and efficient_sam_decoder.py:312, reached
+ * from src/demo/utils.py:40-100.  Floating-point contraction is off in these kernels: every product and every sum is rounded on its own, in fp32.  All four
+ * entries validate before any launch and refuse with FFN_EINVAL: null pointers, non-positive sizes, a side beyond FFN_IMGPREP_MAX_SIDE, N beyond 65535.
+ *
+ * The patch-row entries: src uint8 [B][H][W][3] of any size -> the operand rows [B (side / patch)^2][ldo] of the patch-embedding GEMM for a side x side
+ * network input, columns (c, ky, kx), zero from 3 patch^2 on, in fp32 / bf16 (FFN_F32 / FFN_BF16) -- or, the _pair entry, the PAIR form bf16 [..][2K] of rows of
+ * K fp32 columns (K % 8 == 0, out 16-byte aligned; layout and hi / lo as in the ViT patch-row pair entry above).  v = byte / 255; if (H, W) != (side, side), ATen's
+ * upsample_bilinear2d with align_corners = False and no antialiasing: scale = in / out in fp32, source = scale (dst + 0.5) - 0.5 clamped at 0, i0 = min(int(source),
+ * in - 1), i1 = i0 + (i0 < in - 1), weight of i1 = source - i0 in [0, 1], blended as h0 (w0 v00 + w1 v01) + h1 (w0 v10 + w1 v11); then (v - mean[c]) / std[c].
+ * mean, std: HOST float [3], read before the call returns (they travel as kernel arguments); std > 0.  The fp32 image is never written to memory.
+ *
+ * The hyper-mask entry: out [N][M][hw] fp32 = sum_c hyper[n][m][c] up[n][pixel][c], ascending c: up fp32 [N][hw][C] (NHWC rows of the upscaled embedding, 16-byte aligned),
+ * hyper fp32 [N][M][C]; C % 4 == 0, C <= 64, M <= 8, hw <= FFN_IMGPREP_MAX_SIDE squared.
+ *
+ * The bicubic entry: src fp32 [N][h][w] -> dst fp32 [N][H][W] by ATen's upsample_bicubic2d with align_corners = False, A = -0.75: scale = in / out in fp32, source =
+ * scale (dst + 0.5) - 0.5 NOT clamped, t = source - floor(source), taps floor(source) - 1 .. + 2 each clamped to the border, coefficients cubic_convolution2(t + 1),
+ * cubic_convolution1(t), cubic_convolution1(1 - t), cubic_convolution2(2 - t); the four column taps of each row are summed first, then the four rows.  mask (may be
+ * NULL): uint8 [N][H][W] = 255 where the value STORED in dst is >= 0, else 0 (torch.ge(logits, 0) of src/demo/utils.py:94). */
+int ffn_sam_patch_rows(void* stream, int dtype, const uint8_t* src, void* out, int B, int H, int W, int side, int patch, int ldo, const float* mean, const float* std);
+int ffn_sam_patch_rows_pair(void* stream, const uint8_t* src, void* out, int B, int H, int W, int side, int patch, int K, const float* mean, const float* std);
+int ffn_hyper_masks(void* stream, const float* up, const float* hyper, float* out, int N, int hw, int C, int M);
+int ffn_upsample_bicubic(void* stream, const float* src, float* dst, uint8_t* mask, int N, int h, int w, int H, int W);
 
 #ifdef __cplusplus
 }
