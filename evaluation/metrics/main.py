@@ -3,7 +3,7 @@
     python evaluation/metrics/main.py --path <generated_results.json> [--task 100111111] [--level 0..3] [--no_rotate] [--3d]
            [--use_relative_path --base_dir <GeoBenchMeta>] [--fid_path <real images>] [--gen_img_key gen_img_path]
            [--clip_weights <file>] [--dino_weights <file>] [--dinov2_weights <file>] [--model <SD folder | synthetic:sd21-base>] [--precision f32|x3]
-           [--hps_weights <file> --hps_tokenizer <folder>] [--md_visible_only]
+           [--hps_weights <file> --hps_tokenizer <folder>] [--md_visible_only] [--md_keypoints default|sift]
 
 --task is nine digits (1 = compute): FID, IRS, HPS, BGC, SUBC, WRAP_E, MD, FID_DINO, FID_KD.  The reference downloads its extractors (clip.load, torch.hub); there
 is no download here, the weights are local files: --clip_weights (CLIP ViT-B/32: a transformers CLIPVisionModelWithProjection state dict or the OpenAI
@@ -16,7 +16,10 @@ accumulation; the ViT towers, HPS's two among them, are built with x3=True and t
 For an edit that is neither a translation, a 2-D rotation nor a uniform scale, MD reads the case's correspondence map: <tree>/correspondence/<da>/<ins>/<edit>.npy
 beside the folder of generated images (the 3d_rgb variant of evaluation/FreeFine/freefine_batch_infer_2d.py writes it with --save-correspondence).
 --md_visible_only (an extension of the reference's metric, off by default: values compare with the reference's only without it) drops the keypoints the
-sibling correspondence_visible/....png marks as hidden in the coarse edit."""
+sibling correspondence_visible/....png marks as hidden in the coarse edit.
+--md_keypoints sift takes MD's keypoints as the reference does, from SIFT matches between the source and the edited image that pass Lowe's ratio test and start inside the
+object mask (freefine_amd/sift.py, on the device; Lowe's SIFT with OpenCV's default parameters -- parity with cv2's own output is unmeasured, and where the reference falls
+back to ORB this falls back to SIFT detections).  The default, `default`, is the sample's own "keypoints" list or every s-th mask pixel, as before."""
 import argparse
 import json
 import os
@@ -75,7 +78,7 @@ def load_state(path):
     return st.get("state_dict", st) if isinstance(st, dict) else st
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="Evaluation")
     ap.add_argument("--path", required=True, help="JSON file of generated results")
     ap.add_argument("--level", default=0, type=int, help="edit level (0 = all, 1 = easy, 2 = medium, 3 = hard)")
@@ -95,9 +98,17 @@ def main(argv=None):
     ap.add_argument("--precision", default="f32", choices=("f32", "x3"), help="arithmetic of the networks: f32 = exact fp32, x3 = split-bf16")
     ap.add_argument("--md_visible_only", action="store_true", help="MD: drop keypoints hidden in the coarse 3-D edit (needs correspondence_visible images; "
                                                                    "not the reference's metric)")
+    ap.add_argument("--md_keypoints", default="default", choices=("default", "sift"),
+                    help="MD: where the keypoints come from.  default = the sample's own list or every s-th mask pixel; sift = SIFT ratio-test matches between "
+                         "source and edited image inside the mask, on the device (the reference's kind of point set; parity with cv2 is unmeasured)")
     ap.add_argument("--clip_config", default="vitb32", help=argparse.SUPPRESS)        # "tiny": the test sizes
     ap.add_argument("--dino_config", default="vitb16", help=argparse.SUPPRESS)
     ap.add_argument("--hps_config", default="vith14", choices=("vith14", "tiny"), help=argparse.SUPPRESS)      # with "tiny", --hps_tokenizer bytes: text.ByteTokenizer
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if len(args.task) != len(NAMES) or set(args.task) - set("01"):
         ap.error(f"--task takes {len(NAMES)} digits of 0 / 1")
@@ -141,7 +152,7 @@ def main(argv=None):
                 return "not run (--model missing)"
             from freefine_amd.pipeline import FreeFinePipeline
             return FM.calculate_md(data, label, FreeFinePipeline.from_pretrained(args.model, torch_dtype=torch.float32, device=torch.device("cuda:0"), x3=x3),
-                                   visible_only=args.md_visible_only)
+                                   keypoints="sift" if args.md_keypoints == "sift" else None, visible_only=args.md_visible_only)
         if not args.dinov2_weights or not args.fid_path:
             return "not run (--dinov2_weights or --fid_path missing)"
         return (FM.calculate_fid_dino if name == "FID_DINO" else FM.calculate_fid_kd)(data, label, args.fid_path, dinov2(), x3=x3)

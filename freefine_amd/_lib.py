@@ -157,6 +157,13 @@ SYMBOLS = {
     "ffn_embed_tokens": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _l, _i, _i, _i]),
     "ffn_dift_match": (_i, [_vp, C.POINTER(DiftDesc)]),
     "ffn_dift_workspace_bytes": (_l, [_i, _i, _i, _i]),
+    "ffn_sift_base": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "ffn_gauss_blur_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i]),
+    "ffn_decimate2_f32": (_i, [_vp, _vp, _vp, _i, _i]),
+    "ffn_sift_extrema": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, C.POINTER(C.c_int)]),
+    "ffn_sift_refine_orient": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "ffn_sift_describe": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "ffn_knn2_u8": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "ffn_resize_pil_bilinear_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i]),
     "ffn_resize_pil_u8": (_i, [_vp, C.POINTER(ResizePilDesc)]),
     "ffn_resize_taps8_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

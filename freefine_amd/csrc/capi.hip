@@ -70,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 11; }      // 11: click-to-mask (ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic, FFN_ELT_GELU); 10: the correspondence map of the point-cloud warp (ffn_splat_ids, ffn_splat_correspond); 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
+extern "C" int ffn_version(void) { return 12; }      // 12: SIFT keypoints for Mean Distance (ffn_sift_base, ffn_gauss_blur_f32, ffn_decimate2_f32, ffn_sift_extrema, ffn_sift_refine_orient, ffn_sift_describe, ffn_knn2_u8; FFN_ENOSPC); 11: click-to-mask (ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic, FFN_ELT_GELU); 10: the correspondence map of the point-cloud warp (ffn_splat_ids, ffn_splat_correspond); 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -1199,6 +1199,79 @@ extern "C" int ffn_dift_match(void* stream, const ffn_dift_desc* dp) {
                 d.kps[2 * k], d.kps[2 * k + 1], d.H, d.W);
     fdift_launch(reinterpret_cast<hipStream_t>(stream), &d);
     return check_launch("dift_match");
+}
+
+// ---- SIFT keypoints, descriptors and matching of the Mean Distance metric (kernels: sift.h, compiled in dift.hip) -------------------------------------------
+
+extern "C" __attribute__((visibility("hidden"))) void fsift_base(hipStream_t s, const uint8_t* img, float* out, int H, int W, int C);
+extern "C" __attribute__((visibility("hidden"))) void fsift_blur(hipStream_t s, const float* src, float* dst, float* tmp, int H, int W, const float* taps, int T);
+extern "C" __attribute__((visibility("hidden"))) void fsift_decimate(hipStream_t s, const float* src, float* dst, int H, int W);
+extern "C" __attribute__((visibility("hidden"))) int fsift_extrema(hipStream_t s, const float* G, float* D, int h, int w, int* cand, int cap, int* counter, int* found);
+extern "C" __attribute__((visibility("hidden"))) void fsift_refine(hipStream_t s, const float* D, const float* G, int h, int w, int o, const int* cand, int n, float* out);
+extern "C" __attribute__((visibility("hidden"))) void fsift_describe(hipStream_t s, const float* G, int h, int w, int o, const float* kp, int n, uint8_t* desc, float* raw);
+extern "C" __attribute__((visibility("hidden"))) void fknn2_u8(hipStream_t s, const uint8_t* des1, int n1, const uint8_t* des2, int n2, int* idx, int* dist);
+
+static inline bool sift_side_ok(int h, int w) { return h >= 1 && w >= 1 && h <= FFN_SIFT_MAX_SIDE && w <= FFN_SIFT_MAX_SIDE; }
+
+extern "C" int ffn_sift_base(void* stream, const uint8_t* img, float* out, int H, int W, int C) {
+    REQUIRE(img && out, "sift_base: null pointer");
+    REQUIRE(H >= 1 && W >= 1 && 2 * H <= FFN_SIFT_MAX_SIDE && 2 * W <= FFN_SIFT_MAX_SIDE && (C == 1 || C == 3), "sift_base: bad shape H=%d W=%d C=%d (C in {1, 3}, sides <= %d)", H, W,
+            C, FFN_SIFT_MAX_SIDE / 2);
+    fsift_base(reinterpret_cast<hipStream_t>(stream), img, out, H, W, C);
+    return check_launch("sift_base");
+}
+
+extern "C" int ffn_gauss_blur_f32(void* stream, const float* src, float* dst, float* tmp, int H, int W, const float* taps, int T) {
+    REQUIRE(src && dst && tmp && taps, "gauss_blur_f32: null pointer");
+    REQUIRE(tmp != src && tmp != dst, "gauss_blur_f32: tmp must be a buffer of its own");
+    REQUIRE(sift_side_ok(H, W), "gauss_blur_f32: bad shape H=%d W=%d (sides 1 .. %d)", H, W, FFN_SIFT_MAX_SIDE);
+    REQUIRE(T >= 1 && T <= FFN_SIFT_MAX_TAPS && (T & 1), "gauss_blur_f32: %d taps (odd, 1 .. %d)", T, FFN_SIFT_MAX_TAPS);
+    fsift_blur(reinterpret_cast<hipStream_t>(stream), src, dst, tmp, H, W, taps, T);
+    return check_launch("gauss_blur_f32");
+}
+
+extern "C" int ffn_decimate2_f32(void* stream, const float* src, float* dst, int H, int W) {
+    REQUIRE(src && dst && src != dst, "decimate2_f32: null or aliased pointer");
+    REQUIRE(sift_side_ok(H, W) && H >= 2 && W >= 2, "decimate2_f32: bad shape H=%d W=%d (sides 2 .. %d)", H, W, FFN_SIFT_MAX_SIDE);
+    fsift_decimate(reinterpret_cast<hipStream_t>(stream), src, dst, H, W);
+    return check_launch("decimate2_f32");
+}
+
+extern "C" int ffn_sift_extrema(void* stream, const float* gauss, float* dog, int h, int w, int* cand, int cap, int* counter, int* count) {
+    REQUIRE(gauss && dog && cand && counter && count, "sift_extrema: null pointer");
+    REQUIRE(sift_side_ok(h, w) && cap >= 1, "sift_extrema: bad shape h=%d w=%d cap=%d (sides 1 .. %d, cap >= 1)", h, w, cap, FFN_SIFT_MAX_SIDE);
+    *count = 0;
+    const int e = fsift_extrema(reinterpret_cast<hipStream_t>(stream), gauss, dog, h, w, cand, cap, counter, count);
+    if (e != 0) return fail(FFN_EHIP, "sift_extrema: %s", hipGetErrorString((hipError_t)e));
+    if (*count > cap) return fail(FFN_ENOSPC, "sift_extrema: %d extrema but room for %d: call again with a longer list", *count, cap);
+    return check_launch("sift_extrema");
+}
+
+extern "C" int ffn_sift_refine_orient(void* stream, const float* dog, const float* gauss, int h, int w, int octave, const int* cand, int n, float* out) {
+    REQUIRE(n >= 0, "sift_refine_orient: n=%d", n);
+    if (n == 0) return FFN_OK;
+    REQUIRE(dog && gauss && cand && out, "sift_refine_orient: null pointer");
+    REQUIRE(sift_side_ok(h, w) && octave >= 0 && octave < 24, "sift_refine_orient: bad shape h=%d w=%d octave=%d", h, w, octave);
+    fsift_refine(reinterpret_cast<hipStream_t>(stream), dog, gauss, h, w, octave, cand, n, out);
+    return check_launch("sift_refine_orient");
+}
+
+extern "C" int ffn_sift_describe(void* stream, const float* gauss, int h, int w, int octave, const float* kp, int n, uint8_t* desc, float* raw) {
+    REQUIRE(n >= 0, "sift_describe: n=%d", n);
+    if (n == 0) return FFN_OK;
+    REQUIRE(gauss && kp && desc, "sift_describe: null pointer");
+    REQUIRE(sift_side_ok(h, w) && octave >= 0 && octave < 24, "sift_describe: bad shape h=%d w=%d octave=%d", h, w, octave);
+    fsift_describe(reinterpret_cast<hipStream_t>(stream), gauss, h, w, octave, kp, n, desc, raw);
+    return check_launch("sift_describe");
+}
+
+extern "C" int ffn_knn2_u8(void* stream, const uint8_t* des1, int n1, const uint8_t* des2, int n2, int* idx, int* dist) {
+    REQUIRE(n1 >= 0 && n2 >= 0, "knn2_u8: n1=%d n2=%d", n1, n2);
+    if (n1 == 0) return FFN_OK;
+    REQUIRE(des1 && idx && dist && (des2 || n2 == 0), "knn2_u8: null pointer");
+    REQUIRE((reinterpret_cast<uintptr_t>(des1) & 3) == 0 && (reinterpret_cast<uintptr_t>(des2) & 3) == 0, "knn2_u8: descriptor rows are read as 32-bit words: 4-byte alignment");
+    fknn2_u8(reinterpret_cast<hipStream_t>(stream), des1, n1, des2, n2, idx, dist);
+    return check_launch("knn2_u8");
 }
 
 // ---- device image preparation of the DINOv2 feature metrics (kernels and launches: imgprep.hip / imgprep.h) ----------------------------------------

@@ -28,9 +28,11 @@ Mean Distance (MD/mean_distance.py), the one metric of the suite that measures t
 DIFT, i.e. Stable Diffusion itself, and runs on the project's kernels (freefine_amd/dift.py: HipVAE + HipUNet.features; the correspondence search is
 ops.dift_match).  transform_coordinates / mean_distance / calculate_md below are the metric; the coordinate maps are pinned to the reference's
 get_transform_coordinates by tests/golden/g13_md_coords.npz (tools/gen_golden.py run_g13; translation and uniform scale -- the rotation branch calls cv2 there
-and is pinned only to the documented matrix formula, src/utils/vis_utils.py::_rotation_matrix_2d).  The reference finds its keypoints with cv2 SIFT / ORB, which
-exists neither here nor is restated: keypoints are supplied by the caller or come from a documented deterministic sampler, and MD values are comparable to
-the reference's only when the same keypoints are supplied."""
+and is pinned only to the documented matrix formula, src/utils/vis_utils.py::_rotation_matrix_2d).  The reference finds its keypoints with cv2 SIFT matches (ORB when there are none).  cv2 exists nowhere
+this is built; by default keypoints are supplied by the caller or come from a documented deterministic sampler (default_keypoints), and MD values are comparable to
+the reference's only when the same keypoints are supplied.  Opt-in, calculate_md(..., keypoints="sift"): the keypoints are SIFT ratio-test matches found on the
+device (freefine_amd/sift.py: Lowe's SIFT with OpenCV's default parameters, held to the fp64 restatement tests/sift_ref.py -- the same KIND of point set as the
+reference's, textured points that survived the edit; parity with cv2's own output is unmeasured, and the no-match fallback is SIFT detections, not ORB)."""
 import numpy as np
 
 
@@ -414,7 +416,8 @@ def calculate_md(data, image_label, pipe, keypoints=None, reader=None, max_point
     """mean_distance.py:calculate_md over a GeoBench result tree data[image]["instances"][instance][sample] with ori_img_path / <image_label> / ori_mask_path /
     edit_param / obj_label (the prompt) -> the mean distance over all keypoints of all cases.  pipe: a FreeFinePipeline (its checkpoint is the feature
     extractor: freefine_amd/dift.py states the two deviations from the reference's SDFeaturizer) or a ready HipSDFeaturizer.  keypoints: a callable
-    (src_img, gen_img, mask / 255) -> [[row, col], ...]; None -> the sample's own "keypoints" list when it has one, else default_keypoints(mask).  MD values are
+    (src_img, gen_img, mask / 255) -> [[row, col], ...] (a freefine_amd.sift.HipSift is one); "sift" -> a HipSift on the pipeline's device, i.e. sift.sift_matches,
+    the counterpart of the reference's get_Matches; None -> the sample's own "keypoints" list when it has one, else default_keypoints(mask).  MD values are
     comparable to the reference's only when the reference's keypoints are supplied.  `reader` maps a path to an array (default: PIL).
     visible_only (extension of the reference's metric, default off; values compare with the reference's only when it is off): where the sibling
     `correspondence_visible/....png` of a case's correspondence file exists (warp3d.save_correspondence writes it), keypoints that are not visible in the
@@ -425,6 +428,11 @@ def calculate_md(data, image_label, pipe, keypoints=None, reader=None, max_point
         from PIL import Image
         reader = lambda p: np.array(Image.open(p))
     feat = pipe if isinstance(pipe, HipSDFeaturizer) else HipSDFeaturizer(pipe)
+    if isinstance(keypoints, str):
+        if keypoints != "sift":
+            raise ValueError(f"calculate_md: keypoints={keypoints!r}; the named detectors are 'sift'")
+        from .sift import HipSift
+        keypoints = HipSift(getattr(feat.pipe, "device", None))
     dists = []
     for image in data.values():
         for instance in image["instances"].values():

@@ -30,7 +30,7 @@ extern "C" {
 
 enum { FFN_F32 = 0, FFN_BF16 = 1, FFN_BF16X3 = 2 /* ffn_igemm / ffn_attn: split-bf16 arithmetic, fp32 results (see ffn_igemm) */,
        FFN_FP8 = 3 /* ffn_igemm, 3x3 convolutions only: OCP e4m3 operands, bf16 results (see ffn_igemm) */ };
-enum { FFN_OK = 0, FFN_EINVAL = -22, FFN_ENOSYS = -38, FFN_EHIP = -5 };
+enum { FFN_OK = 0, FFN_EINVAL = -22, FFN_ENOSYS = -38, FFN_EHIP = -5, FFN_ENOSPC = -28 };      /* FFN_ENOSPC (ABI version 12): a caller-sized output list is too short */
 
 int ffn_version(void);
 const char* ffn_last_error(void);
@@ -399,6 +399,45 @@ typedef struct ffn_dift_desc {
 } ffn_dift_desc;
 int ffn_dift_match(void* stream, const ffn_dift_desc* d);
 long ffn_dift_workspace_bytes(int C, int h, int w, int K);
+
+/* ---- SIFT keypoints, descriptors and ratio-test matching of the Mean Distance metric (ABI version 12; csrc/sift.h) ----------------------------
+ * Reference: evaluation/metrics/MD/mean_distance.py:49-79 takes MD's keypoints from cv2.SIFT_create().detectAndCompute and cv2.BFMatcher().knnMatch.  These
+ * entries restate Lowe's SIFT with OpenCV's default parameters, one entry per stage; they are held to the fp64 restatement tests/sift_ref.py, NOT to cv2's output
+ * (cv2 exists nowhere this is built: parity with its bytes is unmeasured).  freefine_amd/sift.py strings them together.  Images are contiguous; every octave side
+ * is at most FFN_SIFT_MAX_SIDE.  Anything outside the stated limits is refused with FFN_EINVAL before any launch.  All on the caller's stream, no allocation;
+ * only ffn_sift_extrema synchronises (it returns a count).
+ *
+ *   ffn_sift_base         img uint8 [H][W][C], C = 3 or 1 -> out fp32 [2H][2W].  gray = (c0 * 1868 + c1 * 9617 + c2 * 4899 + 8192) >> 14 (OpenCV's 8-bit BGR2GRAY
+ *                         applied to the array as given: the reference passes RGB, so channel 0 gets B's weight; C = 1 is taken as gray), then 2x bilinear upsampling
+ *                         (source coordinate (d + 0.5) / 2 - 0.5, clamped).  Exact in fp32.
+ *   ffn_gauss_blur_f32    separable blur of src [H][W] into dst (dst may be src; tmp [H][W] is a third buffer).  taps: HOST float [T], T odd <= FFN_SIFT_MAX_TAPS,
+ *                         read before the call returns.  Per pass out(p) = sum over k ascending of taps[k] * in(reflect101(p + k - T / 2)), each product rounded,
+ *                         then added (no FMA); horizontal pass first.
+ *   ffn_decimate2_f32     dst [H / 2][W / 2] = src(2 y, 2 x): the first image of the next octave.
+ *   ffn_sift_extrema      gauss [6][h][w] -> dog [5][h][w] = gauss[i + 1] - gauss[i], and the list cand int32 [cap][3] = (layer, row, col) of the 26-neighbour extrema
+ *                         of dog layers 1..3 (ties allowed: >= / <=), |value| > 1, 5-pixel border, in no particular order.  counter: one device int (scratch);
+ *                         *count (host): how many were found.  More than cap: FFN_ENOSPC, the list holds cap of them -- never a silently short list.  An octave
+ *                         with a side below 11 pixels has no candidates.
+ *   ffn_sift_refine_orient  per candidate: up to 5 steps of the 3-D quadratic fit (image scale 1 / 255, central differences, Cramer's rule), contrast test
+ *                         |D + grad . x / 2| * 3 >= 0.04, edge test det > 0 and tr^2 * 10 < 121 det, 36-bin orientation histogram on the Gaussian layer (radius
+ *                         round(4.5 s), weight sigma 1.5 s), [1 4 6 4 1] / 16 smoothing, one angle per local peak >= 0.8 max (parabola).  octave: 0 = the
+ *                         upsampled base.  out fp32 [n][27] = (keep, layer, row, col, x, y, size, response, npeaks, 18 angles in degrees), x / y / size in INPUT-image
+ *                         pixels; a rejected candidate's record is all zero.
+ *   ffn_sift_describe     kp fp32 [n][7] = (x, y, size, angle, response, octave - 1, layer), all of octave `octave` -> desc uint8 [n][128] (4 x 4 x 8, trilinear
+ *                         binning, histogram width 3 s, Gaussian weight exp(-(r^2 + c^2) / 8) in bin units, L2-normalise, clip at 0.2, renormalise to 512, saturate);
+ *                         raw (may be null) fp32 [n][128]: the values before the conversion to uint8.
+ *   ffn_knn2_u8           for every row of des1 [n1][128] the two nearest rows of des2 [n2][128] by squared L2 distance in int32, ties to the lower index:
+ *                         idx int32 [n1][2], dist int32 [n1][2]; a missing neighbour (n2 < 2) is index -1 at distance INT_MAX.  Rows 4-byte aligned.  Lowe's ratio
+ *                         test 0.75 is 16 * dist[0] < 9 * dist[1] (the caller's). */
+#define FFN_SIFT_MAX_SIDE 16384
+#define FFN_SIFT_MAX_TAPS 63
+int ffn_sift_base(void* stream, const uint8_t* img, float* out, int H, int W, int C);
+int ffn_gauss_blur_f32(void* stream, const float* src, float* dst, float* tmp, int H, int W, const float* taps, int T);
+int ffn_decimate2_f32(void* stream, const float* src, float* dst, int H, int W);
+int ffn_sift_extrema(void* stream, const float* gauss, float* dog, int h, int w, int* cand, int cap, int* counter, int* count);
+int ffn_sift_refine_orient(void* stream, const float* dog, const float* gauss, int h, int w, int octave, const int* cand, int n, float* out);
+int ffn_sift_describe(void* stream, const float* gauss, int h, int w, int octave, const float* kp, int n, uint8_t* desc, float* raw);
+int ffn_knn2_u8(void* stream, const uint8_t* des1, int n1, const uint8_t* des2, int n2, int* idx, int* dist);
 
 /* ---- device image preparation of the DINOv2 feature metrics (FID-DINO, Kernel Distance) ---------------------------------------------------
  * Reference: evaluation/metrics/FID/fid_score.py:122-124 -- TF.Resize((224, 224)) of a PIL image (antialiased bilinear), TF.ToTensor, TF.Normalize, on the
