@@ -18,7 +18,7 @@ from src.demo.model import DDIMScheduler, FreeFinePipeline  # noqa: E402
 from src.utils.attention import Attention_Modulator, register_attention_control  # noqa: E402
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--base-dir", required=True)
     ap.add_argument("--model", default="synthetic:sd21-base")
@@ -34,7 +34,17 @@ def main():
     ap.add_argument("--save-correspondence", action="store_true",
                     help="3d_rgb: also write every case's correspondence map (Geo-Bench-3D/correspondence/<da>/<ins>/<edit>.npy, where Mean Distance looks "
                          "for it) and the visibility image beside it (Geo-Bench-3D/correspondence_visible/...png)")
-    args = ap.parse_args()
+    ap.add_argument("--warp", default="p3d", choices=["p3d", "geodiffuser"],
+                    help="3d_rgb: p3d = this project's point-cloud warp (object pixels only, radius 1.5, K = 5); geodiffuser = the reference's own step 2 "
+                         "(the GeoDiffuser warp of get_3d_transform_correspondence.py: every pixel, radius 1.3, K = 15, draw mask = md_mask; square images)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.warp != "p3d" and args.variant != "3d_rgb":
+        ap.error("--warp geodiffuser needs --variant 3d_rgb (the other variants do not build the warp)")
     if args.save_correspondence and args.variant != "3d_rgb":
         ap.error("--save-correspondence needs --variant 3d_rgb (the other variants do not build the warp)")
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -66,7 +76,7 @@ def main():
             dcfg = FDp.depth_config({384: "vits", 768: "vitb", 1024: "vitl"}[dstate["pretrained.cls_token"].shape[-1]])
         depth_model = FDp.HipDepthAnything(dcfg, dstate, dtype=dtype, device=device)
     geobench.run(model, args.base_dir, batch=args.batch, rank=rank, world=world, variant=args.variant, depth_model=depth_model,
-                 device_prep=args.device_prep, save_correspondence=args.save_correspondence)
+                 device_prep=args.device_prep, save_correspondence=args.save_correspondence, warp=args.warp)
     if world > 1:
         torch.distributed.destroy_process_group()
 

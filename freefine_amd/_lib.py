@@ -154,6 +154,9 @@ SYMBOLS = {
     "ffn_splat_render": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp, _vp]),
     "ffn_splat_ids": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp]),
     "ffn_splat_correspond": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "ffn_geo_project": (_i, [_vp, _vp, C.POINTER(C.c_float), _f, _i, _i, _vp, _vp]),
+    "ffn_splat_composite": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _i, _i, _vp]),
+    "ffn_mesh_cover": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "ffn_embed_tokens": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _l, _i, _i, _i]),
     "ffn_dift_match": (_i, [_vp, C.POINTER(DiftDesc)]),
     "ffn_dift_workspace_bytes": (_l, [_i, _i, _i, _i]),

@@ -70,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 12; }      // 12: SIFT keypoints for Mean Distance (ffn_sift_base, ffn_gauss_blur_f32, ffn_decimate2_f32, ffn_sift_extrema, ffn_sift_refine_orient, ffn_sift_describe, ffn_knn2_u8; FFN_ENOSPC); 11: click-to-mask (ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic, FFN_ELT_GELU); 10: the correspondence map of the point-cloud warp (ffn_splat_ids, ffn_splat_correspond); 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
+extern "C" int ffn_version(void) { return 13; }      // 13: the GeoDiffuser warp of GeoBench-3D (ffn_geo_project, ffn_splat_composite, ffn_mesh_cover); 12: SIFT keypoints for Mean Distance (ffn_sift_base, ffn_gauss_blur_f32, ffn_decimate2_f32, ffn_sift_extrema, ffn_sift_refine_orient, ffn_sift_describe, ffn_knn2_u8; FFN_ENOSPC); 11: click-to-mask (ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic, FFN_ELT_GELU); 10: the correspondence map of the point-cloud warp (ffn_splat_ids, ffn_splat_correspond); 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -1817,4 +1817,39 @@ extern "C" int ffn_splat_correspond(void* stream, const float* proj, const int* 
     if (n == 0) return FFN_OK;
     LAUNCH(splat_correspond_kernel, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), proj, idx, n, W, H, ids, K, map, visible);
     return check_launch("splat_correspond");
+}
+
+// ---- the GeoDiffuser warp of the reference's GeoBench-3D step 2 (geowarp.h) ---------------------------------------------
+// included here, after everything else, so that the kernels of the units above keep their place in the code object
+#include "geowarp.h"
+extern "C" int ffn_geo_project(void* stream, const float* depth, const float* pose, float focal, int H, int W, float* tcoords, float* proj) {
+    REQUIRE(depth && pose && tcoords && proj, "geo_project: null operand");
+    REQUIRE(H == W, "geo_project: the image must be square (%d x %d): the reference takes sqrt(N) for the side", H, W);
+    REQUIRE(H >= 2 && H <= 4096 && focal > 0.f, "geo_project: side %d outside 2 .. 4096, or focal length <= 0", H);
+    GeoPose P;
+    for (int a = 0; a < 12; ++a) P.m[a] = pose[a];
+    LAUNCH(geo_project_kernel, dim3(grid_for((long)H * W)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), depth, P, focal, H, tcoords, proj);
+    return check_launch("geo_project");
+}
+extern "C" int ffn_splat_composite(void* stream, const float* proj, const float* feat, const int* offs, const int* list, float radius, float tau, int K,
+                                   int C, int H, int W, int round_half, float* out) {
+    REQUIRE(proj && feat && offs && list && out, "splat_composite: null operand");
+    REQUIRE(H == W, "splat_composite: the image must be square (%d x %d)", H, W);
+    REQUIRE(H >= 1 && H <= 4096, "splat_composite: side %d outside 1 .. 4096", H);
+    REQUIRE(K >= 1 && K <= 32, "splat_composite: points per pixel K=%d out of range (1 .. 32)", K);
+    REQUIRE(C >= 1 && C <= 8, "splat_composite: C=%d feature channels out of range (1 .. 8)", C);
+    REQUIRE(radius > 0.f && tau > 0.f, "splat_composite: radius and tau must be positive");
+    const int tiles = ((W + 15) / 16) * ((H + 15) / 16);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (K <= 8) LAUNCH(geo_composite_kernel<8>, dim3(tiles), dim3(256), 0, s, proj, feat, offs, list, radius, tau, K, C, W, H, round_half, out);
+    else if (K <= 16) LAUNCH(geo_composite_kernel<16>, dim3(tiles), dim3(256), 0, s, proj, feat, offs, list, radius, tau, K, C, W, H, round_half, out);
+    else LAUNCH(geo_composite_kernel<32>, dim3(tiles), dim3(256), 0, s, proj, feat, offs, list, radius, tau, K, C, W, H, round_half, out);
+    return check_launch("splat_composite");
+}
+extern "C" int ffn_mesh_cover(void* stream, const float* tcoords, const uint8_t* mask, int H, int W, uint8_t* cover) {
+    REQUIRE(tcoords && mask && cover, "mesh_cover: null operand");
+    REQUIRE(H == W, "mesh_cover: the image must be square (%d x %d)", H, W);
+    REQUIRE(H >= 2 && H <= 4096, "mesh_cover: side %d outside 2 .. 4096", H);
+    LAUNCH(geo_mesh_cover_kernel, dim3(grid_for(2l * (H - 1) * (W - 1))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), tcoords, mask, H, cover);
+    return check_launch("mesh_cover");
 }

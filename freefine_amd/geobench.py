@@ -276,13 +276,56 @@ def finish_case_3d_rgb(raw, depth_model, focal_length=550.0, prep=HostPrep, corr
                 cons_area=np.maximum(target_mask, (m2 > 0).astype(np.uint8) * 255), **extra)
 
 
+WARPS = ("p3d", "geodiffuser")
+
+
+def _check_warp(warp, variant="3d_rgb"):
+    if warp not in WARPS:
+        raise ValueError(f"warp = {warp!r}: one of {WARPS}")
+    if warp != "p3d" and variant != "3d_rgb":
+        raise ValueError(f"warp = {warp!r}: only the 3d_rgb variant builds its own warp (variant = {variant!r})")
+
+
+def finish_case_3d_geo(raw, depth_model, focal_length=550.0, prep=HostPrep, correspondence=False):
+    """finish_case_3d_rgb with the coarse edit rendered the reference's way (warp="geodiffuser"): step 2 of the reference's 3-D run,
+    evaluation/FreeFine/get_3d_transform_correspondence.py:207-289, through warp3d.geodiffuser_coarse_edit.  `raw` must still hold the decoded files
+    (read_case_3d_rgb(prep=None)): as in the reference the warp's image is resized with PIL's default bicubic (:181) and its mask with PIL nearest
+    (:227), the depth is monocular_depth(translate_factor=0.0), translations are edit_param / 512 and the focal length 550 at the 512 size (scaled with
+    the side elsewhere).  The draw mask is the reference's md_mask (the projected mask mesh outside the splatted object); cons_area stays as in
+    finish_case_3d_rgb; ori_img / ori_mask, the edit's own inputs, go through `prep` as today.  Square dsize only.  correspondence: the dict also carries
+    `correspondence` (the reference's map, float32 [S, S, 2], (x, y)), `correspondence_visible` = None and `md_mask` (uint8 x 255) -- not inputs of
+    the edit: run() / prepare_3d take them out."""
+    from PIL import Image
+    from . import warp3d
+    if raw.get("_resized", True):
+        raise ValueError("finish_case_3d_geo resizes the decoded files itself (PIL bicubic / nearest, like the reference): read the case with read_case_3d_rgb(prep=None)")
+    dsize = raw["dsize"]
+    if dsize[0] != dsize[1]:
+        raise ValueError(f"the GeoDiffuser warp takes square images; dsize = {dsize}")
+    assert depth_model is not None, "the 3d_rgb variant needs a depth model (freefine_amd.depth.HipDepthAnything or depth_anything.dpt.DepthAnything)"
+    L = int(dsize[0])
+    g_img = np.array(Image.fromarray(raw["ori_img"]).resize((L, L)))
+    g_mask = np.array(Image.fromarray(np.ascontiguousarray(raw["ori_mask"][:, :, 0] if raw["ori_mask"].ndim == 3 else raw["ori_mask"])).resize((L, L), resample=Image.NEAREST))
+    g_bg = raw["bg"] if raw["bg"].shape[:2] == (L, L) else np.array(Image.fromarray(raw["bg"]).resize((L, L)))      # the reference reads it at 512 already
+    depth = monocular_depth(g_img, depth_model, translate_factor=0.0)
+    coarse, tmask, _, md, corr = warp3d.geodiffuser_coarse_edit(g_img, g_mask, depth, raw["edit_param"], g_bg, focal_length=focal_length * L / 512.0)
+    res = _resize_case_3d_rgb(raw, prep)
+    ori_mask = res["ori_mask"]
+    m2 = ori_mask if ori_mask.ndim == 2 else ori_mask[:, :, 0]
+    target_mask = tmask.astype(np.uint8) * 255
+    extra = dict(correspondence=corr, correspondence_visible=None, md_mask=md.astype(np.uint8) * 255) if correspondence else {}
+    return dict(ori_img=res["ori_img"], ori_mask=ori_mask, coarse_input=coarse, target_mask=target_mask, guidance_text=raw["obj_label"],
+                draw_mask=md.astype(np.uint8), use_auto_draw=False, reduce_inp_artifacts=True,
+                cons_area=np.maximum(target_mask, (m2 > 0).astype(np.uint8) * 255), **extra)
+
+
 def load_case_3d_rgb(case, dst_base, dsize=(512, 512), depth_model=None, focal_length=550.0):
     """a GeoBench-3D case whose coarse edit is built HERE from the RGB image and a 3-D transform instead of being read from disk
     (freefine_batch_infer_3d_depth.py:121 reads coarse3d_depth_anything/...png).  A NON-PARITY EXTENSION, not a restatement of the dataset's
     generator: evaluation/FreeFine/get_3d_transform_correspondence.py:217-251 renders those files through the GeoDiffuser warp
     (`get_transformed_mask`: translation edit_param / 512 in world units composed as T.S.Rx.Ry.Rz, splatting radius 1.3, 15 points per
-    pixel, depth from get_depth(translate_factor=0.0)), whose modules are not in the reference tree; here the cloud goes through
-    freefine_amd.warp3d (the pytorch3d splat of geo_utils.py:427-528: radius 1.5 px, K = 5), the translation is read as PIXELS at the 512
+    pixel, depth from get_depth(translate_factor=0.0)) -- that warp is built too, as an opt-in: finish_case_3d_geo / warp="geodiffuser" --; here the cloud
+    goes through freefine_amd.warp3d.coarse_edit_3d (the pytorch3d splat of geo_utils.py:427-528: radius 1.5 px, K = 5), the translation is read as PIXELS at the 512
     reference size at the object's mean depth (warp3d pixel_translation) and the depth is pushed back by 0.1 max.  Coarse images and target
     masks therefore differ systematically from the dataset's coarse3d_depth_anything files; use --variant 3d_depth to reproduce those.
     edit_param = [tx, ty, tz, rx, ry, rz (degrees), sx, sy, sz].  = read_case_3d_rgb (host) + finish_case_3d_rgb (device)."""
@@ -352,18 +395,21 @@ def warm_and_sync(model, batch, params, dsize=(512, 512), variant="2d", src=0):
 
 
 def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True, verbose=True, dsize=(512, 512), variant="2d", depth_model=None,
-        device_prep=False, save_correspondence=False):
+        device_prep=False, save_correspondence=False, warp="p3d"):
     """edit every case of the variant's annotation file that this rank owns; rank 0 writes the variant's result JSON
     (2d: annotations_2d.json -> generated_results_freefine_2d.json; 3d_depth: annotations.json -> generated_results_freefine_depth.json).
     device_prep: the prefetch thread only reads and decodes; resizes and the coarse edit run on the device (DevicePrep) on this thread, between batches.
     save_correspondence (variant 3d_rgb only): every case's correspondence map and visibility image are written under <dst_base>/Geo-Bench-3D/
     (warp3d.save_correspondence: correspondence/<da>/<ins>/<edit>.npy -- the path metrics.calculate_md derives from the case's gen_img_path -- and
     correspondence_visible/...png) on this thread, next to where the result is saved.
+    warp (variant 3d_rgb only): "p3d", today's point-cloud warp (finish_case_3d_rgb), or "geodiffuser", the reference's own step 2 (finish_case_3d_geo:
+    the coarse image, target mask, draw mask = md_mask and correspondence map the dataset's generator renders; no visibility image).
     Returns the merged result list (on every rank)."""
     from . import dist as FD
     from . import warp3d
     if save_correspondence and variant != "3d_rgb":
         raise ValueError(f"save_correspondence: only the 3d_rgb variant builds its own warp (variant = {variant!r})")
+    _check_warp(warp, variant)
     V = VARIANTS[variant]
     params = dict(V["params"], **(params or {}))
     seed = params.pop("seed")
@@ -385,6 +431,8 @@ def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True
         cases = [p[0] for p in pending]
         inputs = [p[1] for p in pending]
         maps = [(i.pop("correspondence", None), i.pop("correspondence_visible", None)) for i in inputs]      # not inputs of the edit
+        for i in inputs:
+            i.pop("md_mask", None)
         if len(inputs) == 1:
             kw = {k: v for k, v in inputs[0].items() if k not in ("ori_img", "ori_mask", "coarse_input", "target_mask", "guidance_text")}
             imgs = [model.FreeFine_generation(inputs[0]["ori_img"], inputs[0]["ori_mask"], inputs[0]["coarse_input"], inputs[0]["target_mask"],
@@ -411,12 +459,17 @@ def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True
     else:
         prep = HostPrep
         loader = {"2d": load_case, "3d_depth": load_case_3d_depth, "3d_rgb": read_case_3d_rgb}[variant]
+    if warp == "geodiffuser":      # the warp resizes the decoded files itself, the reference's way
+        loader = lambda c, b, d: read_case_3d_rgb(c, b, d, prep=None)      # noqa: E731
     try:
         for case, inputs, err in _prefetch(mine, dst_base, 2 * batch, dsize, loader):
             if err is None and (inputs.get("_raw_3d_rgb") or inputs.get("_raw")):
                 try:
                     if inputs.get("_raw_3d_rgb"):
-                        inputs = finish_case_3d_rgb(inputs, depth_model, prep=prep, correspondence=save_correspondence)
+                        if warp == "geodiffuser":
+                            inputs = finish_case_3d_geo(inputs, depth_model, prep=prep, correspondence=save_correspondence)
+                        else:
+                            inputs = finish_case_3d_rgb(inputs, depth_model, prep=prep, correspondence=save_correspondence)
                     else:
                         inputs = {"2d": finish_case_2d, "3d_depth": finish_case_3d_depth}[inputs["_raw"]](inputs, prep)
                 except Exception as e:  # noqa: BLE001 -- reported with the case attached, like a failed read
@@ -445,17 +498,46 @@ def run(model, dst_base, batch=4, params=None, rank=0, world=1, check_exist=True
     return merged
 
 
-def prepare_3d(dst_base, depth_model, rank=0, world=1, dsize=(512, 512), check_exist=True, verbose=True):
+def prepare_3d(dst_base, depth_model, rank=0, world=1, dsize=(512, 512), check_exist=True, verbose=True, warp="p3d"):
     """Step 2 of the 3-D run without the diffusion edit (run_script_3D.sh "Step2", evaluation/FreeFine/get_3d_transform_correspondence.py:207-289): for
     every case of annotations.json that this rank owns (sharded like run) the coarse image Geo-Bench-3D/coarse3d_depth_anything_rgb/<da>/<ins>/<edit>.png,
     the target mask Geo-Bench-3D/mesh_mask/... and the correspondence map (warp3d.save_correspondence: Geo-Bench-3D/correspondence/....npy and
-    correspondence_visible/....png).  A case whose three files exist is skipped (check_exist).  A NON-PARITY EXTENSION, not a restatement of the
-    dataset's generator, in the words of load_case_3d_rgb: the reference renders these files through the GeoDiffuser warp, whose modules are not in the
-    reference tree (hence the folder's own name: coarse3d_depth_anything is the dataset's); its md_mask is not written.  -> the list of
-    dict(key, coarse_input_path, target_mask_path, correspondence_path) this rank wrote."""
+    correspondence_visible/....png).  A case whose three files exist is skipped (check_exist).  With the default warp a NON-PARITY EXTENSION, not a
+    restatement of the dataset's generator, in the words of load_case_3d_rgb: the reference renders these files through the GeoDiffuser warp (hence the
+    folder's own name: coarse3d_depth_anything is the dataset's); no md_mask is written.  -> the list of
+    dict(key, coarse_input_path, target_mask_path, correspondence_path) this rank wrote.
+    warp="geodiffuser": the reference's step 2 itself (finish_case_3d_geo / warp3d.geodiffuser_coarse_edit), written under the reference's names:
+    Geo-Bench-3D/coarse3d_depth_anything_blended/, mesh_mask/, md_mask/ and correspondence/ (no visibility image; every dict also has md_mask_path).
+    Neither warp ever writes into coarse3d_depth_anything/, the dataset's own folder."""
     from . import dist as FD
     from . import warp3d
+    _check_warp(warp)
     root = osp.join(dst_base, "Geo-Bench-3D")
+    if warp == "geodiffuser":
+        data = load_json(osp.join(dst_base, VARIANTS["3d_rgb"]["annotations"]))
+        if data is None:
+            raise FileNotFoundError(osp.join(dst_base, VARIANTS["3d_rgb"]["annotations"]))
+        cl = CaseList(data, osp.join(root, "coarse3d_depth_anything_blended"), check_exist=False)
+        done = []
+        for i in FD.shard_indices(len(cl), rank, world):
+            c = cl[i]
+            sub = (str(c["da_n"]), str(c["ins_id"]), f'{c["edit_ins"]}')
+            paths = [osp.join(root, tree, *sub) + ext for tree, ext in (("coarse3d_depth_anything_blended", ".png"), ("mesh_mask", ".png"), ("md_mask", ".png"),
+                                                                       ("correspondence", ".npy"))]
+            if check_exist and all(osp.exists(p) for p in paths):
+                continue
+            try:
+                inputs = finish_case_3d_geo(read_case_3d_rgb(c, dst_base, dsize, prep=None), depth_model, correspondence=True)
+            except Exception as e:  # noqa: BLE001 -- reported with the case attached, like run
+                if verbose:
+                    print(f'[geobench] skipped {"/".join(sub)}: {e}')
+                continue
+            wrote = warp3d.save_geodiffuser_case(root, *sub, inputs["coarse_input"], inputs["target_mask"], inputs["md_mask"], inputs["correspondence"])
+            assert wrote == paths
+            done.append(dict(key="/".join(sub), coarse_input_path=paths[0], target_mask_path=paths[1], md_mask_path=paths[2], correspondence_path=paths[3]))
+        if verbose:
+            print(f"[geobench] prepare_3d (geodiffuser): {len(done)} cases written")
+        return done
     coarse_dir, mask_dir = osp.join(root, "coarse3d_depth_anything_rgb"), osp.join(root, "mesh_mask")
     data = load_json(osp.join(dst_base, VARIANTS["3d_rgb"]["annotations"]))
     if data is None:

@@ -1342,6 +1342,78 @@ def dilate_u8(mask, k):
     return out
 
 
+def _square(t, what):
+    if t.ndim < 2 or t.shape[0] != t.shape[1]:
+        raise ValueError(f"{what}: the GeoDiffuser warp takes square images (the reference takes sqrt(N) for the side); got {tuple(t.shape)}")
+    return int(t.shape[0])
+
+
+def geo_project(depth_n, pose, focal):
+    """ffn_geo_project: depth_n fp32 [S, S] on the device (already normalised), pose 3 x 4 (or 4 x 4) on the host -> (tcoords fp32 [S, S, 3] =
+    (X_norm, Y_norm, Z), the reference's t_coords; proj fp32 [S * S, 4], the same points as the splat entry points read them)"""
+    lib = L.load()
+    S = _square(depth_n, "geo_project")
+    assert depth_n.dtype == torch.float32 and depth_n.is_contiguous() and depth_n.ndim == 2
+    m = [float(v) for v in torch.as_tensor(pose, dtype=torch.float32).reshape(-1)[:12]]
+    tcoords = torch.empty((S, S, 3), dtype=torch.float32, device=depth_n.device)
+    proj = torch.empty((S * S, 4), dtype=torch.float32, device=depth_n.device)
+    L.check(_timed("geo_project", 30.0 * S * S, 32.0 * S * S,
+                   lambda: lib.ffn_geo_project(_stream(), depth_n.data_ptr(), (CT.c_float * 12)(*m), float(focal), S, S, tcoords.data_ptr(), proj.data_ptr())),
+            "ffn_geo_project")
+    return tcoords, proj
+
+
+def splat_tile_lists(proj, radius, S):
+    """the tile lists of ffn_splat_bin for a square S x S image (count, exclusive scan, fill) -> (offs int32 [tiles + 1], list int32).  The scan's total is
+    read back: this call synchronises."""
+    lib = L.load()
+    n, tiles = int(proj.shape[0]), ((S + 15) // 16) ** 2
+    counts = torch.zeros(tiles, dtype=torch.int32, device=proj.device)
+    L.check(_timed("splat_bin", 0.0, 16.0 * n, lambda: lib.ffn_splat_bin(_stream(), 0, proj.data_ptr(), n, float(radius), S, S, counts.data_ptr(), None, None)),
+            "ffn_splat_bin(count)")
+    offs = torch.zeros(tiles + 1, dtype=torch.int32, device=proj.device)
+    offs[1:] = torch.cumsum(counts, 0)
+    lst = torch.empty(max(int(offs[-1].item()), 1), dtype=torch.int32, device=proj.device)
+    counts.zero_()
+    L.check(_timed("splat_bin", 0.0, 20.0 * n, lambda: lib.ffn_splat_bin(_stream(), 1, proj.data_ptr(), n, float(radius), S, S, counts.data_ptr(), offs.data_ptr(),
+                                                                       lst.data_ptr())), "ffn_splat_bin(fill)")
+    return offs, lst
+
+
+def splat_composite(proj, feat, offs, lst, radius, tau, K, S, round_half=True):
+    """ffn_splat_composite: proj fp32 [S * S, 4], feat fp32 [S * S, C] (C <= 8), the tile lists of splat_tile_lists, radius in NDC units -> fp32 [S, S, C]"""
+    lib = L.load()
+    assert proj.dtype == torch.float32 and feat.dtype == torch.float32 and proj.is_contiguous() and feat.is_contiguous() and feat.ndim == 2
+    if feat.shape[0] != S * S or proj.shape[0] != S * S:
+        raise ValueError(f"splat_composite: {S} x {S} pixels, {proj.shape[0]} points, {feat.shape[0]} feature rows: every pixel is a point")
+    C = int(feat.shape[1])
+    out = torch.empty((S, S, C), dtype=torch.float32, device=proj.device)
+    L.check(_timed("splat_composite", 0.0, 4.0 * S * S * (4 + 2 * C),
+                   lambda: lib.ffn_splat_composite(_stream(), proj.data_ptr(), feat.data_ptr(), offs.data_ptr(), lst.data_ptr(), float(radius), float(tau), int(K), C,
+                                                   S, S, 1 if round_half else 0, out.data_ptr())), "ffn_splat_composite")
+    return out
+
+
+def splat_ids(proj, offs, lst, radius, K, S):
+    """ffn_splat_ids on the same lists: int32 [S, S, K], the point ids splat_composite blends at each pixel in compositing order, -1 = empty"""
+    lib = L.load()
+    ids = torch.empty((S, S, int(K)), dtype=torch.int32, device=proj.device)
+    L.check(lib.ffn_splat_ids(_stream(), proj.data_ptr(), offs.data_ptr(), lst.data_ptr(), float(radius), int(K), S, S, ids.data_ptr()), "ffn_splat_ids")
+    return ids
+
+
+def mesh_cover(tcoords, obj):
+    """ffn_mesh_cover: tcoords fp32 [S, S, 3], obj uint8 [S, S] (nonzero = a vertex of the mask's mesh) -> uint8 [S, S], 1 where a pixel centre lies strictly
+    inside a projected triangle"""
+    lib = L.load()
+    S = _square(tcoords, "mesh_cover")
+    assert tcoords.dtype == torch.float32 and tcoords.is_contiguous() and obj.dtype == torch.uint8 and obj.is_contiguous() and tuple(obj.shape) == (S, S)
+    cover = torch.zeros((S, S), dtype=torch.uint8, device=tcoords.device)
+    L.check(_timed("mesh_cover", 0.0, 13.0 * S * S, lambda: lib.ffn_mesh_cover(_stream(), tcoords.data_ptr(), obj.data_ptr(), S, S, cover.data_ptr())),
+            "ffn_mesh_cover")
+    return cover
+
+
 def mask_bbox_u8(mask):
     """int64 numpy [B, 4] = (top, bottom, left, right) of the pixels whose channel 0 is nonzero, mask uint8 [B, H, W] or [B, H, W, C] on the device
     (ffn_mask_bbox_u8: one reduction, 16 bytes per case read back -- this call synchronises).  ValueError on an empty mask, like numpy's ys.min()."""

@@ -122,8 +122,8 @@ def point_cloud_warp(img, depth, transforms, focal_length_x, focal_length_y, mas
 def coarse_edit_3d(ori_img, ori_mask, depth, transforms, background, focal_length=550.0, splatting_radius=None, points_per_pixel=5,
                    device=None, pixel_translation=True, return_correspondence=False):
     """A coarse 3-D edit built from the RGB image and a transform instead of being read from disk (freefine_batch_infer_3d_depth.py:121 reads
-    `coarse3d_depth_anything/...png`, rendered by the GeoDiffuser warp of get_3d_transform_correspondence.py:217-251, which is not in the
-    reference tree): the object's pixels, lifted through `depth`, moved by `transforms` (translation in image pixels by default -- this
+    `coarse3d_depth_anything/...png`, rendered by the GeoDiffuser warp of get_3d_transform_correspondence.py:217-251: geodiffuser_coarse_edit
+    below): the object's pixels, lifted through `depth`, moved by `transforms` (translation in image pixels by default -- this
     module's own convention, an extension; see geobench.load_case_3d_rgb) and splatted over `background` (the inpainted scene).  NOT a
     restatement of the dataset's generator.  Returns (coarse uint8 [H, W, 3], target_mask uint8 {0, 255}), followed with return_correspondence by
     point_cloud_warp's `corr` and `visible` (the map of THIS warp, half-pixel offset included: it describes `coarse`).
@@ -136,6 +136,116 @@ def coarse_edit_3d(ori_img, ori_mask, depth, transforms, background, focal_lengt
     tgt = cov > 0
     coarse = np.where(tgt[:, :, None], img, background).astype(np.uint8)
     return (coarse, tgt.astype(np.uint8) * 255, *extra)
+
+
+def geodiffuser_pose(edit_param, centre, length=512):
+    """The pose the reference's step 2 applies to every point (float32 torch on the host, op for op): P = T(t) Sx Sy Sz Rx Ry Rz with t = edit_param[0:3] /
+    length (get_transformed_mask, evaluation/GeoDiffuser/GeoDiffuser/utils/ui_utils2.py:709-735, called at evaluation/FreeFine/
+    get_3d_transform_correspondence.py:233-251), moved to the object's centre: T(-c)^-1 P T(-c) (warp_utils.py:427-437).  -> float32 [4, 4]"""
+    e = [float(v) for v in edit_param]
+    P = torch.eye(4).float()
+    tr = torch.eye(4)
+    for a in range(3):
+        tr[a, 3] += e[a] / length
+    P = P @ tr.type_as(P)
+    for a in range(3):
+        if e[6 + a] != 1.0:
+            s = torch.eye(4).type_as(P)
+            s[a, a] = e[6 + a]
+            P = P @ s
+    for a in range(3):
+        if e[3 + a] != 0.0:
+            r = np.radians(e[3 + a])
+            c, s = np.cos(r), np.sin(r)
+            R = [[[1, 0, 0, 0], [0, c, -s, 0], [0, s, c, 0], [0, 0, 0, 1]],
+                 [[c, 0, s, 0], [0, 1, 0, 0], [-s, 0, c, 0], [0, 0, 0, 1]],
+                 [[c, -s, 0, 0], [s, c, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]]][a]
+            P = P @ torch.tensor(R, dtype=torch.float64).type_as(P)
+    back = torch.eye(4).float()
+    back[:3, 3] += -torch.as_tensor(centre, dtype=torch.float32).cpu()
+    return (back.inverse() @ P @ back).float()
+
+
+def geodiffuser_coarse_edit(img_u8, mask, depth, edit_param, background, focal_length=550, radius=1.3, tau=1.0, points_per_pixel=15, device=None,
+                            return_stages=False):
+    """Step 2 of the reference's GeoBench-3D preparation on the HIP kernels of csrc/geowarp.h: the GeoDiffuser warp that renders the dataset's
+    coarse3d_depth_anything_blended/, mesh_mask/, md_mask/ and correspondence/ (evaluation/FreeFine/get_3d_transform_correspondence.py:207-289 ->
+    get_transformed_mask / project_image_latest, evaluation/GeoDiffuser/GeoDiffuser/utils/ui_utils2.py:685-743, 504-593; get_transform_coordinates,
+    vis_utils.py:404-479; forward_splatting_pytorch3d_warp and the SynSin splat, warp_utils.py:407-492, 28-176; the mask mesh, :235-399).
+    img_u8 uint8 [S, S, 3], mask [S, S] (> 0 = object; splatted as 0 / 255 like the reference's mask image), depth float [S, S] as the depth network
+    gives it (normalised here), edit_param = [tx, ty, tz (pixels of a 512 image: / 512), rx, ry, rz (degrees), sx, sy, sz], background uint8 [S, S, 3].
+    EVERY pixel is lifted and moved (not only the object's); the mask is one more splatted feature.  Square images only (ValueError otherwise).
+    -> (coarse uint8 [S, S, 3] = where(target_mask, splat * 255 -> uint8, background); target_mask bool [S, S] = warped mask > 0.5, what the script saves as
+    mesh_mask; mesh_projected bool [S, S], the projected mask mesh; md_mask = mesh_projected outside target_mask; correspondence float32 [S, S, 2], last
+    axis (x, y), the reference's denormalize_coordinates of t_coords in its on-disk order).  return_stages: followed by a dict of the device's intermediates.
+    PINNED to the reference's code: pose, t_coords and the mesh's triangles.  NOT pinned: the point and mesh rasterisers (pytorch3d is absent; they
+    restate its published kernels and are held to tests/geowarp_ref.py).  Out of scope: the GeoDiffuser diffusion edit, the softsplat / cupy path."""
+    from . import ops
+    dev = _device(device)
+    depth = np.asarray(depth)
+    if depth.ndim != 2 or depth.shape[0] != depth.shape[1]:
+        raise ValueError(f"geodiffuser_coarse_edit: square images only (the reference takes sqrt(N) for the side); depth is {depth.shape}")
+    S = depth.shape[0]
+    m2 = np.asarray(mask)
+    m2 = m2 if m2.ndim == 2 else m2[:, :, 0]
+    if np.asarray(img_u8).shape != (S, S, 3) or m2.shape != (S, S) or np.asarray(background).shape != (S, S, 3):
+        raise ValueError(f"geodiffuser_coarse_edit: image {np.asarray(img_u8).shape}, mask {m2.shape}, background {np.asarray(background).shape} for a depth of {depth.shape}")
+    K = int(points_per_pixel)
+    f = float(focal_length)
+    with torch.cuda.device(dev):
+        d = torch.as_tensor(np.ascontiguousarray(depth), dtype=torch.float32).to(dev)
+        if float(d.sum()) == 0.5 * d.numel():                              # the constant-depth case (vis_utils.py:410-411)
+            d = torch.full_like(d, 0.5)
+        else:
+            d = d / (d.max() + 1e-8)
+            d[d > 0.95] = 1.0
+        d = d.contiguous()
+        m = torch.as_tensor(np.ascontiguousarray(m2)).to(dev) > 0
+        obj = (m & (d < 0.95))
+        if not bool(obj.any()):
+            raise ValueError("geodiffuser_coarse_edit: no pixel of the mask is nearer than 0.95 of the depth range: the object has no centre")
+        # pixel2cam (warp_utils.py:738-747) for the centre only; the kernel lifts every pixel again
+        ar = torch.arange(S, dtype=torch.float32, device=dev)
+        c = S / 2.0
+        lin = ar * (1.0 / f) + (-c / f)
+        cam = torch.stack([lin[None, :] * d, lin[:, None] * d, d], 0)
+        centre = cam[:, obj].mean(-1)
+        pose = geodiffuser_pose(edit_param, centre)
+        tcoords, proj = ops.geo_project(d, pose[:3], f)
+        r = float(radius) / float(S) * 2.0
+        img = torch.as_tensor(np.ascontiguousarray(img_u8)).to(dev)
+        feat = torch.cat([img.reshape(-1, 3).float() / 255.0, m.reshape(-1, 1).float() * 255.0], 1).contiguous()
+        offs, lst = ops.splat_tile_lists(proj, r, S)
+        out = ops.splat_composite(proj, feat, offs, lst, r, tau, K, S, round_half=True)
+        cover = ops.mesh_cover(tcoords, obj.to(torch.uint8).contiguous())
+        # `(image_warped...numpy() * 255.0).astype("uint8")`, ui_utils2.py:541: a float16 array times a Python scalar stays float16, so the product is
+        # rounded to fp16 once more before it is truncated (`out` holds fp16 values: .half() is exact)
+        p_image = (out[..., :3].half() * 255.0).to(torch.uint8)
+        tmask = out[..., 3].to(torch.uint8).double() / 255.0 > 0.5         # :553-556
+        bg = torch.as_tensor(np.ascontiguousarray(background)).to(dev)
+        coarse = torch.where(tmask[..., None], p_image, bg)
+        corr = (tcoords[..., :2] + 1.0) / 2.0 * (S - 1)
+        mesh = cover > 0
+        res = (coarse.cpu().numpy(), tmask.cpu().numpy(), mesh.cpu().numpy(), (mesh & ~tmask).cpu().numpy(), corr.cpu().numpy())
+        if return_stages:
+            res += (dict(depth_n=d, obj=obj, pose=pose, tcoords=tcoords, proj=proj, offs=offs, list=lst, composite=out, feat=feat, radius=r),)
+    return res
+
+
+def save_geodiffuser_case(root, da_n, ins_id, edit_ins, coarse, target_mask, md_mask, corr):
+    """One case of the reference's step 2 under the reference's names (get_3d_transform_correspondence.py:194-203, 253-288): <root>/
+    coarse3d_depth_anything_blended/<da>/<ins>/<edit>.png, mesh_mask/...png, md_mask/...png, correspondence/...npy.  Never the dataset's own
+    coarse3d_depth_anything/.  -> the four paths"""
+    from PIL import Image
+    sub = os.path.join(str(da_n), str(ins_id))
+    paths = []
+    for tree, arr in (("coarse3d_depth_anything_blended", np.asarray(coarse, np.uint8)), ("mesh_mask", (np.asarray(target_mask) > 0).astype(np.uint8) * 255),
+                      ("md_mask", (np.asarray(md_mask) > 0).astype(np.uint8) * 255)):
+        os.makedirs(os.path.join(root, tree, sub), exist_ok=True)
+        paths.append(os.path.join(root, tree, sub, f"{edit_ins}.png"))
+        Image.fromarray(arr).save(paths[-1])
+    paths.append(save_correspondence(root, da_n, ins_id, edit_ins, corr)[0])
+    return paths
 
 
 def save_correspondence(root, da_n, ins_id, edit_ins, corr, visible=None):

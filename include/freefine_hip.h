@@ -290,6 +290,31 @@ int ffn_splat_render(void* stream, const float* proj, const float* rgb, const in
 int ffn_splat_ids(void* stream, const float* proj, const int* offs, const int* list, float radius, int K, int W, int H, int* ids);
 int ffn_splat_correspond(void* stream, const float* proj, const int* idx, int n, int W, int H, const int* ids, int K, float* map, uint8_t* visible);
 
+/* ---- the GeoDiffuser warp (ABI version 13): step 2 of the reference's GeoBench-3D preparation -----------------------------------
+ * evaluation/FreeFine/get_3d_transform_correspondence.py:207-289 through evaluation/GeoDiffuser/GeoDiffuser/utils (ui_utils2.py:504-593, 685-743;
+ * vis_utils.py:404-479; warp_utils.py:28-176, 235-298, 304-399, 407-492, 599-645).  Square images only (the reference takes sqrt(N) for the side).
+ * PINNED to the reference's code: the coordinates of ffn_geo_project and the triangle topology of ffn_mesh_cover.  NOT pinned: the two rasterisers
+ * (pytorch3d's rasterize_points and rasterize_meshes, absent from the build image), which restate pytorch3d's published kernels.
+ *   ffn_geo_project    every pixel (i, j) of the S x S image: cam = K^-1 (j, i, 1) depth[i][j] with K = (f, f, S/2, S/2); p = pose[:, :3] cam + pose[:, 3]
+ *                      (pose: 12 floats in HOST memory, 3 x 4 row-major); (X, Y, Z') = K p; Z = max(Z', 1e-3); tcoords[S][S][3] = (2 (X / Z) / (S - 1) - 1,
+ *                      2 (Y / Z) / (S - 1) - 1, Z), the reference's t_coords, whose first two channels are the correspondence map; proj[S*S][4] =
+ *                      (-X_norm, -Y_norm, Z, 0), the same point as ffn_splat_bin / ffn_splat_ids read it (warp_utils.py:90-91).  depth is already
+ *                      normalised (vis_utils.py:410-423) by the caller.
+ *   ffn_splat_composite  out[S][S][C] (fp32) from feat[n][C] over the tile lists of ffn_splat_bin (n = S*S points, radius in NDC units = radius_px / S * 2):
+ *                      the selection of ffn_splat_render (the K nearest by z among the points with d^2 < r^2, ties by point id, points with z < 0
+ *                      dropped -- pytorch3d leaves the order of equal z unpinned), alpha = (1 - sqrt(clamp(d^2 / r^2, 1e-3, 1)))^tau, front-to-back
+ *                      alpha_composite; round_half != 0 rounds the result once through fp16 (the reference returns `.to(torch.half)`).
+ *   ffn_mesh_cover     cover[S][S] (uint8; the caller zeroes it, the kernel only ever stores 1): the pixel centre lies strictly inside (all three
+ *                      barycentric coordinates > 0) a projected triangle of the mask's mesh: per 2 x 2 pixel quad the triangles (tl, tr, bl) and
+ *                      (bl, tr, br) of create_triangles, each present when its own three vertices have mask != 0; vertices = tcoords.  Faces of
+ *                      |area| <= 1e-8 or entirely behind z = 0 are skipped; no back-face culling (rasterize_meshes at blur radius ~ 0).
+ * All three: no allocation, no sync, the caller's stream; FFN_EINVAL before any launch on a null pointer, H != W, a side beyond 4096, C outside 1 .. 8,
+ * K outside 1 .. 32, radius, tau or focal <= 0. */
+int ffn_geo_project(void* stream, const float* depth, const float* pose, float focal, int H, int W, float* tcoords, float* proj);
+int ffn_splat_composite(void* stream, const float* proj, const float* feat, const int* offs, const int* list, float radius, float tau, int K,
+                        int C, int H, int W, int round_half, float* out);
+int ffn_mesh_cover(void* stream, const float* tcoords, const uint8_t* mask, int H, int W, uint8_t* cover);
+
 /* ---- normalisation ------------------------------------------------------------------------------------------- */
 /* `silu` of ffn_groupnorm / ffn_gn_apply is a flag word: FFN_NORM_SILU applies SiLU; FFN_NORM_OUT_PAIR (fp32 input only) writes y as the
  * bf16 PAIR rows [B*HW][2C] an FFN_BF16X3 GEMM reads (layout: FFN_BF16X3 above; no separate ffn_split_pair pass).  ffn_layernorm_pair: the same for LayerNorm. */

@@ -910,10 +910,105 @@ def run_g16():
     assert os.path.getsize(path) < 1_000_000
 
 
+# --------------------------------------------------------------------------------------------------------------
+# G18: the GeoDiffuser warp's coordinates and mesh topology (step 2 of the reference's GeoBench-3D preparation)
+# --------------------------------------------------------------------------------------------------------------
+def import_warp_utils():
+    """evaluation/GeoDiffuser/GeoDiffuser/utils/warp_utils.py with cupy (softsplat's) and pytorch3d stubbed: the coordinate functions and the triangle
+    builder run on the CPU; the two pytorch3d rasterisers cannot."""
+    import types
+
+    class Anything(types.ModuleType):
+        def __getattr__(self, name):
+            if name.startswith("__"):
+                raise AttributeError(name)
+            return lambda *a, **k: (a[0] if len(a) == 1 and callable(a[0]) and not k else (lambda f: f))
+
+    for name in ("cupy", "pytorch3d", "pytorch3d.structures", "pytorch3d.renderer", "pytorch3d.renderer.points", "pytorch3d.renderer.mesh",
+                 "pytorch3d.renderer.mesh.rasterizer"):
+        sys.modules.setdefault(name, Anything(name))
+    root = os.path.join(RH.REF, "evaluation", "GeoDiffuser")
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import importlib.util
+    for pkg, sub in (("GeoDiffuser", "GeoDiffuser"), ("GeoDiffuser.utils", os.path.join("GeoDiffuser", "utils"))):      # bare packages: their __init__ is not run
+        if pkg not in sys.modules:
+            m = types.ModuleType(pkg)
+            m.__path__ = [os.path.join(root, sub)]
+            sys.modules[pkg] = m
+    spec = importlib.util.spec_from_file_location("GeoDiffuser.utils.warp_utils", os.path.join(root, "GeoDiffuser", "utils", "warp_utils.py"))
+    W = importlib.util.module_from_spec(spec)
+    sys.modules[spec.name] = W
+    spec.loader.exec_module(W)
+    return W
+
+
+def run_g18():
+    """For every case of tests/geowarp_ref.py: the composed pose, t_coords (the reference's fp32, on the CPU) and the face list, by the reference's own
+    pixel2cam, translateMatrixFromVector, rotateAxis, cam2pixel_vanilla, get_coordinate_array and create_triangles, called as
+    forward_splatting_pytorch3d_warp (warp_utils.py:407-457) and get_transformed_mask (ui_utils2.py:709-735) call them.  The depth normalisation and the
+    object mask (vis_utils.py:410-430: five numpy lines in a module that imports a display stack) are repeated here in float32.  Also stored:
+    e_ref = max |reference fp32 - fp64 restatement| over the points the Z clamp leaves alone, per case -- the size of single-precision error the GPU
+    test multiplies by geowarp_ref.MARGIN."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import geowarp_ref as GR
+    W = import_warp_utils()
+    out = {}
+    for name in GR.CASES:
+        img, mask, depth, bg, edit = GR.case_inputs(name)
+        S = depth.shape[0]
+        d = depth.astype(np.float32)
+        d = d / (d.max() + 1e-8)
+        d[d > 0.95] = 1.0
+        obj = ((d < 0.95) * 1.0) * mask >= 0.5
+        T = torch.eye(4).float()
+        tr = torch.eye(4)
+        for a in range(3):
+            tr[a, 3] += edit[a] / 512
+        T = T @ tr.type_as(T)
+        for a in range(3):
+            if edit[6 + a] != 1.0:
+                s = torch.eye(4).type_as(T)
+                s[a, a] = edit[6 + a]
+                T = T @ s
+        for a in range(3):
+            if edit[3 + a] != 0.0:
+                T = T @ W.rotateAxis(edit[3 + a], a).type_as(T)
+        K = np.array([[GR.FOCAL, 0, S / 2.0], [0, GR.FOCAL, S / 2.0], [0, 0, 1]])
+        dep = torch.from_numpy(d)[None, None].float()
+        intr = torch.from_numpy(K)[None].type_as(dep)
+        obj_t = (torch.tensor(obj)[None, None] >= 0.5) * 1.0
+        W.pixel_coords = None
+        cam = W.pixel2cam(dep, intr.inverse())
+        b, c, h, w = cam.shape
+        centre = torch.mean(cam.reshape(b, c, -1)[:, :, obj_t.reshape(1, 1, -1)[0, 0] >= 0.5], -1)
+        tt = W.translateMatrixFromVector(-centre[0]).repeat(b, 1, 1)
+        pose = (tt.inverse() @ T[None].type_as(dep) @ tt).float()
+        t = W.cam2pixel_vanilla(cam, pose[:, :3, :3], pose[:, :3, -1:], intr, norm_scale=True, return_z=True)[0].numpy()
+        gx, gy = W.get_indexing_grid((h - 1, w - 1))
+        fc = W.create_triangles(W.get_coordinate_array(obj_t), gx, gy).numpy()
+        dn = GR.normalise_depth(depth)
+        assert np.array_equal(GR.object_mask(dn, mask), obj)
+        t64, clamped = GR.project(dn, GR.compose_pose(dn, obj, edit), GR.FOCAL)
+        assert np.array_equal(fc, GR.faces(obj)), name
+        free = ~clamped & (t[..., 2] > 1e-3)
+        e_ref = np.abs(t - t64)[free].max()
+        out[name + "/e_rel"] = np.array((np.abs(t - t64) / np.maximum(1.0, np.abs(t64)))[free].max(), np.float64)      # the same, over max(1, |value|)
+        pose_err = np.abs(pose[0].numpy() - GR.compose_pose(dn, obj, edit)).max()
+        print(f"[G18] {name}: S {S}, object {int(obj.sum())} px, faces {len(fc)}, clamped {int(clamped.sum())}, in frame "
+              f"{int((np.abs(t[..., :2]).max(-1) <= 1).sum())}, e_ref {e_ref:.3e} (|t| max {np.abs(t64[free]).max():.1f}), pose err {pose_err:.2e}")
+        out[name + "/depth_n"], out[name + "/pose"], out[name + "/tcoords"], out[name + "/faces"] = d, pose[0].numpy(), t, fc.astype(np.int32)
+        out[name + "/e_ref"] = np.array(e_ref, np.float64)
+    path = os.path.join(GOLD, "g18_geodiffuser_coords.npz")
+    np.savez_compressed(path, **out)
+    print(f"[G18] {path}: {os.path.getsize(path)} bytes")
+    assert os.path.getsize(path) < 1_000_000
+
+
 if __name__ == "__main__":
-    only = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g6b", "g7", "g8", "g9", "g11", "g13", "g14", "g15", "g16"]
+    only = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g6b", "g7", "g8", "g9", "g11", "g13", "g14", "g15", "g16", "g18"]
     torch.set_grad_enabled(False)
-    A, Mo = RH.import_reference()
+    A, Mo = RH.import_reference() if set(only) & {"g1", "g3", "g4", "g5", "g9"} else (None, None)      # the pipeline's modules: only where a run takes them
     if "g1" in only:
         run_g1(A)
     if "g3" in only:
@@ -942,3 +1037,5 @@ if __name__ == "__main__":
         run_g15()
     if "g16" in only:
         run_g16()
+    if "g18" in only:
+        run_g18()
