@@ -17,6 +17,7 @@ ATT_HEAD_RULE, ATT_UNIFORM_SEL1, ATT_UNIFORM_SEL0, ATT_CAUSAL = 1, 2, 4, 8
 NORM_SILU, NORM_OUT_PAIR = 1, 2
 IMGPREP_MAX_SIDE = 4096      # FFN_IMGPREP_MAX_SIDE
 IMGPREP_MAX_TAPS = 2 * 3 * IMGPREP_MAX_SIDE + 1      # FFN_IMGPREP_MAX_TAPS
+BOX_NMS_MAX = 16384          # FFN_BOX_NMS_MAX
 KEEP_NONE, KEEP_SUM_LT128, KEEP_GT128 = 0, 1, 2
 
 
@@ -180,6 +181,8 @@ SYMBOLS = {
     "ffn_sam_patch_rows_pair": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ffn_hyper_masks": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "ffn_upsample_bicubic": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "ffn_upsample_bicubic_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f]),
+    "ffn_box_nms": (_i, [_vp, _vp, _vp, _i, _f]),
     "ffn_image_to_nhwc": (_i, [_vp, _i, _vp, _vp, _l, _i]),
     "ffn_nhwc_to_image": (_i, [_vp, _i, _vp, _vp, _i, _i, _i]),
 }

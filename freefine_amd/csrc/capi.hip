@@ -70,7 +70,7 @@ static int set_lds(K kernel, int bytes) {
     return FFN_OK;
 }
 
-extern "C" int ffn_version(void) { return 13; }      // 13: the GeoDiffuser warp of GeoBench-3D (ffn_geo_project, ffn_splat_composite, ffn_mesh_cover); 12: SIFT keypoints for Mean Distance (ffn_sift_base, ffn_gauss_blur_f32, ffn_decimate2_f32, ffn_sift_extrema, ffn_sift_refine_orient, ffn_sift_describe, ffn_knn2_u8; FFN_ENOSPC); 11: click-to-mask (ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic, FFN_ELT_GELU); 10: the correspondence map of the point-cloud warp (ffn_splat_ids, ffn_splat_correspond); 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
+extern "C" int ffn_version(void) { return 14; }      // 14: automatic mask generation (ffn_upsample_bicubic_stats, ffn_box_nms); 13: the GeoDiffuser warp of GeoBench-3D (ffn_geo_project, ffn_splat_composite, ffn_mesh_cover); 12: SIFT keypoints for Mean Distance (ffn_sift_base, ffn_gauss_blur_f32, ffn_decimate2_f32, ffn_sift_extrema, ffn_sift_refine_orient, ffn_sift_describe, ffn_knn2_u8; FFN_ENOSPC); 11: click-to-mask (ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic, FFN_ELT_GELU); 10: the correspondence map of the point-cloud warp (ffn_splat_ids, ffn_splat_correspond); 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;
@@ -1460,6 +1460,30 @@ extern "C" int ffn_upsample_bicubic(void* stream, const float* src, float* dst, 
     REQUIRE(H >= 1 && W >= 1 && H <= lim && W <= lim, "upsample_bicubic: destination %d x %d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE)", H, W, lim);
     fsam_bicubic(reinterpret_cast<hipStream_t>(stream), src, dst, mask, N, h, w, H, W);
     return check_launch("upsample_bicubic");
+}
+
+// ---- automatic mask generation: the statistics of the upsampled candidates, box NMS (kernels: sam.h, launches: imgprep.hip) ------------------------
+extern "C" __attribute__((visibility("hidden"))) void fsam_bicubic_stats(hipStream_t s, const float* src, int* stats, uint8_t* mask, int N, int h, int w, int H, int W,
+                                                                         float offset);
+extern "C" __attribute__((visibility("hidden"))) void fsam_box_nms(hipStream_t s, const float* boxes, unsigned long long* suppress, int M, float thresh);
+
+extern "C" int ffn_upsample_bicubic_stats(void* stream, const float* src, int32_t* stats, uint8_t* mask, int N, int h, int w, int H, int W, float offset) {
+    const int lim = FFN_IMGPREP_MAX_SIDE;
+    REQUIRE(src && stats, "upsample_bicubic_stats: null pointer");
+    REQUIRE(N >= 1 && N <= 65535, "upsample_bicubic_stats: N=%d outside 1 .. 65535", N);
+    REQUIRE(h >= 1 && w >= 1 && h <= lim && w <= lim, "upsample_bicubic_stats: source %d x %d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE)", h, w, lim);
+    REQUIRE(H >= 1 && W >= 1 && H <= lim && W <= lim, "upsample_bicubic_stats: destination %d x %d outside 1 .. %d (FFN_IMGPREP_MAX_SIDE)", H, W, lim);
+    REQUIRE(__builtin_isfinite(offset) && offset >= 0.f, "upsample_bicubic_stats: offset=%g must be finite and >= 0", (double)offset);
+    fsam_bicubic_stats(reinterpret_cast<hipStream_t>(stream), src, stats, mask, N, h, w, H, W, offset);
+    return check_launch("upsample_bicubic_stats");
+}
+
+extern "C" int ffn_box_nms(void* stream, const float* boxes, uint64_t* suppress, int M, float thresh) {
+    REQUIRE(boxes && suppress, "box_nms: null pointer");
+    REQUIRE(M >= 1 && M <= FFN_BOX_NMS_MAX, "box_nms: M=%d outside 1 .. %d (FFN_BOX_NMS_MAX)", M, FFN_BOX_NMS_MAX);
+    REQUIRE(__builtin_isfinite(thresh), "box_nms: thresh=%g is not finite", (double)thresh);
+    fsam_box_nms(reinterpret_cast<hipStream_t>(stream), boxes, reinterpret_cast<unsigned long long*>(suppress), M, thresh);
+    return check_launch("box_nms");
 }
 
 // ---- elementwise / resampling helpers of the depth front end ----------------------------------------------------------

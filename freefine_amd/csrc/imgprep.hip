@@ -1,7 +1,7 @@
 // Fifth translation unit of libfreefine_hip.so: the device image preparation of the DINOv2 feature metrics (imgprep.h) and the device case preparation of the
 // GeoBench harness (caseprep.h) and the image preparation, mask product and upsampling of click-to-mask (sam.h).  A unit of its own, like dift.hip, so that it compiles beside capi.hip; default code generation.  capi.o validates the arguments
 // (ffn_resize_pil_bilinear_u8, ffn_resize_pil_u8, ffn_vit_patch_rows, ffn_vit_patch_rows_pair; ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8,
-// ffn_mask_bbox_u8, ffn_coarse_edit_2d; ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic) and calls the hidden functions below; nothing here is exported.
+// ffn_mask_bbox_u8, ffn_coarse_edit_2d; ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic, ffn_upsample_bicubic_stats, ffn_box_nms) and calls the hidden functions below; nothing here is exported.
 #include <hip/hip_runtime.h>
 
 #include "../../include/freefine_hip.h"
@@ -118,4 +118,20 @@ extern "C" __attribute__((visibility("hidden"))) void fsam_hyper_masks(hipStream
 extern "C" __attribute__((visibility("hidden"))) void fsam_bicubic(hipStream_t s, const float* src, float* dst, uint8_t* mask, int N, int h, int w, int H, int W) {
     (void)hipGetLastError();
     hipLaunchKernelGGL(upsample_bicubic_kernel, dim3((unsigned)((W + SAM_THREADS - 1) / SAM_THREADS), (unsigned)H, (unsigned)N), dim3(SAM_THREADS), 0, s, src, dst, mask, h, w, H, W);
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fsam_bicubic_stats(hipStream_t s, const float* src, int* stats, uint8_t* mask, int N, int h, int w, int H, int W,
+                                                                         float offset) {
+    (void)hipGetLastError();
+    const dim3 maps((unsigned)((N + SAM_THREADS - 1) / SAM_THREADS)), blk(SAM_THREADS);
+    hipLaunchKernelGGL(bicubic_stats_init_kernel, maps, blk, 0, s, stats, N);
+    hipLaunchKernelGGL(upsample_bicubic_stats_kernel, dim3((unsigned)(H < SAM_STATS_ROW_BLOCKS ? H : SAM_STATS_ROW_BLOCKS), (unsigned)N), blk, 0, s, src, stats, mask, h, w, H,
+                       W, offset);
+    hipLaunchKernelGGL(bicubic_stats_finish_kernel, maps, blk, 0, s, stats, N);
+}
+
+extern "C" __attribute__((visibility("hidden"))) void fsam_box_nms(hipStream_t s, const float* boxes, unsigned long long* suppress, int M, float thresh) {
+    (void)hipGetLastError();
+    const unsigned nb = (unsigned)((M + SAM_WAVE - 1) / SAM_WAVE);
+    hipLaunchKernelGGL(box_nms_kernel, dim3(nb, nb), dim3(SAM_WAVE), 0, s, boxes, suppress, M, thresh);
 }

@@ -7,6 +7,9 @@
 //   hyper_masks_kernel           logits[n][m][pixel] = <hyper[n][m][:], up[n][pixel][:]>: the mask decoder's hyper_in @ upscaled.view(b, c, h w) on NHWC rows.
 //   upsample_bicubic_kernel      ATen's upsample_bicubic2d (align_corners = False, A = -0.75) of the logits to the image size, and the thresholded uint8 mask
 //                                from the very value that is stored.
+// and the two of automatic mask generation (HipEfficientSam.generate), whose cost is what happens to 3 x points^2 candidate maps at image size:
+//   upsample_bicubic_stats_kernel  the same bicubic values counted, not stored: per map the pixels >= 0, > +offset, > -offset and the box of the first
+//   box_nms_kernel                 the pairwise IoU > thresh bit matrix of score-ordered boxes, one 64 x 64 tile of pairs per workgroup
 //
 // Included after caseprep.h: floating-point contraction is OFF here too.  The no-resize rows are (byte / 255 - mean) / std bit for bit as torch evaluates
 // them, and the interpolations round every product and every sum as ATen's scalar code does.
@@ -155,14 +158,11 @@ __device__ __forceinline__ void sam_cubic_coeffs(float t, float* k) {
     k[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
 }
 
-// src [N][h][w] fp32 -> dst [N][H][W] fp32 and (mask != null) mask [N][H][W] = 255 (dst >= 0).  grid = (ceil(W / 256), H, N), one thread per output pixel.
-// Source coordinate scale (dst + 0.5) - 0.5 with scale = in / out in fp32, NOT clamped; the four tap indices per axis are clamped to the border; rows first
-// (each the sum of its four column taps), then the four rows, as ATen's upsample_bicubic2d sums.
-__global__ __launch_bounds__(SAM_THREADS) void upsample_bicubic_kernel(const float* __restrict__ src, float* __restrict__ dst, uint8_t* __restrict__ mask, int h, int w,
-                                                                      int H, int W) {
-    const int x = blockIdx.x * SAM_THREADS + threadIdx.x, y = blockIdx.y;
-    if (x >= W) return;
-    const float* s = src + (long)blockIdx.z * h * w;
+// The value of destination pixel (y, x) of a map s [h][w] resampled to H x W: ATen's upsample_bicubic2d.  Source coordinate scale (dst + 0.5) - 0.5 with
+// scale = in / out in fp32, NOT clamped; the four tap indices per axis are clamped to the border; rows first (each the sum of its four column taps), then
+// the four rows, as ATen sums.  The ONE place this value is computed: upsample_bicubic_kernel stores it, upsample_bicubic_stats_kernel counts it, and the
+// two cannot differ in a rounding.
+__device__ __forceinline__ float sam_bicubic_value(const float* __restrict__ s, int h, int w, int H, int W, int y, int x) {
     const float ry = ((float)h / (float)H) * ((float)y + 0.5f) - 0.5f, rx = ((float)w / (float)W) * ((float)x + 0.5f) - 0.5f;
     const float fy = floorf(ry), fx = floorf(rx);
     float ky[4], kx[4];
@@ -186,7 +186,137 @@ __global__ __launch_bounds__(SAM_THREADS) void upsample_bicubic_kernel(const flo
         for (int j = 0; j < 4; ++j) t = t + row[cx[j]] * kx[j];
         v = v + t * ky[i];
     }
+    return v;
+}
+
+// src [N][h][w] fp32 -> dst [N][H][W] fp32 and (mask != null) mask [N][H][W] = 255 (dst >= 0).  grid = (ceil(W / 256), H, N), one thread per output pixel.
+__global__ __launch_bounds__(SAM_THREADS) void upsample_bicubic_kernel(const float* __restrict__ src, float* __restrict__ dst, uint8_t* __restrict__ mask, int h, int w,
+                                                                      int H, int W) {
+    const int x = blockIdx.x * SAM_THREADS + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    const float v = sam_bicubic_value(src + (long)blockIdx.z * h * w, h, w, H, W, y, x);
     const long o = ((long)blockIdx.z * H + y) * W + x;
     dst[o] = v;
     if (mask) mask[o] = v >= 0.f ? 255 : 0;
+}
+
+// ---- automatic mask generation (freefine_amd/sam.py generate): what the point-grid pass wants from 3 x points^2 candidate maps at image size --------------
+#define SAM_STATS_ROW_BLOCKS 16      // workgroups per map: each strides over its rows and ends in at most 7 global atomics
+#define SAM_WAVE 64
+
+// stats int32 [N][8] = area, n_hi, n_lo, x_min, y_min, x_max, y_max, 0.  The three launches of one call: neutral elements, accumulation, empty maps -> 0 0 0 0.
+__global__ __launch_bounds__(SAM_THREADS) void bicubic_stats_init_kernel(int* __restrict__ stats, int N) {
+    const int n = blockIdx.x * SAM_THREADS + threadIdx.x;
+    if (n >= N) return;
+    int* st = stats + 8 * (long)n;
+    st[0] = st[1] = st[2] = 0;
+    st[3] = st[4] = 0x7fffffff;
+    st[5] = st[6] = -1;
+    st[7] = 0;
+}
+
+__global__ __launch_bounds__(SAM_THREADS) void bicubic_stats_finish_kernel(int* __restrict__ stats, int N) {
+    const int n = blockIdx.x * SAM_THREADS + threadIdx.x;
+    if (n >= N) return;
+    int* st = stats + 8 * (long)n;
+    if (st[0] == 0) st[3] = st[4] = st[5] = st[6] = 0;
+}
+
+// src [N][h][w] fp32 -> per map the counts of v >= 0, v > +offset, v > -offset and the extents of v >= 0 over the H x W values v that
+// upsample_bicubic_kernel would store; no fp32 image is written.  mask (may be null) [N][H][W] = 255 (v >= 0).  grid = (row blocks, N): a workgroup takes rows
+// blockIdx.x, + gridDim.x, .. in runs of 256 columns.  Everything accumulated is an integer, so the result does not depend on the order of execution: the counts
+// are wave ballots and population counts (uniform over the wave), the extents per-lane integer min / max folded across the wave by shuffles at the end; the four
+// waves meet in LDS and the workgroup issues 3 atomic adds and, where it saw a pixel of the mask, 4 atomic min / max.
+__global__ __launch_bounds__(SAM_THREADS) void upsample_bicubic_stats_kernel(const float* __restrict__ src, int* __restrict__ stats, uint8_t* __restrict__ mask, int h, int w,
+                                                                            int H, int W, float offset) {
+    __shared__ int part[SAM_THREADS / SAM_WAVE][7];
+    const long n = blockIdx.y;
+    const float* s = src + n * h * w;
+    const float lo_t = -offset;
+    int area = 0, n_hi = 0, n_lo = 0, x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1;
+    for (int y = blockIdx.x; y < H; y += gridDim.x) {
+        for (int xb = 0; xb < W; xb += SAM_THREADS) {           // uniform bounds: every lane reaches the ballots
+            const int x = xb + threadIdx.x;
+            bool on = false, hi = false, lo = false;
+            if (x < W) {
+                const float v = sam_bicubic_value(s, h, w, H, W, y, x);
+                on = v >= 0.f;
+                hi = v > offset;
+                lo = v > lo_t;
+                if (mask) mask[(n * H + y) * W + x] = on ? 255 : 0;
+                if (on) {
+                    x0 = x < x0 ? x : x0;
+                    x1 = x > x1 ? x : x1;
+                    y0 = y < y0 ? y : y0;
+                    y1 = y > y1 ? y : y1;
+                }
+            }
+            area += __popcll(__ballot(on));
+            n_hi += __popcll(__ballot(hi));
+            n_lo += __popcll(__ballot(lo));
+        }
+    }
+#pragma unroll
+    for (int d = SAM_WAVE / 2; d >= 1; d >>= 1) {
+        const int a = __shfl_xor(x0, d, SAM_WAVE), b = __shfl_xor(y0, d, SAM_WAVE), c = __shfl_xor(x1, d, SAM_WAVE), e = __shfl_xor(y1, d, SAM_WAVE);
+        x0 = a < x0 ? a : x0;
+        y0 = b < y0 ? b : y0;
+        x1 = c > x1 ? c : x1;
+        y1 = e > y1 ? e : y1;
+    }
+    const int wave = threadIdx.x / SAM_WAVE;
+    if (threadIdx.x % SAM_WAVE == 0) {
+        int* p = part[wave];
+        p[0] = area, p[1] = n_hi, p[2] = n_lo, p[3] = x0, p[4] = y0, p[5] = x1, p[6] = y1;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int k = 1; k < SAM_THREADS / SAM_WAVE; ++k) {
+        const int* p = part[k];
+        area += p[0], n_hi += p[1], n_lo += p[2];
+        x0 = p[3] < x0 ? p[3] : x0;
+        y0 = p[4] < y0 ? p[4] : y0;
+        x1 = p[5] > x1 ? p[5] : x1;
+        y1 = p[6] > y1 ? p[6] : y1;
+    }
+    int* st = stats + 8 * n;
+    if (area) atomicAdd(st + 0, area);
+    if (n_hi) atomicAdd(st + 1, n_hi);
+    if (n_lo) atomicAdd(st + 2, n_lo);
+    if (area) {
+        atomicMin(st + 3, x0);
+        atomicMin(st + 4, y0);
+        atomicMax(st + 5, x1);
+        atomicMax(st + 6, y1);
+    }
+}
+
+// boxes fp32 [M][4] XYXY, best first -> suppress uint64 [M][ceil(M / 64)]: bit j of row i = (j > i and iou(i, j) > thresh), torchvision's box arithmetic in fp32
+// (no "+ 1"; contraction is off, every operation rounds on its own): area = (x2 - x1)(y2 - y1), inter = max(min(x2) - max(x1), 0) max(min(y2) - max(y1), 0),
+// iou = inter / (area_i + area_j - inter).  0 / 0 is NaN and NaN > thresh is false: two zero-area boxes do not suppress each other.  grid = (column blocks,
+// row blocks), one wave per 64 x 64 tile of pairs: lane = row, the tile's 64 column boxes in LDS.  Tiles below the diagonal are written as zeros: the whole
+// matrix is defined by this launch.
+__global__ __launch_bounds__(SAM_WAVE) void box_nms_kernel(const float* __restrict__ boxes, unsigned long long* __restrict__ suppress, int M, float thresh) {
+    __shared__ float4 col[SAM_WAVE];
+    const int nb = gridDim.x, cb = blockIdx.x, rb = blockIdx.y;
+    const int i = rb * SAM_WAVE + threadIdx.x, jl = cb * SAM_WAVE + threadIdx.x;
+    if (cb >= rb && jl < M) col[threadIdx.x] = make_float4(boxes[4 * (long)jl], boxes[4 * (long)jl + 1], boxes[4 * (long)jl + 2], boxes[4 * (long)jl + 3]);
+    __syncthreads();
+    if (i >= M) return;
+    unsigned long long bits = 0ull;
+    if (cb >= rb) {
+        const float x1 = boxes[4 * (long)i], y1 = boxes[4 * (long)i + 1], x2 = boxes[4 * (long)i + 2], y2 = boxes[4 * (long)i + 3];
+        const float ai = (x2 - x1) * (y2 - y1);
+        const int cols = M - cb * SAM_WAVE < SAM_WAVE ? M - cb * SAM_WAVE : SAM_WAVE;
+        for (int k = 0; k < cols; ++k) {
+            if (cb * SAM_WAVE + k <= i) continue;
+            const float4 b = col[k];
+            const float aj = (b.z - b.x) * (b.w - b.y);
+            const float iw = fmaxf(fminf(x2, b.z) - fmaxf(x1, b.x), 0.f), ih = fmaxf(fminf(y2, b.w) - fmaxf(y1, b.y), 0.f);
+            const float inter = iw * ih;
+            const float iou = inter / ((ai + aj) - inter);
+            if (iou > thresh) bits |= 1ull << k;
+        }
+    }
+    suppress[(long)i * nb + cb] = bits;
 }

@@ -1578,6 +1578,52 @@ def upsample_bicubic(x, H, W, mask=False):
     return (out, m) if mask else out
 
 
+def upsample_bicubic_stats(x, H, W, offset, mask=False):
+    """fp32 [N, h, w] -> int32 [N, 8] = (area, n_hi, n_lo, x_min, y_min, x_max, y_max, 0) of the H x W image upsample_bicubic would return, which is not stored:
+    area = #(v >= 0), n_hi = #(v > offset), n_lo = #(v > -offset), the extents over v >= 0 (maxima inclusive; an empty map gives 0, 0, 0, 0); mask: also the
+    uint8 [N, H, W] = 255 (v >= 0) of upsample_bicubic(..., mask=True), bit for bit (ffn_upsample_bicubic_stats)"""
+    lib = L.load()
+    assert x.dtype == torch.float32 and x.ndim == 3 and x.is_contiguous()
+    N, h, w = x.shape
+    stats = torch.empty(N, 8, dtype=torch.int32, device=x.device)
+    m = torch.empty(N, H, W, dtype=torch.uint8, device=x.device) if mask else None
+    L.check(_timed("upsample_bicubic_stats_kernel", 0.0, 4.0 * x.numel() + 32.0 * N + (float(N) * H * W if mask else 0.0),
+                   lambda: lib.ffn_upsample_bicubic_stats(_stream(), x.data_ptr(), stats.data_ptr(), _p(m), N, h, w, H, W, float(offset))), "ffn_upsample_bicubic_stats")
+    return (stats, m) if mask else stats
+
+
+def nms_sweep(suppress):
+    """host: the bit matrix of ffn_box_nms as numpy uint64 [M, ceil(M / 64)] -> the rows greedy NMS keeps, ascending: row i unless an earlier KEPT row has bit i set"""
+    import numpy as np
+    removed = np.zeros(suppress.shape[1], dtype=np.uint64)
+    keep = []
+    for i in range(suppress.shape[0]):
+        if not (int(removed[i >> 6]) >> (i & 63)) & 1:
+            keep.append(i)
+            removed |= suppress[i]
+    return keep
+
+
+def box_nms(boxes, scores, thresh):
+    """boxes fp32 [M, 4] (x1, y1, x2, y2), scores [M] (device) -> int64 [K] (device): greedy non-maximum suppression by box IoU > thresh, as torchvision.ops.nms
+    defines it (no "+ 1" in the areas; zero-area boxes never suppress each other).  Order: torch.argsort(scores, descending=True, stable=True); the result indexes
+    the caller's boxes, best first.  The pairwise bit matrix is the device's (ffn_box_nms), the sweep over its rows the host's (nms_sweep)."""
+    import numpy as np
+    lib = L.load()
+    assert boxes.dtype == torch.float32 and boxes.ndim == 2 and boxes.shape[1] == 4 and scores.shape == (boxes.shape[0],) and scores.device == boxes.device
+    M = boxes.shape[0]
+    if M == 0:
+        return torch.empty(0, dtype=torch.int64, device=boxes.device)
+    order = torch.argsort(scores, descending=True, stable=True)
+    ranked = boxes[order].contiguous()
+    nb = (M + 63) // 64
+    sup = torch.empty(M, nb, dtype=torch.int64, device=boxes.device)          # the bits of uint64 words
+    L.check(_timed("box_nms_kernel", 20.0 * M * M / 2, 16.0 * M + 8.0 * M * nb, lambda: lib.ffn_box_nms(_stream(), ranked.data_ptr(), sup.data_ptr(), M, float(thresh))),
+            "ffn_box_nms")
+    keep = nms_sweep(sup.cpu().numpy().view(np.uint64))
+    return order[torch.as_tensor(keep, dtype=torch.int64, device=boxes.device)]
+
+
 def image_to_nhwc(img_u8, CP, dtype, out=None):
     """uint8 [B,H,W,3] -> dtype [B,HW,CP] in [-1,1]."""
     lib = L.load()

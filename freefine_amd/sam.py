@@ -9,6 +9,12 @@ reference's application turns two clicks into `ori_mask` with (src/demo/utils.py
               GEMMs + pixel shuffle, GroupNorm(1) + GELU between them -> hypernetwork product (ops.hyper_masks) -> IoU head -> bicubic upsampling to the image size
               (ops.upsample_bicubic, which also thresholds) -> the three masks sorted by predicted IoU.
     segment   both, and the best mask as uint8 255 / 0.
+    generate  the masks of everything in the image -- the `mask_pool` of the edit calls: the single-crop path of SamAutomaticMaskGenerator (source:
+              evaluation/GeoDiffuser/GeoDiffuser/segment_anything/automatic_mask_generator.py, utils/amg.py).  encode once; a grid of foreground clicks through
+              decode_low (predict up to the low-res logits) in batches; per candidate the predicted-IoU filter, then ops.upsample_bicubic_stats -- the bicubic values
+              counted at image size, not stored: area, the two counts of the stability score, the box -- the stability filter, ops.box_nms over all survivors, and
+              byte masks of the kept ones only.  Pinned to the reference's code: the point grid, the stability score, the boxes, XYWH and the order of the filters
+              (tests/golden/g19_amg.npz); restated from its definition: box NMS (torchvision is not installed).
 
 Keys projected from the fixed dense positional encoding (K pe, Q pe of the cross attentions) are computed once at load and enter as GEMM residuals.  torch is
 used for layout plumbing only (pixel shuffle, tiling the embedding per query, sorting three numbers per query).
@@ -173,6 +179,20 @@ def prepare_prompts(cfg, points, labels, input_hw):
     elif P < n:
         pts, lab = F.pad(pts, (0, 0, 0, n - P), value=-1.0), F.pad(lab, (0, n - P), value=-1)
     return pts.reshape(-1, n, 2), lab.reshape(-1, n)
+
+
+def build_point_grid(n_per_side):
+    """segment_anything/utils/amg.py build_point_grid: the n x n cell centres of the unit square, float64 [n n, 2] (x, y), x fastest"""
+    offset = 1 / (2 * n_per_side)
+    side = np.linspace(offset, 1 - offset, n_per_side)
+    return np.stack([np.tile(side[None, :], (n_per_side, 1)), np.tile(side[:, None], (1, n_per_side))], axis=-1).reshape(-1, 2)
+
+
+def box_xyxy_to_xywh(box):
+    """amg.py box_xyxy_to_xywh on one box of four numbers: (x1, y1, x2 - x1, y2 - y1) -- with the inclusive extents of a mask the width of a w-pixel box is w - 1"""
+    out = np.array(box, copy=True)
+    out[2], out[3] = out[2] - out[0], out[3] - out[1]
+    return out
 
 
 _ATTN = ("q_proj", "k_proj", "v_proj", "out_proj")
@@ -354,23 +374,30 @@ class HipEfficientSam:
         return masks[:, 1:], iou[:, 1:]                      # multimask output: the first mask token is the single-mask one
 
     @torch.no_grad()
+    def decode_low(self, embedding, points, labels, input_hw):
+        """predict up to the network's own outputs: embedding, points [B, Q, P, 2], labels [B, Q, P] and input_hw as predict takes them -> (low-res logits fp32
+        [B, Q, 3, 4 g, 4 g], predicted IoU [B, Q, 3]) in the network's output order (NOT sorted).  A query's rows do not depend on the queries beside it."""
+        cfg = self.cfg
+        pts, lab = prepare_prompts(cfg, points, labels, input_hw)
+        B, Q = np.asarray(labels).shape[:2]
+        assert embedding.shape[0] == B and embedding.dtype == torch.float32
+        nm = cfg.num_masks
+        with ops.batch_invariant():                          # a query's masks do not depend on the queries beside it
+            emb = embedding if Q == 1 else embedding[:, None].expand(-1, Q, -1, -1).reshape(B * Q, *embedding.shape[1:])
+            low, iou = self._decode(emb.contiguous(), self._tokens(pts, lab))
+        return low.contiguous().view(B, Q, nm, *low.shape[2:]), iou.reshape(B, Q, nm)
+
+    @torch.no_grad()
     def predict(self, embedding, points, labels, input_hw, output_hw=None, details=False):
         """embedding: encode()'s [B, n, D]; points [B, Q, P, 2] (x, y in pixels of the input_hw = (H, W) image; negative = absent), labels [B, Q, P] (1 point,
         2 box top-left, 3 box bottom-right, -1 absent) -> (mask logits fp32 [B, Q, 3, H', W'] at output_hw (default input_hw) sorted by predicted IoU descending,
         predicted IoU [B, Q, 3]); details: also (low-res logits [B, Q, 3, 4 g, 4 g], uint8 masks [B, Q, 3, H', W'] = 255 (logit >= 0)), sorted the same way, and
         the order itself [B, Q, 3] (indices into the network's three outputs)"""
-        cfg = self.cfg
-        pts, lab = prepare_prompts(cfg, points, labels, input_hw)
-        B, Q = np.asarray(labels).shape[:2]
-        assert embedding.shape[0] == B and embedding.dtype == torch.float32
+        low, iou = self.decode_low(embedding, points, labels, input_hw)
+        B, Q, nm = iou.shape
         Ho, Wo = output_hw if output_hw is not None else input_hw
-        nm = cfg.num_masks
-        with ops.batch_invariant():                          # a query's masks do not depend on the queries beside it
-            emb = embedding if Q == 1 else embedding[:, None].expand(-1, Q, -1, -1).reshape(B * Q, *embedding.shape[1:])
-            low, iou = self._decode(emb.contiguous(), self._tokens(pts, lab))
-            low = low.contiguous()
-            full, m8 = ops.upsample_bicubic(low.view(B * Q * nm, *low.shape[2:]), Ho, Wo, mask=True)
-        iou = iou.reshape(B, Q, nm)
+        with ops.batch_invariant():
+            full, m8 = ops.upsample_bicubic(low.view(B * Q * nm, *low.shape[3:]), Ho, Wo, mask=True)
         order = torch.argsort(iou, dim=-1, descending=True)
         pick = lambda t: torch.take_along_dim(t.view(B, Q, nm, *t.shape[-2:]), order[..., None, None], dim=2)
         out = (pick(full), torch.take_along_dim(iou, order, dim=2))
@@ -384,3 +411,60 @@ class HipEfficientSam:
         pts, lab = np.asarray(points, dtype=np.float32).reshape(1, 1, -1, 2), np.asarray(labels).reshape(1, 1, -1)
         m8 = self.predict(self.encode(img), pts, lab, img.shape[:2], details=True)[3]
         return m8[0, 0, 0].cpu().numpy()
+
+    @torch.no_grad()
+    def generate(self, image_u8, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.88, stability_score_thresh=0.95, stability_score_offset=1.0,
+                 box_nms_thresh=0.7, point_grid=None):
+        """uint8 [H, W, 3] image -> the masks of everything in it: the single-crop path of SamAutomaticMaskGenerator (crop_n_layers = 0, min_mask_region_area = 0;
+        segment_anything/automatic_mask_generator.py: generate, _process_crop, _process_batch), in its order:
+          1. encode once;
+          2. points = build_point_grid(points_per_side) * (W, H), or point_grid [n, 2] in the unit square in its place;
+          3. per batch of points_per_batch points, each one foreground click (label 1) of a query of its own: decode_low; the candidates point-major, then the
+             network's three outputs; keep predicted IoU > pred_iou_thresh; ops.upsample_bicubic_stats of the survivors at the image's size; stability =
+             n_hi / n_lo, the fp32 quotient of the two counts (0 / 0 = NaN fails); keep stability >= stability_score_thresh; boxes from the statistics.  As in
+             the reference a threshold <= 0 switches its filter off;
+          4. the survivors' low-res logits stay on the device;
+          5. ops.box_nms of all survivors by predicted IoU at box_nms_thresh;
+          6. the byte masks of the kept ones: ops.upsample_bicubic_stats(mask=True), in chunks.
+        -> records in NMS order (best predicted IoU first), each a dict: segmentation uint8 [H, W] 0 / 255 (the project's mask form: SAM returns bool), area (int),
+        bbox [x, y, w, h] (box_xyxy_to_xywh of the inclusive extents: w = x_max - x_min), predicted_iou, point_coords [[x, y]], stability_score.
+        Where this differs from SAM: a pixel belongs to a mask where its logit is >= 0 (predict's rule, src/demo/utils.py:94 of the reference), SAM's generator takes
+        > 0; area and bbox follow the bytes returned.  The filter of boxes near a crop's edge (_process_batch) is the empty filter for a single crop -- a box edge
+        near the crop's edge is near the image's edge -- and is not run.  The result does not depend on points_per_batch: decode_low is batch-invariant and every
+        later step is per candidate or over all of them."""
+        img = np.asarray(image_u8)
+        assert img.ndim == 3 and img.shape[-1] == 3 and img.dtype == np.uint8
+        H, W = img.shape[:2]
+        grid = build_point_grid(points_per_side) if point_grid is None else np.asarray(point_grid, dtype=np.float64).reshape(-1, 2)
+        points = grid * np.array([[W, H]], dtype=np.float64)
+        emb = self.encode(img)
+        nm, step = self.cfg.num_masks, int(points_per_batch)
+        assert 1 <= step * nm <= 65535
+        lows, ious, stabs, boxes, areas, coords = [], [], [], [], [], []
+        for at in range(0, len(points), step):
+            p = points[at:at + step]
+            low, iou = self.decode_low(emb, p[None, :, None, :], np.ones((1, len(p), 1), dtype=np.int64), (H, W))
+            low, iou_h, cand = low.view(len(p) * nm, *low.shape[3:]), iou.reshape(-1).cpu().numpy(), np.repeat(p, nm, axis=0)
+            keep = np.flatnonzero(iou_h > np.float32(pred_iou_thresh)) if pred_iou_thresh > 0.0 else np.arange(len(iou_h))
+            if len(keep) == 0:
+                continue
+            low = low[torch.as_tensor(keep, device=low.device)].contiguous()
+            st = ops.upsample_bicubic_stats(low, H, W, stability_score_offset).cpu().numpy()
+            with np.errstate(divide="ignore", invalid="ignore"):
+                stab = st[:, 1].astype(np.float32) / st[:, 2].astype(np.float32)
+            stable = np.flatnonzero(stab >= np.float32(stability_score_thresh)) if stability_score_thresh > 0.0 else np.arange(len(stab))
+            if len(stable) == 0:
+                continue
+            lows.append(low[torch.as_tensor(stable, device=low.device)])
+            keep = keep[stable]
+            ious.append(iou_h[keep]), stabs.append(stab[stable]), boxes.append(st[stable, 3:7]), areas.append(st[stable, 0]), coords.append(cand[keep])
+        if not lows:
+            return []
+        lows, ious, stabs, boxes, areas, coords = torch.cat(lows), np.concatenate(ious), np.concatenate(stabs), np.concatenate(boxes), np.concatenate(areas), np.concatenate(coords)
+        dev = lows.device
+        kept = ops.box_nms(torch.from_numpy(boxes.astype(np.float32)).to(dev), torch.from_numpy(ious).to(dev), box_nms_thresh)
+        lows, kept = lows[kept].contiguous(), kept.cpu().numpy()
+        chunk = min(max(1, (64 << 20) // (H * W)), 65535)     # byte masks of at most 64 MiB per launch
+        masks = np.concatenate([ops.upsample_bicubic_stats(lows[c:c + chunk], H, W, stability_score_offset, mask=True)[1].cpu().numpy() for c in range(0, len(kept), chunk)])
+        return [dict(segmentation=masks[r], area=int(areas[k]), bbox=box_xyxy_to_xywh(boxes[k]).tolist(), predicted_iou=float(ious[k]), point_coords=[coords[k].tolist()],
+                     stability_score=float(stabs[k])) for r, k in enumerate(kept)]

@@ -599,6 +599,29 @@ int ffn_sam_patch_rows_pair(void* stream, const uint8_t* src, void* out, int B, 
 int ffn_hyper_masks(void* stream, const float* up, const float* hyper, float* out, int N, int hw, int C, int M);
 int ffn_upsample_bicubic(void* stream, const float* src, float* dst, uint8_t* mask, int N, int h, int w, int H, int W);
 
+/* ---- automatic mask generation: what a point-grid pass wants from its candidate maps (ABI version 14; csrc/sam.h, HipEfficientSam.generate) ----------
+ * Reference: evaluation/GeoDiffuser/GeoDiffuser/segment_anything/automatic_mask_generator.py (_process_batch :266-321) and utils/amg.py (calculate_stability_score
+ * :156, batched_mask_to_box :303).  Both entries validate before any launch and refuse with FFN_EINVAL.
+ *
+ * The statistics entry: src fp32 [N][h][w] -> stats int32 [N][8] over the H x W values v that ffn_upsample_bicubic would store for the same arguments (the two
+ * kernels call one device function: v is the same bit pattern), WITHOUT storing them:
+ *     stats[n] = { area = #(v >= 0), n_hi = #(v > +offset), n_lo = #(v > -offset), x_min, y_min, x_max, y_max, 0 }
+ * area counts the bits of ffn_upsample_bicubic's byte mask; n_hi, n_lo compare strictly, as calculate_stability_score does (stability = n_hi / n_lo); the extents are
+ * those of the pixels with v >= 0, maxima inclusive as in batched_mask_to_box, and 0, 0, 0, 0 for an empty map.  stats is initialised by the entry itself (its
+ * previous content does not matter).  mask (may be NULL): uint8 [N][H][W] = 255 (v >= 0), else 0 -- the byte mask without the fp32 image.  All accumulation is in
+ * integers: the result does not depend on the order of execution.  Refused: null src / stats, N outside 1 .. 65535, a side outside 1 .. FFN_IMGPREP_MAX_SIDE,
+ * offset negative or not finite.
+ *
+ * The NMS entry: boxes fp32 [M][4] (x1, y1, x2, y2), ordered best first -> suppress uint64 [M][ceil(M / 64)], every word written: bit (j % 64) of word (j / 64) of
+ * row i is set iff j > i and iou(i, j) > thresh, with torchvision's box arithmetic in fp32, each operation rounded on its own:
+ *     area = (x2 - x1)(y2 - y1); inter = max(min(x2) - max(x1), 0) max(min(y2) - max(y1), 0); iou = inter / (area_i + area_j - inter)
+ * (no "+ 1"; two zero-area boxes give 0 / 0 = NaN, which is not > thresh: they do not suppress each other).  The greedy sweep -- keep row i unless an earlier KEPT
+ * row has bit i set -- is the caller's (freefine_amd/ops.py box_nms runs it on the host from the copied matrix).  Refused: null pointers, M outside
+ * 1 .. FFN_BOX_NMS_MAX, a thresh that is not finite. */
+#define FFN_BOX_NMS_MAX 16384
+int ffn_upsample_bicubic_stats(void* stream, const float* src, int32_t* stats, uint8_t* mask, int N, int h, int w, int H, int W, float offset);
+int ffn_box_nms(void* stream, const float* boxes, uint64_t* suppress, int M, float thresh);
+
 #ifdef __cplusplus
 }
 #endif
