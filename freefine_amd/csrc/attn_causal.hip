@@ -1,26 +1,28 @@
-// Third translation unit of libfreefine_hip.so: the kernels only the CLIP text tower needs (attention_causal.h: attn_causal_kernel in its three
-// arithmetic modes, embed_tokens_kernel), and the two small kernels behind the CLIP towers' projections (pool_layernorm_kernel, cosine_rows_kernel).  A unit of its own so that they compile beside capi.hip (which takes minutes) instead of lengthening it; default
-// code generation.  capi.o validates the descriptor, plans the launch and launches the kernel like every other.  No exported symbol: the getters have
-// hidden visibility.
-#include <hip/hip_runtime.h>
+// The text tower's unit of libfreefine_hip.so: the kernels only the CLIP text tower needs (attention_causal.h: attn_causal_kernel in its three
+// arithmetic modes, embed_tokens_kernel), and the two small kernels behind the CLIP towers' projections (pool_layernorm_kernel, cosine_rows_kernel).
+// Default code generation.  It exports the entries of its own kernels (ffn_embed_tokens, ffn_pool_layernorm, ffn_cosine_rows); attn_causal_kernel is
+// planned and launched by ffn_attn (capi_attn.hip), which reaches it through fcausal_kernel (attn_units.h).
 #include <limits.h>
 
+#include "capi_common.h"
 #include "attention_causal.h"
 #include "layernorm_row.h"
+#include "attn_units.h"
 
-// dtype: FFN_F32 / FFN_BF16 / FFN_BF16X3
-extern "C" __attribute__((visibility("hidden"))) void (*fcausal_kernel(int dtype))(ffn_attn_desc) {
+attn_kernel_t fcausal_kernel(int dtype) {
     return dtype == FFN_BF16 ? attn_causal_kernel<bf16, false> : (dtype == FFN_BF16X3 ? attn_causal_kernel<float, true> : attn_causal_kernel<float, false>);
 }
 
-extern "C" __attribute__((visibility("hidden"))) void fembed_launch(hipStream_t s, int bf16_out, const int* ids, const float* table, const float* pos, void* out,
-                                                                    long M, int S, int C, int V) {
+// ---- token + position embedding of the text tower ------------------------------------------------------------------------
+extern "C" int ffn_embed_tokens(void* stream, int dtype, const int* ids, const float* table, const float* pos, void* out, long M, int S, int C, int V) {
+    REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16 || dtype == FFN_BF16X3, "embed_tokens: bad dtype %d", dtype);
+    REQUIRE(ids && table && pos && out && aligned16(table) && aligned16(pos) && aligned16(out), "embed_tokens: null / unaligned pointer");
+    REQUIRE(M > 0 && S > 0 && V > 0 && C > 0 && C % 4 == 0 && M < (1l << 31), "embed_tokens: bad shape M=%ld S=%d C=%d V=%d (C %% 4 == 0)", M, S, C, V);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const long n4 = M * (C / 4);
-    long grid = (n4 + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    (void)hipGetLastError();
-    if (bf16_out) hipLaunchKernelGGL(embed_tokens_kernel<bf16>, dim3((unsigned)grid), dim3(256), 0, s, ids, table, pos, (bf16*)out, n4, S, C, V);
-    else hipLaunchKernelGGL(embed_tokens_kernel<float>, dim3((unsigned)grid), dim3(256), 0, s, ids, table, pos, (float*)out, n4, S, C, V);
+    if (dtype == FFN_BF16) LAUNCH(embed_tokens_kernel<bf16>, dim3(grid_for(n4)), dim3(256), 0, s, ids, table, pos, (bf16*)out, n4, S, C, V);
+    else LAUNCH(embed_tokens_kernel<float>, dim3(grid_for(n4)), dim3(256), 0, s, ids, table, pos, (float*)out, n4, S, C, V);
+    return check_launch("embed_tokens");
 }
 
 // ---- ffn_pool_layernorm: LayerNorm of ONE row per sequence -- row 0 (ids == nullptr: the image tower's class token) or the row at the first position holding
@@ -52,13 +54,20 @@ __global__ __launch_bounds__(64) void pool_layernorm_kernel(const T* __restrict_
 }
 
 // dtype FFN_F32 / FFN_BF16; pair (fp32 input only): the pair rows of ffn_layernorm_pair.  MAXCH as ffn_layernorm chooses it.
-extern "C" __attribute__((visibility("hidden"))) void fpool_ln_launch(hipStream_t s, int bf16_in, int pair, const void* x, const int* ids, void* y,
-                                                                      const float* gamma, const float* beta, int N, int S, int C, float eps) {
-    const int cch = C / (bf16_in ? 8 : 4);
-    (void)hipGetLastError();
-#define POOL_LN(T, MAXCH, PAIR) \
-    hipLaunchKernelGGL((pool_layernorm_kernel<T, MAXCH, PAIR>), dim3((unsigned)N), dim3(64), 0, s, (const T*)x, ids, (T*)y, gamma, beta, S, C, eps)
-    if (bf16_in) {
+extern "C" int ffn_pool_layernorm(void* stream, int dtype, const void* x, const int* ids, void* y, const float* gamma, const float* beta, int N, int S, int C,
+                                  float eps, int pair) {
+    REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16, "pool_layernorm: bad dtype %d", dtype);
+    REQUIRE(pair == 0 || (pair == 1 && dtype == FFN_F32), "pool_layernorm: pair output takes fp32 input (dtype %d, pair %d)", dtype, pair);
+    REQUIRE(x && y && gamma && beta, "pool_layernorm: null pointer");
+    REQUIRE(aligned16(x) && aligned16(y) && (reinterpret_cast<uintptr_t>(ids) & 3) == 0, "pool_layernorm: x, y must be 16-byte aligned, ids 4-byte aligned");
+    const int epc = dtype == FFN_F32 ? 4 : 8;
+    REQUIRE(N > 0 && S > 0 && C > 0 && C % epc == 0 && C / epc <= 64 * 6, "pool_layernorm: bad shape N=%d S=%d C=%d (C %% %d == 0, C <= %d)", N, S, C, epc,
+            64 * 6 * epc);
+    REQUIRE(!ids || S <= 96, "pool_layernorm: S=%d ids per sequence (at most 96)", S);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int cch = C / epc;
+#define POOL_LN(T, MAXCH, PAIR) LAUNCH((pool_layernorm_kernel<T, MAXCH, PAIR>), dim3((unsigned)N), dim3(64), 0, s, (const T*)x, ids, (T*)y, gamma, beta, S, C, eps)
+    if (dtype == FFN_BF16) {
         if (cch <= 128) POOL_LN(bf16, 2, false);
         else POOL_LN(bf16, 6, false);
     } else if (pair) {
@@ -69,6 +78,7 @@ extern "C" __attribute__((visibility("hidden"))) void fpool_ln_launch(hipStream_
         else POOL_LN(float, 6, false);
     }
 #undef POOL_LN
+    return check_launch("pool_layernorm");
 }
 
 // ---- ffn_cosine_rows: out[i] = <a_i, b_j> / (max(|a_i|, 1e-12) max(|b_j|, 1e-12)), j = i or 0 (one b row for all): the cosine of F.normalize'd rows.
@@ -98,7 +108,11 @@ __global__ __launch_bounds__(256) void cosine_rows_kernel(const float* __restric
     if (lane == 0) out[row] = ab / (fmaxf(sqrtf(aa), 1e-12f) * fmaxf(sqrtf(bb), 1e-12f));
 }
 
-extern "C" __attribute__((visibility("hidden"))) void fcosine_launch(hipStream_t s, const float* a, const float* b, float* out, int B, int P, int b_rows) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(cosine_rows_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, a, b, out, B, P, b_rows);
+extern "C" int ffn_cosine_rows(void* stream, const float* a, const float* b, float* out, int B, int P, int b_rows) {
+    REQUIRE(a && b && out, "cosine_rows: null pointer");
+    REQUIRE(aligned16(a) && aligned16(b) && (reinterpret_cast<uintptr_t>(out) & 3) == 0, "cosine_rows: a, b must be 16-byte aligned, out 4-byte aligned");
+    REQUIRE(B > 0 && P > 0 && P % 4 == 0, "cosine_rows: bad shape B=%d P=%d (P %% 4 == 0)", B, P);
+    REQUIRE(b_rows == 1 || b_rows == B, "cosine_rows: b has %d rows (1 or B=%d)", b_rows, B);
+    LAUNCH(cosine_rows_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, b, out, B, P, b_rows);
+    return check_launch("cosine_rows");
 }

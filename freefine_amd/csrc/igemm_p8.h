@@ -40,7 +40,7 @@
 // past M, and the zero padding of a convolution, encoded as offset 0x80000000) get ZEROS written to LDS by the range check (probed
 // on gfx950: tools/native/probe_bufload_lds.hip), so there is no zero page and no select.
 //
-// Restrictions (checked by the launcher, capi.hip): bf16; K % 64 == 0 and K >= 128 (conv: Cin % 64 == 0); N % BN == 0; alpha == 1;
+// Restrictions (checked by the launcher, pp_ok of capi_igemm.hip): bf16; K % 64 == 0 and K >= 128 (conv: Cin % 64 == 0); N % BN == 0; alpha == 1;
 // flags subset of {GEGLU (BN = 256)}; rowbias only with rows_per_batch >= 128; every operand < 2 GiB.
 #pragma once
 #include <type_traits>
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IgemmParams p, int 
     constexpr int NST = (SPLIT || TRANS || X3) ? FH * FN : (GEGLU ? FH * FN / 2 : FH * ((FN + 1) / 2));
     constexpr int OSZ = (X3 && !GEGLU) ? 4 : 2;         // bytes per output / residual element
     constexpr int OOB = (int)0x80000000;
-    // (BN = 128, round 6: the VAE's 128-channel 3x3 convolutions in split-bf16 mode -- two column fragments per wave, launched by capi.hip for X3 convolutions only)
+    // (BN = 128, round 6: the VAE's 128-channel 3x3 convolutions in split-bf16 mode -- two column fragments per wave, launched by capi_igemm.hip for X3 convolutions only)
     static_assert((BM == 256 || BM == 192) && (BN == 256 || BN == 320 || (BN == 128 && BM == 256 && X3 && AMODE == AMODE_CONV3 && !GEGLU && !SPLIT && !TRANS)), "tiles built for this kernel");
     static_assert(!GEGLU || FN % 2 == 0, "GEGLU pairs hidden / gate column blocks inside a wave");
 

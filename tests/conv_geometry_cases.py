@@ -166,8 +166,8 @@ def border_class(m, M, Hout, Wout):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# which kernel a forced configuration must run: csrc/capi.hip restated (pp_ok: lines 151-193, halo_bytes_for: 196-211, the tile list kCfg: 138-144,
-# candidates_for's extra conditions on halo and split-K candidates: 353-377) for the descriptors ops.conv3x3 builds from these cases
+# which kernel a forced configuration must run: csrc/capi_igemm.hip restated (pp_ok, halo_bytes_for, the tile list kCfg,
+# candidates_for's extra conditions on halo and split-K candidates) for the descriptors ops.conv3x3 builds from these cases
 # ---------------------------------------------------------------------------------------------------------------------
 HALO_CFGS = {9: (128, 320), 10: (256, 128), 11: (256, 256), 12: (128, 128)}
 PP_CFGS = {13: (256, 320), 14: (256, 256), 15: (192, 320), 16: (192, 256), 17: (256, 128)}

@@ -285,7 +285,7 @@ def test_igemm_kernel_choice_table():
     ]
     for dtype, d, want in rows:
         assert name(dtype, d) == f"void {want}({'ffn_igemm_desc, int' if 'igemm_pp' in want else 'ffn_igemm_desc'})", (dtype, d.M, d.N, d.K, d.conv, d.flags, want)
-    # forced rows: one 3x3 stride-1 convolution, B = 3, 32x32, Cin = 128, N = 320.  kCfg of csrc/capi.hip: (BM, BN, NWM, NWN), then the halo
+    # forced rows: one 3x3 stride-1 convolution, B = 3, 32x32, Cin = 128, N = 320.  kCfg of csrc/capi_igemm.hip: (BM, BN, NWM, NWN), then the halo
     # kernel's four tiles and the ping-pong kernel's five.  Every generic and halo tile is a candidate (M = 3072 is whole tiles of whole image
     # rows); of the ping-pong tiles the two 320 columns wide (N % 256 != 0; the 256x128 tile is for split-bf16 problems)
     kcfg = [(64, 64, 2, 2), (128, 64, 4, 2), (128, 128, 2, 4), (128, 128, 4, 4), (256, 128, 4, 4), (256, 256, 4, 4), (128, 320, 4, 4), (128, 160, 4, 2), (192, 320, 3, 4),

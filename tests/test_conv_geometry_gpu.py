@@ -17,7 +17,7 @@ Method:
                   image that is not turned into padding shows as NaN;
   configurations  bf16 / split-bf16 / fp8 cases run unforced and under ffn_igemm_force_config(cfg) for every cfg (fp32 is planned by rule: once), the K split
                   pinned (1, or 3 for the split-K cases).  First-use timing is off for the file, so ffn_igemm_kernel_name names the kernel launched;
-  eligibility     conv_geometry_cases.halo_eligible / pp_eligible restate halo_bytes_for / pp_ok of csrc/capi.hip: a forced halo / ping-pong configuration must
+  eligibility     conv_geometry_cases.halo_eligible / pp_eligible restate halo_bytes_for / pp_ok of csrc/capi_igemm.hip: a forced halo / ping-pong configuration must
                   run exactly where they say and must be refused (the launch then lands on igemm_glds_kernel) where they do not -- row bias below 128 rows
                   per image (class D), the halo of a 256-wide row piece (class E);
   ledger          every test ends by asserting that each kernel form ran on its class (REQUIRED), and that every generic tile was really launched: a forced
@@ -37,7 +37,7 @@ pytestmark = pytest.mark.gpu
 
 SENT, GUARD, PADC = 7.0, 300, 8
 MODES = ["f32", "bf16", "x3", "f8"]
-GENERIC_WAVES = [(2, 2), (4, 2), (2, 4), (4, 4), (4, 4), (4, 4), (4, 4), (4, 2), (3, 4)]          # kCfg of csrc/capi.hip: wave grid of the nine generic tiles
+GENERIC_WAVES = [(2, 2), (4, 2), (2, 4), (4, 4), (4, 4), (4, 4), (4, 4), (4, 2), (3, 4)]          # kCfg of csrc/capi_igemm.hip: wave grid of the nine generic tiles
 WIDE = ["256x320", "192x320", "256x256", "192x256"]
 LEDGER = collections.defaultdict(set)          # (class, form) -> geometries, over the whole file
 
@@ -81,7 +81,7 @@ def form_of(name, cin, mode):
     if mode == "x3":
         return "ring recomputing split-bf16 " + ("planes" if cin % 32 else "blocks")
     if mode == "bf16":
-        assert cin % 64, (name, "whole 64-channel chunks take the streaming loader (igemm_plan, csrc/capi.hip)")
+        assert cin % 64, (name, "whole 64-channel chunks take the streaming loader (igemm_plan, csrc/capi_igemm.hip)")
         return "ring recomputing bf16 (Cin % 64 != 0)"
     return "ring recomputing " + ("fp32" if mode == "f32" else "fp8")
 
@@ -155,7 +155,7 @@ def prepare(mode, o, gpu, Cin, Cout, guard_pix, pack=None):
 
 
 def expect_kernel(c, mode, variant, cfg, name, led):
-    """a forced halo / ping-pong configuration runs exactly where csrc/capi.hip's rules admit it; everything else these small problems run is igemm_glds_kernel"""
+    """a forced halo / ping-pong configuration runs exactly where csrc/capi_igemm.hip's rules admit it; everything else these small problems run is igemm_glds_kernel"""
     for table, pred, kern in ((G.HALO_CFGS, G.halo_eligible, "igemm_halo_kernel<bf16, "), (G.PP_CFGS, G.pp_eligible, "igemm_pp_kernel<")):
         if cfg in table:
             bm, bn = table[cfg]
@@ -281,7 +281,7 @@ def test_gaussian_pass(gpu, cls, mode):
 # class F: conv3x3_up2x (conv = 2, four sub-pixel classes + pixel shuffle) against upsample -> conv in fp64
 # ---------------------------------------------------------------------------------------------------------------------
 def conv2_tile(M, N, cfg):
-    """csrc/capi.hip: a forced ping-pong configuration where the tile applies (N % bn == 0, M >= bm; the 128-column tile never), else conv2_tile's first"""
+    """csrc/capi_igemm.hip: a forced ping-pong configuration where the tile applies (N % bn == 0, M >= bm; the 128-column tile never), else conv2_tile's first"""
     if cfg in G.PP_CFGS and G.PP_CFGS[cfg][1] != 128 and N % G.PP_CFGS[cfg][1] == 0 and M >= G.PP_CFGS[cfg][0]:
         return G.PP_CFGS[cfg]
     return next((bm, bn) for bn in (320, 256) for bm in (256, 192) if N % bn == 0 and M >= bm)

@@ -515,7 +515,7 @@ def test_kernels_are_deterministic(gpu):
     same(lambda: ops.attention(q, kt, vtt, heads, 0.125, loc, Sk=77), 3)
 
 
-# (BM, BN) of ffn_igemm's bf16 configurations (kCfg of csrc/capi.hip): 9 generic tiles, the halo kernel's 4, the ping-pong kernel's 5
+# (BM, BN) of ffn_igemm's bf16 configurations (kCfg of csrc/capi_igemm.hip): 9 generic tiles, the halo kernel's 4, the ping-pong kernel's 5
 _IGEMM_CFG_TILES = [(64, 64), (128, 64), (128, 128), (128, 128), (256, 128), (256, 256), (128, 320), (128, 160), (192, 320),
                     (128, 320), (256, 128), (256, 256), (128, 128), (256, 320), (256, 256), (192, 320), (192, 256), (256, 128)]
 
