@@ -3,15 +3,17 @@
     python evaluation/metrics/main.py --path <generated_results.json> [--task 100111111] [--level 0..3] [--no_rotate] [--3d]
            [--use_relative_path --base_dir <GeoBenchMeta>] [--fid_path <real images>] [--gen_img_key gen_img_path]
            [--clip_weights <file>] [--dino_weights <file>] [--dinov2_weights <file>] [--model <SD folder | synthetic:sd21-base>] [--precision f32|x3]
-           [--hps_weights <file> --hps_tokenizer <folder>] [--md_visible_only] [--md_keypoints default|sift]
+           [--hps_weights <file> --hps_tokenizer <folder>] [--irs_weights <file> --irs_tokenizer <folder>] [--md_visible_only] [--md_keypoints default|sift]
 
 --task is nine digits (1 = compute): FID, IRS, HPS, BGC, SUBC, WRAP_E, MD, FID_DINO, FID_KD.  The reference downloads its extractors (clip.load, torch.hub); there
 is no download here, the weights are local files: --clip_weights (CLIP ViT-B/32: a transformers CLIPVisionModelWithProjection state dict or the OpenAI
 checkpoint's visual.* names), --dino_weights (dino_vitb16), --dinov2_weights (dinov2_vitb14), each a .safetensors file or a torch.save'd state dict;
 --model is the Stable-Diffusion checkpoint whose features Mean Distance matches; --hps_weights is `HPS_v2.1_compressed.pt` (its state_dict in open_clip's layout,
-or transformers' CLIPModel layout) and --hps_tokenizer a folder with CLIP's vocab.json and merges.txt (HPS: OpenCLIP ViT-H/14, freefine_amd/hps.py).  FID
-(Inception-v3 needs torchvision) and IRS (ImageReward and BLIP) need packages that are not installed, so there is nothing to pin an implementation to: they are
-reported as `not built`, and the other metrics still run.  A metric whose weights were not given is reported as such, likewise.  --precision is the arithmetic of the networks: f32 (default: exact-fp32 MFMA) or x3 (split-bf16: hi + lo bf16 operand pairs, fp32
+or transformers' CLIPModel layout) and --hps_tokenizer a folder with CLIP's vocab.json and merges.txt (HPS: OpenCLIP ViT-H/14, freefine_amd/hps.py);
+--irs_weights is `ImageReward.pt` (its state_dict: blip.visual_encoder.*, blip.text_encoder.*, mlp.layers.*) and --irs_tokenizer a folder with
+bert-base-uncased's vocab.txt (IRS: BLIP ViT-L/16 and BLIP's cross-attending BERT, freefine_amd/irs.py, pinned to transformers' BlipVisionModel / BlipTextModel;
+parity with the published checkpoint is unmeasured).  FID (Inception-v3 needs torchvision) needs a package that is not installed, so there is nothing to pin an
+implementation to: it is reported as `not built`, and the other metrics still run.  A metric whose weights were not given is reported as such, likewise.  --precision is the arithmetic of the networks: f32 (default: exact-fp32 MFMA) or x3 (split-bf16: hi + lo bf16 operand pairs, fp32
 accumulation; the ViT towers, HPS's two among them, are built with x3=True and the MD pipeline with from_pretrained(..., x3=True)).
 For an edit that is neither a translation, a 2-D rotation nor a uniform scale, MD reads the case's correspondence map: <tree>/correspondence/<da>/<ins>/<edit>.npy
 beside the folder of generated images (the 3d_rgb variant of evaluation/FreeFine/freefine_batch_infer_2d.py writes it with --save-correspondence).
@@ -29,7 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 NAMES = ("FID", "IRS", "HPS", "BGC", "SUBC", "WRAP_E", "MD", "FID_DINO", "FID_KD")
 NOT_BUILT = {"FID": "not built (Inception-v3: torchvision is not installed, nothing to pin it to)",
-             "IRS": "not built (ImageReward and BLIP are not installed, nothing to pin it to)"}
+             "IRS": "not built into this run (--irs_weights / --irs_tokenizer missing)"}      # IRS is built: run() answers it before this table is read
 LEVEL_WORDS = {1: ("lightly", "slightly", "gently", "mildly"), 2: ("moderately", "markedly", "appreciably"), 3: ("heavily", "intensely", "significantly", "strongly")}
 PATH_KEYS = ("ori_img_path", "coarse_input_path", "ori_mask_path", "tgt_mask_path")
 
@@ -95,6 +97,8 @@ def build_parser():
     ap.add_argument("--model", default=None, help="Stable-Diffusion folder or synthetic:<name> (MD)")
     ap.add_argument("--hps_weights", default=None, help="HPS_v2.1_compressed.pt: OpenCLIP ViT-H/14 weights, open_clip or transformers layout (HPS)")
     ap.add_argument("--hps_tokenizer", default=None, help="folder with CLIP's vocab.json and merges.txt (HPS)")
+    ap.add_argument("--irs_weights", default=None, help="ImageReward.pt: BLIP ViT-L/16, BLIP's BERT and the reward head (IRS)")
+    ap.add_argument("--irs_tokenizer", default=None, help="folder with bert-base-uncased's vocab.txt (IRS)")
     ap.add_argument("--precision", default="f32", choices=("f32", "x3"), help="arithmetic of the networks: f32 = exact fp32, x3 = split-bf16")
     ap.add_argument("--md_visible_only", action="store_true", help="MD: drop keypoints hidden in the coarse 3-D edit (needs correspondence_visible images; "
                                                                    "not the reference's metric)")
@@ -104,6 +108,7 @@ def build_parser():
     ap.add_argument("--clip_config", default="vitb32", help=argparse.SUPPRESS)        # "tiny": the test sizes
     ap.add_argument("--dino_config", default="vitb16", help=argparse.SUPPRESS)
     ap.add_argument("--hps_config", default="vith14", choices=("vith14", "tiny"), help=argparse.SUPPRESS)      # with "tiny", --hps_tokenizer bytes: text.ByteTokenizer
+    ap.add_argument("--irs_config", default="med", choices=("med", "tiny"), help=argparse.SUPPRESS)            # with "tiny", --irs_tokenizer bytes: text.ByteTokenizer
     return ap
 
 
@@ -126,6 +131,13 @@ def main(argv=None):
     def run(name):
         import torch
         from freefine_amd import metrics as FM
+        if name == "IRS":
+            if not args.irs_weights or not args.irs_tokenizer:
+                return NOT_BUILT["IRS"]
+            from freefine_amd import irs
+            vcfg, tcfg = ("tiny16", "tiny") if args.irs_config == "tiny" else ("vitl16", "med")
+            model = irs.HipImageReward.from_state(load_state(args.irs_weights), irs.load_tokenizer(args.irs_tokenizer), vcfg, tcfg, dtype=torch.float32, x3=x3)
+            return FM.calculate_irs(data, label, model)
         if name in NOT_BUILT:
             return NOT_BUILT[name]
         if name == "HPS":

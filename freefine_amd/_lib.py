@@ -19,6 +19,7 @@ IMGPREP_MAX_SIDE = 4096      # FFN_IMGPREP_MAX_SIDE
 IMGPREP_MAX_TAPS = 2 * 3 * IMGPREP_MAX_SIDE + 1      # FFN_IMGPREP_MAX_TAPS
 BOX_NMS_MAX = 16384          # FFN_BOX_NMS_MAX
 KEEP_NONE, KEEP_SUM_LT128, KEEP_GT128 = 0, 1, 2
+CHAIN_MAXL, CHAIN_MAXW = 8, 1024      # FFN_CHAIN_MAXL, FFN_CHAIN_MAXW
 
 
 class IgemmDesc(C.Structure):
@@ -159,6 +160,8 @@ SYMBOLS = {
     "ffn_splat_composite": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _i, _i, _vp]),
     "ffn_mesh_cover": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "ffn_embed_tokens": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _l, _i, _i, _i]),
+    "ffn_embed_tokens_ln": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _f]),
+    "ffn_affine_chain": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_int), _i, _f, _f]),
     "ffn_dift_match": (_i, [_vp, C.POINTER(DiftDesc)]),
     "ffn_dift_workspace_bytes": (_l, [_i, _i, _i, _i]),
     "ffn_sift_base": (_i, [_vp, _vp, _vp, _i, _i, _i]),

@@ -217,9 +217,6 @@ class HipCLIPVision:
         """images uint8 [B, H, W, 3] of ONE size (numpy or torch, host or device); keep = None or (rule, m1, m2) as in ops.resize_pil_u8 (uint8 [B, H, W], host or
         device) -> fp32 [B, projection_dim]: CLIP's transform (clip/clip.py _transform: Resize(n, BICUBIC), CenterCrop(n), ToTensor, Normalize) and the tower"""
         cfg = self.config
-        img, keep = encoder.u8_batch(images, keep, self.device)
-        size = cfg.image_size
-        oh, ow = ops.torchvision_resize_size(img.shape[1], img.shape[2], size)
-        small = ops.resize_pil_u8(img, oh, ow, "bicubic", crop=ops.center_crop_window(oh, ow, size), keep=keep)
+        small = encoder.clip_crop_u8(images, keep, cfg.image_size, self.device)
         a = encoder.patch_rows_u8(small, self._lut, cfg.patch_size, self.kpe, self.dtype, self.x3)
-        return self._tower(a, img.shape[0])
+        return self._tower(a, small.shape[0])

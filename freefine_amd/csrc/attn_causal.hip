@@ -1,7 +1,8 @@
 // The text tower's unit of libfreefine_hip.so: the kernels only the CLIP text tower needs (attention_causal.h: attn_causal_kernel in its three
 // arithmetic modes, embed_tokens_kernel), and the two small kernels behind the CLIP towers' projections (pool_layernorm_kernel, cosine_rows_kernel).
 // Default code generation.  It exports the entries of its own kernels (ffn_embed_tokens, ffn_pool_layernorm, ffn_cosine_rows); attn_causal_kernel is
-// planned and launched by ffn_attn (capi_attn.hip), which reaches it through fcausal_kernel (attn_units.h).
+// planned and launched by ffn_attn (capi_attn.hip), which reaches it through fcausal_kernel (attn_units.h).  The two small kernels of the ImageReward score's
+// BERT live here too, beside the lookup and the row norm they build on (ffn_embed_tokens_ln, ffn_affine_chain).
 #include <limits.h>
 
 #include "capi_common.h"
@@ -115,4 +116,117 @@ extern "C" int ffn_cosine_rows(void* stream, const float* a, const float* b, flo
     REQUIRE(b_rows == 1 || b_rows == B, "cosine_rows: b has %d rows (1 or B=%d)", b_rows, B);
     LAUNCH(cosine_rows_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a, b, out, B, P, b_rows);
     return check_launch("cosine_rows");
+}
+
+// ---- ffn_embed_tokens_ln: y[m] = LayerNorm(table[ids[m]] + pos[m % S]) -- BERT's embedding (BLIP's text encoder), whose LayerNorm sits behind the lookup.
+// One wave per row, four rows per workgroup.  A lane forms the fp32 sums of its own 16-byte chunks (lane, lane + 64, ...: layernorm_row's chunks) exactly as
+// embed_tokens_kernel does and parks them in its wave's LDS row; layernorm_row then reads that row, so every lane reads back only what it wrote itself (no
+// barrier) and the fp32 result has the bits of ffn_layernorm(ffn_embed_tokens(..., FFN_F32)).
+template <typename T, int MAXCH>
+__global__ __launch_bounds__(256) void embed_tokens_ln_kernel(const int* __restrict__ ids, const float* __restrict__ table, const float* __restrict__ pos,
+                                                              T* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta, int M, int S,
+                                                              int C, int V, float eps) {
+    __shared__ __attribute__((aligned(16))) float rowbuf[4][MAXCH * 64 * 4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = blockIdx.x * 4 + wave;
+    if (m >= M) return;
+    const int id = ids[m], cch = C / 4;
+    const float* prow = pos + (long)(m % S) * C;
+#pragma unroll
+    for (int i = 0; i < MAXCH; ++i) {
+        const int cc = lane + 64 * i;
+        if (cc < cch) {
+            float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4];
+            if ((unsigned)id < (unsigned)V) load4(table + (long)id * C + cc * 4, a);      // (the host refuses ids outside the table before upload)
+            load4(prow + cc * 4, b);
+            const float v[4] = {a[0] + b[0], a[1] + b[1], a[2] + b[2], a[3] + b[3]};
+            store4(&rowbuf[wave][cc * 4], v);
+        }
+    }
+    layernorm_row<float, MAXCH, false, T>(rowbuf[wave], 0l, y, (long)m, gamma, beta, C, eps, lane);
+}
+
+extern "C" int ffn_embed_tokens_ln(void* stream, int dtype, const int* ids, const float* table, const float* pos, void* out, const float* gamma, const float* beta,
+                                   long M, int S, int C, int V, float eps) {
+    REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16, "embed_tokens_ln: bad dtype %d", dtype);
+    REQUIRE(ids && table && pos && out && gamma && beta && aligned16(table) && aligned16(pos) && aligned16(out) && (reinterpret_cast<uintptr_t>(ids) & 3) == 0,
+            "embed_tokens_ln: null / unaligned pointer");
+    const int epc = dtype == FFN_F32 ? 4 : 8;
+    REQUIRE(M > 0 && S > 0 && V > 0 && C > 0 && C % epc == 0 && C / 4 <= 64 * 6 && M < (1l << 31) - 4,
+            "embed_tokens_ln: bad shape M=%ld S=%d C=%d V=%d (C %% %d == 0, C <= %d)", M, S, C, V, epc, 64 * 6 * 4);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((M + 3) / 4));
+#define EMBED_LN(T, MAXCH) LAUNCH((embed_tokens_ln_kernel<T, MAXCH>), grid, dim3(256), 0, s, ids, table, pos, (T*)out, gamma, beta, (int)M, S, C, V, eps)
+    if (dtype == FFN_BF16) {
+        if (C / 4 <= 128) EMBED_LN(bf16, 2);
+        else EMBED_LN(bf16, 6);
+    } else {
+        if (C / 4 <= 128) EMBED_LN(float, 2);
+        else EMBED_LN(float, 6);
+    }
+#undef EMBED_LN
+    return check_launch("embed_tokens_ln");
+}
+
+// ---- ffn_affine_chain: out[b] = ((W_L ( ... (W_1 x_b + b_1) ... ) + b_L) - shift) / scale, layer after layer (ImageReward's reward head: five Linears with
+// nothing but dropout between them).  One workgroup of sixteen waves per row; the activations ping-pong between two LDS rows.  A wave takes four neighbouring
+// outputs at a time (four independent sums over one read of the activations: the loads of a step do not wait for each other).  For EVERY output, lane j sums
+// the products k = j, j + 64, ... in ascending order, the 64 partial sums go through a fixed xor tree, the bias is added last.  That order depends on neither
+// B nor the row nor which wave owns the output: deterministic, and equal rows give equal bits.  Scalar loads and stores: widths and offsets need no alignment.
+struct AffineChain {
+    int L, dims[FFN_CHAIN_MAXL + 1];
+};
+constexpr int CHAIN_WAVES = 16, CHAIN_OUTS = 4;
+__global__ __launch_bounds__(64 * CHAIN_WAVES) void affine_chain_kernel(const float* __restrict__ x, const float* __restrict__ params, float* __restrict__ out,
+                                                                        AffineChain c, int ldx, float shift, float scale) {
+    __shared__ float act[2][FFN_CHAIN_MAXW];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k = threadIdx.x; k < c.dims[0]; k += 64 * CHAIN_WAVES) act[0][k] = x[(long)b * ldx + k];
+    __syncthreads();
+    const float* w = params;
+    int cur = 0;
+    for (int l = 0; l < c.L; ++l) {
+        const int K = c.dims[l], N = c.dims[l + 1];
+        const float* bias = w + (long)N * K;
+        const bool last = l == c.L - 1;
+        for (int n0 = wave * CHAIN_OUTS; n0 < N; n0 += CHAIN_WAVES * CHAIN_OUTS) {      // (uniform per wave: every lane reaches the shuffles)
+            const float* wr[CHAIN_OUTS];
+#pragma unroll
+            for (int j = 0; j < CHAIN_OUTS; ++j) wr[j] = w + (long)(n0 + j < N ? n0 + j : N - 1) * K;      // past the last output: its row again, never stored
+            float s[CHAIN_OUTS] = {0.f, 0.f, 0.f, 0.f};
+            for (int k = lane; k < K; k += 64) {
+                const float a = act[cur][k];
+#pragma unroll
+                for (int j = 0; j < CHAIN_OUTS; ++j) s[j] += wr[j][k] * a;
+            }
+#pragma unroll
+            for (int j = 0; j < CHAIN_OUTS; ++j)
+                for (int off = 32; off > 0; off >>= 1) s[j] += __shfl_xor(s[j], off);
+            if (lane < CHAIN_OUTS && n0 + lane < N) {
+                const int n = n0 + lane;
+                float v = s[0];
+#pragma unroll
+                for (int j = 1; j < CHAIN_OUTS; ++j) v = lane == j ? s[j] : v;
+                v += bias[n];
+                if (last) out[(long)b * N + n] = (v - shift) / scale;
+                else act[cur ^ 1][n] = v;
+            }
+        }
+        __syncthreads();
+        w = bias + N;
+        cur ^= 1;
+    }
+}
+
+extern "C" int ffn_affine_chain(void* stream, const float* x, const float* params, float* out, int B, int ldx, const int* dims, int L, float shift, float scale) {
+    REQUIRE(x && params && out && dims, "affine_chain: null pointer");
+    REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(out)) & 3) == 0, "affine_chain: x, params, out must be 4-byte aligned");
+    REQUIRE(L >= 1 && L <= FFN_CHAIN_MAXL, "affine_chain: L=%d layers (1 .. %d)", L, FFN_CHAIN_MAXL);
+    AffineChain c;
+    c.L = L;
+    for (int l = 0; l <= FFN_CHAIN_MAXL; ++l) c.dims[l] = l <= L ? dims[l] : 0;
+    for (int l = 0; l <= L; ++l) REQUIRE(c.dims[l] >= 1 && c.dims[l] <= FFN_CHAIN_MAXW, "affine_chain: width %d of layer boundary %d (1 .. %d)", c.dims[l], l, FFN_CHAIN_MAXW);
+    REQUIRE(B > 0 && ldx >= c.dims[0], "affine_chain: bad shape B=%d ldx=%d (ldx >= %d)", B, ldx, c.dims[0]);
+    REQUIRE(scale != 0.f && scale == scale && shift == shift, "affine_chain: shift / scale must be numbers, scale non-zero");
+    LAUNCH(affine_chain_kernel, dim3((unsigned)B), dim3(64 * CHAIN_WAVES), 0, reinterpret_cast<hipStream_t>(stream), x, params, out, c, ldx, shift, scale);
+    return check_launch("affine_chain");
 }

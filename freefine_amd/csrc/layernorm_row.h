@@ -19,8 +19,9 @@ __device__ __forceinline__ void store_pair4(bf16* yp, long row, int C, int c, co
 
 // layernorm_row: one wave normalises row `row` of x [.][C] and writes it as row `orow` of y.  The routine of every LayerNorm entry (ffn_layernorm,
 // ffn_layernorm_pair, and ffn_pool_layernorm in attn_causal.hip, whose row is gathered): the same loads, sums and affine step, so the same bits.
-template <typename T, int MAXCH, bool PAIR = false>  // MAXCH = max 16-byte chunks per lane
-__device__ __forceinline__ void layernorm_row(const T* x, long row, T* y, long orow, const float* gamma, const float* beta, int C, float eps, int lane) {
+// TO (ffn_embed_tokens_ln: T = float, TO = bf16): the output's element type where it differs from the input's; the four values of a chunk go out as one 8-byte store.
+template <typename T, int MAXCH, bool PAIR = false, typename TO = T>  // MAXCH = max 16-byte chunks per lane
+__device__ __forceinline__ void layernorm_row(const T* x, long row, TO* y, long orow, const float* gamma, const float* beta, int C, float eps, int lane) {
     constexpr int EPC = DT<T>::EPC;
     const int cch = C / EPC;
     float f[MAXCH][EPC];
@@ -63,7 +64,8 @@ __device__ __forceinline__ void layernorm_row(const T* x, long row, T* y, long o
                 o[e] = (f[i][e] - mean) * rstd * gamma[c] + beta[c];
             }
             if constexpr (PAIR) store_pair4(reinterpret_cast<bf16*>(y), orow, C, cc * EPC, o);
-            else *reinterpret_cast<u32x4*>(y + orow * C + cc * EPC) = DT<T>::pack(o);
+            else if constexpr (sizeof(TO) == sizeof(T)) *reinterpret_cast<u32x4*>(y + orow * C + cc * EPC) = DT<T>::pack(o);
+            else store4(y + orow * C + cc * EPC, o);
         }
     }
 }

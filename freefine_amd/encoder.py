@@ -11,7 +11,9 @@ fp32 accumulation), bfloat16 = fast mode.  Split-bf16: weights are packed with o
 
 V^T: ONE buffer per forward (`vt_buffer`), [B, C, ceil8(S)] in the activation type, zero-filled once and handed as `out=` to every layer's V^T GEMM.  The
 padding columns (S not a multiple of 8) are multiplied by P = 0 in the attention kernels and must be finite; no GEMM writes them, so zeroing them once holds
-for all layers.  The stream orders a layer's attention before the next layer's V^T GEMM, and no tower keeps a V^T."""
+for all layers.  The stream orders a layer's attention before the next layer's V^T GEMM, and no tower keeps a V^T.
+
+The post-LayerNorm block with cross-attention to a second sequence (BERT as BLIP runs it: irs.py) is CrossBlock / run_cross_block further down."""
 import math
 from collections import namedtuple
 
@@ -60,6 +62,63 @@ def run_block(b, x, vt, *, heads, eps, act, hidden, x3=False, causal=False, spli
     return ops.linear(h, *b.fc2, K=hidden, residual=x, splitk=splitk)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the post-LayerNorm block that also attends to a second sequence (BERT with cross-attention: BLIP's text encoder, irs.py)
+# ---------------------------------------------------------------------------------------------------------------------
+# lns / lnc / lnm: the LayerNorms behind self-attention, cross-attention and the MLP; cq / co: the cross-attention's query and output projections.  The
+# cross-attention's K and V projections read the second sequence only, so they are no part of the block: the tower projects them for all its layers before
+# the first block runs (cross_kv).
+CrossBlock = namedtuple("CrossBlock", "qk v o lns cq co lnc fc1 fc2 lnm")
+
+
+def pack_cross_block(qk, v, o, lns, cq, co, lnc, fc1, fc2, lnm, dtype, x3=False):
+    """fp32 (weight, bias) pairs on the tower's device -> CrossBlock"""
+    norm = lambda p: (p[0].contiguous(), p[1].contiguous())
+    lin = lambda p: (ops.pack_linear(p[0].contiguous(), dtype, x3=x3), p[1].contiguous())
+    return CrossBlock(lin(qk), lin(v), lin(o), norm(lns), lin(cq), lin(co), norm(lnc), lin(fc1), lin(fc2), norm(lnm))
+
+
+def cross_kv(e, wk, wv, layers, C):
+    """The cross-attention operands of all `layers` blocks from the second sequence e [B, Sk, Ce] (activation type; split-bf16: fp32, or pair rows, which are
+    split once here): wk = (the layers' K weights stacked into one packed [layers * C, Ce] weight, the stacked bias), wv = per layer (packed weight, bias) ->
+    (ck: per layer a [B, Sk, C] column view of ONE [B, Sk, layers * C] GEMM result, cvt: per layer V^T [B, C, ceil8(Sk)] of one zero-filled buffer -- the padding
+    columns are written by no GEMM and stay zero, as in vt_buffer)."""
+    B, Sk = e.shape[0], e.shape[1]
+    x3 = ops.is_x3(wk[0])
+    if x3 and ops.pair_width(e) is None:
+        e = ops.split_pair(e)
+    Ce = ops.pair_width(e) or e.shape[-1]
+    k = ops.linear(e, *wk, K=Ce)
+    cvt = torch.zeros(layers, B, C, ceil8(Sk), dtype=k.dtype, device=k.device)
+    for i in range(layers):
+        ops.linear(e, *wv[i], K=Ce, rows_per_batch=Sk, transposed_ld=cvt.shape[-1], out=cvt[i])
+    return [k[..., i * C:(i + 1) * C] for i in range(layers)], [cvt[i] for i in range(layers)]
+
+
+def run_cross_block(b, x, vt, ck, cvt, *, heads, eps, hidden, kmask=None, x3=False, splitk=0):
+    """x [B, S, C] -> the block's output, the same shape:
+
+        x = LN(x + o(attn(q = k = v = x, key mask)));  x = LN(x + co(attn(q = cq(x), k = ck, v = cvt)));  x = LN(x + fc2(gelu(fc1(x))))
+
+    vt: vt_buffer(x); ck [B, Sk, C] (may be a column view) and cvt [B, C, ceil8(Sk)]: cross_kv's; kmask: None, or per row of x one uint8 [>= S] device tensor
+    (4-byte aligned; non-zero = the key is attended to), a list of B or of one shared by all rows.  Every residual is its GEMM's epilogue and every LayerNorm
+    normalises that sum.  Post-LN: the residual stream IS the next GEMM's operand, so in split-bf16 mode it stays fp32 and ops.linear splits it; attention and
+    fc1 still hand pair rows to the GEMM behind them."""
+    B, S, C = x.shape
+    scale = (C // heads) ** -0.5
+    xa = ops.split_pair(x) if x3 else x                                                                # split once for the two GEMMs that read it
+    qk = ops.linear(xa, *b.qk, K=C, splitk=splitk)                                                     # [B, S, 2C]: q | k
+    ops.linear(xa, *b.v, K=C, rows_per_batch=S, transposed_ld=vt.shape[-1], splitk=splitk, out=vt)     # V^T [B, C, S']
+    passes = None if kmask is None else [[ops.AttnEntrySpec(i, i, kmask=kmask[i % len(kmask)]) for i in range(B)]]
+    a = ops.attention(qk, qk[..., C:], vt, heads, scale, passes, Sk=S, C=C, x3=x3, out_pair=x3)
+    x = ops.layernorm(ops.linear(a, *b.o, K=C, residual=x, splitk=splitk), *b.lns, eps=eps)
+    q = ops.linear(x, *b.cq, K=C, splitk=splitk)
+    a = ops.attention(q, ck, cvt, heads, scale, None, Sk=ck.shape[1], C=C, x3=x3, out_pair=x3)
+    x = ops.layernorm(ops.linear(a, *b.co, K=C, residual=x, splitk=splitk), *b.lnc, eps=eps)
+    h = ops.linear(x, *b.fc1, K=C, out_pair=x3, splitk=splitk, gelu=True)
+    return ops.layernorm(ops.linear(h, *b.fc2, K=hidden, residual=x, splitk=splitk), *b.lnm, eps=eps)
+
+
 def im2col(x, ps):
     """[B, 3, H, W] -> [B (H/ps)(W/ps), 3 ps ps]: one row per patch (row-major over the patch grid), columns ordered (channel, ky, kx) like the patch
     embedding's Conv2d(kernel = stride = patch) weight .reshape(C, -1)"""
@@ -77,6 +136,15 @@ def u8_batch(images, keep, device):
     if keep is not None:
         keep = (keep[0],) + tuple(None if m is None else torch.as_tensor(m).to(device).contiguous() for m in keep[1:])
     return img, keep
+
+
+def clip_crop_u8(images, keep, size, device):
+    """CLIP's geometric transform on the device (clip/clip.py _transform: Resize(size, BICUBIC) of the short side, CenterCrop(size)), after image * keep mask: one
+    ffn_resize_pil_u8 with a crop window.  images / keep as u8_batch takes them -> uint8 [B, size, size, 3].  The CLIP image towers and the ImageReward
+    score's BLIP tower (irs.py) share it."""
+    img, keep = u8_batch(images, keep, device)
+    oh, ow = ops.torchvision_resize_size(img.shape[1], img.shape[2], size)
+    return ops.resize_pil_u8(img, oh, ow, "bicubic", crop=ops.center_crop_window(oh, ow, size), keep=keep)
 
 
 def patch_rows_u8(small, lut, patch, K, dtype, x3):

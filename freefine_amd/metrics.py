@@ -294,6 +294,18 @@ def calculate_hps(data, image_label, model, reader=None, batch_size=32):
     score_u8(uint8 [B, H, W, 3], prompt) -> [B]).  The files of one entry are grouped by size so that one launch sees one size, batched by `batch_size`
     within a group.  `reader` maps a path to a uint8 HWC array (default: PIL, as decoded); RGB only -- open_clip's transform converts other modes, this
     driver refuses them.  No samples: ValueError (the reference divides by zero)."""
+    return _mean_caption_score(data, image_label, model, reader, batch_size, "calculate_hps")
+
+
+def calculate_irs(data, image_label, model, reader=None, batch_size=32):
+    """image_reward.py:calculate_irs: the ImageReward score of every sample's data[...][image_label] file given its image entry's image["4v_caption"], summed and
+    divided by the number of samples.  model: a freefine_amd.irs.HipImageReward (anything with score_u8(uint8 [B, H, W, 3], prompt) -> [B]).  Grouping by size,
+    batching, `reader`, RGB only and the ValueError on no samples are calculate_hps's: one loop serves both."""
+    return _mean_caption_score(data, image_label, model, reader, batch_size, "calculate_irs")
+
+
+def _mean_caption_score(data, image_label, model, reader, batch_size, what):
+    """the loop of calculate_hps and calculate_irs (their docstrings)"""
     if reader is None:
         from PIL import Image
         reader = lambda p: np.array(Image.open(p))
@@ -316,7 +328,7 @@ def calculate_hps(data, image_label, model, reader=None, batch_size=32):
                 total += float(sc.astype(np.float64).sum())
         number += len(files)
     if number == 0:
-        raise ValueError(f"calculate_hps: no samples with {image_label!r} in the data")
+        raise ValueError(f"{what}: no samples with {image_label!r} in the data")
     return total / number
 
 

@@ -1017,6 +1017,59 @@ def embed_tokens(ids, table, pos, dtype, out=None):
     return out
 
 
+def embed_tokens_ln(ids, table, pos, gamma, beta, dtype, eps=1e-12, out=None):
+    """ids int32 [N, S] (device), table fp32 [V, C], pos fp32 [>= S, C], gamma / beta fp32 [C] -> [N, S, C] of `dtype`: LayerNorm(table[ids] + pos), the sum and
+    the norm in fp32 (ffn_embed_tokens_ln: BERT's embedding; the fp32 result has the bits of layernorm(embed_tokens(..., float32))).  The caller has checked
+    0 <= id < V on the host."""
+    lib = L.load()
+    assert ids.dtype == torch.int32 and ids.is_contiguous() and table.dtype == pos.dtype == torch.float32 and table.is_contiguous() and pos.is_contiguous()
+    N, S = ids.shape
+    V, C = table.shape
+    assert pos.shape[0] >= S and pos.shape[1] == C
+    assert gamma.dtype == beta.dtype == torch.float32 and tuple(gamma.shape) == tuple(beta.shape) == (C,) and gamma.is_contiguous() and beta.is_contiguous()
+    if out is None:
+        out = torch.empty(N, S, C, dtype=dtype, device=ids.device)
+    else:
+        assert out.dtype == dtype and tuple(out.shape) == (N, S, C) and out.is_contiguous()
+    L.check(_timed(f"embed_tokens_ln_kernel<{_tname(out)}>", 0.0, (8.0 + out.element_size()) * out.numel(),
+                   lambda: lib.ffn_embed_tokens_ln(_stream(), _dt(out), ids.data_ptr(), table.data_ptr(), pos.data_ptr(), out.data_ptr(), gamma.data_ptr(),
+                                                   beta.data_ptr(), N * S, S, C, V, eps)), "ffn_embed_tokens_ln")
+    return out
+
+
+def affine_chain_params(layers):
+    """[(W [n, k], b [n]), ...] fp32 -> (the packed parameter buffer of ffn_affine_chain: W_1, b_1, W_2, b_2 ... back to back, the widths [k_1, n_1, n_2 ...])"""
+    dims = [layers[0][0].shape[1]]
+    for w, b in layers:
+        assert w.ndim == 2 and w.shape[1] == dims[-1] and tuple(b.shape) == (w.shape[0],), "affine_chain: layer widths do not chain"
+        dims.append(w.shape[0])
+    return torch.cat([t.detach().float().reshape(-1) for w, b in layers for t in (w, b)]).contiguous(), dims
+
+
+def affine_chain(x, params, dims, shift=0.0, scale=1.0, ldx=None, B=None, out=None):
+    """x fp32: B rows of dims[0] values, row b at x.data_ptr() + 4 b ldx (default: the rows of a contiguous [B, dims[0]] tensor; ldx = S * C with x [B, S, C] reads
+    row 0 of every sequence); params: affine_chain_params' buffer on x's device -> fp32 [B, dims[-1]]: the layers one after the other, then (y - shift) / scale
+    (ffn_affine_chain; deterministic)."""
+    lib = L.load()
+    dims = [int(d) for d in dims]
+    nl = len(dims) - 1
+    assert x.dtype == params.dtype == torch.float32 and x.is_contiguous() and params.is_contiguous() and x.device == params.device
+    if ldx is None:
+        assert x.ndim == 2 and x.shape[1] == dims[0]
+        ldx, B = dims[0], x.shape[0]
+    assert B is not None and B > 0 and (B - 1) * ldx + dims[0] <= x.numel(), "affine_chain: rows reach outside x"
+    assert params.numel() == sum(dims[i + 1] * (dims[i] + 1) for i in range(nl)), "affine_chain: params do not hold the layers of dims"
+    if out is None:
+        out = torch.empty(B, dims[-1], dtype=torch.float32, device=x.device)
+    else:
+        assert out.dtype == torch.float32 and tuple(out.shape) == (B, dims[-1]) and out.is_contiguous()
+    cd = (CT.c_int * len(dims))(*dims)
+    macs = sum(dims[i + 1] * dims[i] for i in range(nl))
+    L.check(_timed("affine_chain_kernel", 2.0 * B * macs, 4.0 * (B * (dims[0] + dims[-1]) + params.numel()),
+                   lambda: lib.ffn_affine_chain(_stream(), x.data_ptr(), params.data_ptr(), out.data_ptr(), B, ldx, cd, nl, shift, scale)), "ffn_affine_chain")
+    return out
+
+
 _DIFT_WS = {}
 
 

@@ -398,6 +398,23 @@ int ffn_cast(void* stream, int src_dtype, int dst_dtype, const void* src, void* 
  * FFN_BF16X3: fp32 rows -- a LayerNorm follows, no pair rows; FFN_BF16: bf16 rows).  ids int32 [M] in device memory, 0 <= id < V (the CALLER checks that on
  * the host before upload; the kernel reads no table row outside [0, V)); table fp32 [V][C], pos fp32 [S][C], C % 4 == 0. */
 int ffn_embed_tokens(void* stream, int dtype, const int* ids, const float* table, const float* pos, void* out, long M, int S, int C, int V);
+/* ABI version 15.  BERT's embedding (transformers BlipTextEmbeddings, the text encoder of the ImageReward score): out[m][:] = LayerNorm(table[ids[m]][:] +
+ * pos[m % S][:]; gamma, beta, eps).  Arguments and checks as ffn_embed_tokens.  The sum is taken in fp32 and normalised by the routine of ffn_layernorm
+ * (csrc/layernorm_row.h); out is fp32 (FFN_F32: bit-identical to ffn_layernorm(ffn_embed_tokens(..., FFN_F32))) or bf16 (FFN_BF16: the same fp32 values rounded
+ * once).  C as ffn_layernorm: a multiple of 4 (fp32) / 8 (bf16), at most 1536.  A row whose sum is constant has variance 0 and gives beta, finite at any
+ * eps > 0.  Anything else: FFN_EINVAL before any launch. */
+int ffn_embed_tokens_ln(void* stream, int dtype, const int* ids, const float* table, const float* pos, void* out, const float* gamma, const float* beta, long M,
+                        int S, int C, int V, float eps);
+/* ABI version 15.  A chain of L affine layers with nothing between them, then a shift and a scale (ImageReward's reward head):
+ *   a_0 = x[b][0 : dims[0]] (row b starts at x + b * ldx: ldx = S * C reads row 0 of every [S][C] sequence without a gather);  a_l = W_l a_{l-1} + b_l;
+ *   out[b][0 : dims[L]] = (a_L - shift) / scale.
+ * x, out and params fp32; params holds W_1 [dims[1]][dims[0]], b_1 [dims[1]], W_2 [dims[2]][dims[1]], b_2 ... back to back; dims: HOST int32 [L + 1], read
+ * before the call returns.  1 <= L <= FFN_CHAIN_MAXL, 1 <= dims[l] <= FFN_CHAIN_MAXW, no width needs to be a multiple of anything; ldx >= dims[0]; scale != 0.
+ * One workgroup per row; every output value is one sum over k in an order that depends on neither B nor the row: deterministic, equal rows give equal bits.
+ * Anything else: FFN_EINVAL before any launch. */
+#define FFN_CHAIN_MAXL 8
+#define FFN_CHAIN_MAXW 1024
+int ffn_affine_chain(void* stream, const float* x, const float* params, float* out, int B, int ldx, const int* dims, int L, float shift, float scale);
 int ffn_image_to_nhwc(void* stream, int dtype, const uint8_t* img, void* dst, long npix, int CP);
 int ffn_nhwc_to_image(void* stream, int dtype, const void* src, float* dst, int B, int HW, int ld);
 
