@@ -4,6 +4,7 @@
            [--use_relative_path --base_dir <GeoBenchMeta>] [--fid_path <real images>] [--gen_img_key gen_img_path]
            [--clip_weights <file>] [--dino_weights <file>] [--dinov2_weights <file>] [--model <SD folder | synthetic:sd21-base>] [--precision f32|x3]
            [--hps_weights <file> --hps_tokenizer <folder>] [--irs_weights <file> --irs_tokenizer <folder>] [--md_visible_only] [--md_keypoints default|sift]
+           [--fid_weights <file>]
 
 --task is nine digits (1 = compute): FID, IRS, HPS, BGC, SUBC, WRAP_E, MD, FID_DINO, FID_KD.  The reference downloads its extractors (clip.load, torch.hub); there
 is no download here, the weights are local files: --clip_weights (CLIP ViT-B/32: a transformers CLIPVisionModelWithProjection state dict or the OpenAI
@@ -12,8 +13,11 @@ checkpoint's visual.* names), --dino_weights (dino_vitb16), --dinov2_weights (di
 or transformers' CLIPModel layout) and --hps_tokenizer a folder with CLIP's vocab.json and merges.txt (HPS: OpenCLIP ViT-H/14, freefine_amd/hps.py);
 --irs_weights is `ImageReward.pt` (its state_dict: blip.visual_encoder.*, blip.text_encoder.*, mlp.layers.*) and --irs_tokenizer a folder with
 bert-base-uncased's vocab.txt (IRS: BLIP ViT-L/16 and BLIP's cross-attending BERT, freefine_amd/irs.py, pinned to transformers' BlipVisionModel / BlipTextModel;
-parity with the published checkpoint is unmeasured).  FID (Inception-v3 needs torchvision) needs a package that is not installed, so there is nothing to pin an
-implementation to: it is reported as `not built`, and the other metrics still run.  A metric whose weights were not given is reported as such, likewise.  --precision is the arithmetic of the networks: f32 (default: exact-fp32 MFMA) or x3 (split-bf16: hi + lo bf16 operand pairs, fp32
+parity with the published checkpoint is unmeasured); --fid_weights is the `pt_inception-2015-12-05` state dict of pytorch-fid (.pth or .safetensors; FID:
+Inception-v3 written from its published topology, freefine_amd/inception.py, held to the torch restatement tests/inception_ref.py -- torchvision is not installed,
+parity with the published checkpoint and with torchvision's classes is unmeasured) and needs --fid_path, the folder of real images; without either FID is
+reported as `not built` into this run, and the other metrics still run.  A metric whose weights were not given is reported as such, likewise.  FID is always
+computed in fp32, whatever --precision says (11.5 GFLOP per image: seconds for a whole run).  --precision is the arithmetic of the networks: f32 (default: exact-fp32 MFMA) or x3 (split-bf16: hi + lo bf16 operand pairs, fp32
 accumulation; the ViT towers, HPS's two among them, are built with x3=True and the MD pipeline with from_pretrained(..., x3=True)).
 For an edit that is neither a translation, a 2-D rotation nor a uniform scale, MD reads the case's correspondence map: <tree>/correspondence/<da>/<ins>/<edit>.npy
 beside the folder of generated images (the 3d_rgb variant of evaluation/FreeFine/freefine_batch_infer_2d.py writes it with --save-correspondence).
@@ -30,8 +34,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 
 NAMES = ("FID", "IRS", "HPS", "BGC", "SUBC", "WRAP_E", "MD", "FID_DINO", "FID_KD")
-NOT_BUILT = {"FID": "not built (Inception-v3: torchvision is not installed, nothing to pin it to)",
-             "IRS": "not built into this run (--irs_weights / --irs_tokenizer missing)"}      # IRS is built: run() answers it before this table is read
+NOT_BUILT = {"FID": "not built into this run (--fid_weights / --fid_path missing)",
+             "IRS": "not built into this run (--irs_weights / --irs_tokenizer missing)"}      # both are built: run() answers them before this table is read
 LEVEL_WORDS = {1: ("lightly", "slightly", "gently", "mildly"), 2: ("moderately", "markedly", "appreciably"), 3: ("heavily", "intensely", "significantly", "strongly")}
 PATH_KEYS = ("ori_img_path", "coarse_input_path", "ori_mask_path", "tgt_mask_path")
 
@@ -88,7 +92,7 @@ def build_parser():
     ap.add_argument("--gen_img_key", default="gen_img_path", help="JSON key of the generated image paths")
     ap.add_argument("--no_rotate", action="store_true", help="leave out the cases with a rotation")
     ap.add_argument("--3d", dest="three_d", action="store_true", help="use the 3-D evaluation's masks and coarse inputs")
-    ap.add_argument("--fid_path", default=None, help="folder of real images (FID_DINO, FID_KD)")
+    ap.add_argument("--fid_path", default=None, help="folder of real images (FID, FID_DINO, FID_KD)")
     ap.add_argument("--use_relative_path", action="store_true", help="join the JSON's paths to --base_dir")
     ap.add_argument("--base_dir", default=None, help="base folder of relative paths")
     ap.add_argument("--clip_weights", default=None, help="CLIP ViT-B/32 weights (BGC)")
@@ -99,7 +103,8 @@ def build_parser():
     ap.add_argument("--hps_tokenizer", default=None, help="folder with CLIP's vocab.json and merges.txt (HPS)")
     ap.add_argument("--irs_weights", default=None, help="ImageReward.pt: BLIP ViT-L/16, BLIP's BERT and the reward head (IRS)")
     ap.add_argument("--irs_tokenizer", default=None, help="folder with bert-base-uncased's vocab.txt (IRS)")
-    ap.add_argument("--precision", default="f32", choices=("f32", "x3"), help="arithmetic of the networks: f32 = exact fp32, x3 = split-bf16")
+    ap.add_argument("--fid_weights", default=None, help="pt_inception-2015-12-05 state dict of pytorch-fid, .pth or .safetensors (FID; needs --fid_path)")
+    ap.add_argument("--precision", default="f32", choices=("f32", "x3"), help="arithmetic of the networks: f32 = exact fp32, x3 = split-bf16 (FID stays in fp32)")
     ap.add_argument("--md_visible_only", action="store_true", help="MD: drop keypoints hidden in the coarse 3-D edit (needs correspondence_visible images; "
                                                                    "not the reference's metric)")
     ap.add_argument("--md_keypoints", default="default", choices=("default", "sift"),
@@ -109,6 +114,7 @@ def build_parser():
     ap.add_argument("--dino_config", default="vitb16", help=argparse.SUPPRESS)
     ap.add_argument("--hps_config", default="vith14", choices=("vith14", "tiny"), help=argparse.SUPPRESS)      # with "tiny", --hps_tokenizer bytes: text.ByteTokenizer
     ap.add_argument("--irs_config", default="med", choices=("med", "tiny"), help=argparse.SUPPRESS)            # with "tiny", --irs_tokenizer bytes: text.ByteTokenizer
+    ap.add_argument("--fid_config", default="full", choices=("full", "tiny"), help=argparse.SUPPRESS)          # "tiny": the test widths, input side 75
     return ap
 
 
@@ -138,6 +144,10 @@ def main(argv=None):
             vcfg, tcfg = ("tiny16", "tiny") if args.irs_config == "tiny" else ("vitl16", "med")
             model = irs.HipImageReward.from_state(load_state(args.irs_weights), irs.load_tokenizer(args.irs_tokenizer), vcfg, tcfg, dtype=torch.float32, x3=x3)
             return FM.calculate_irs(data, label, model)
+        if name == "FID":
+            if not args.fid_weights or not args.fid_path:
+                return NOT_BUILT["FID"]
+            return FM.calculate_fid(data, label, args.fid_path, load_state(args.fid_weights), config=args.fid_config, side=75 if args.fid_config == "tiny" else None)
         if name in NOT_BUILT:
             return NOT_BUILT[name]
         if name == "HPS":

@@ -20,6 +20,8 @@ IMGPREP_MAX_TAPS = 2 * 3 * IMGPREP_MAX_SIDE + 1      # FFN_IMGPREP_MAX_TAPS
 BOX_NMS_MAX = 16384          # FFN_BOX_NMS_MAX
 KEEP_NONE, KEEP_SUM_LT128, KEEP_GT128 = 0, 1, 2
 CHAIN_MAXL, CHAIN_MAXW = 8, 1024      # FFN_CHAIN_MAXL, FFN_CHAIN_MAXW
+CONV_RELU = 1
+POOL_MAX, POOL_AVG_VALID = 0, 1
 
 
 class IgemmDesc(C.Structure):
@@ -100,6 +102,15 @@ class CoarseEditDesc(C.Structure):
         ("src_img", C.c_void_p), ("src_mask", C.c_void_p), ("bg", C.c_void_p), ("hole_img", C.c_void_p), ("hole_mask", C.c_void_p), ("inv", C.c_void_p),
         ("final_img", C.c_void_p), ("tmask", C.c_void_p), ("trans_hole", C.c_void_p),
         ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("mask_c", C.c_int), ("hole_mask_c", C.c_int),
+    ]
+
+
+class Conv2dDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int), ("Hin", C.c_int), ("Win", C.c_int), ("Cin", C.c_int), ("N", C.c_int),
+        ("KH", C.c_int), ("KW", C.c_int), ("stride", C.c_int), ("pad_h", C.c_int), ("pad_w", C.c_int),
+        ("ldx", C.c_int), ("ldo", C.c_int), ("Kpad", C.c_int), ("flags", C.c_int),
     ]
 
 
@@ -188,6 +199,10 @@ SYMBOLS = {
     "ffn_box_nms": (_i, [_vp, _vp, _vp, _i, _f]),
     "ffn_image_to_nhwc": (_i, [_vp, _i, _vp, _vp, _l, _i]),
     "ffn_nhwc_to_image": (_i, [_vp, _i, _vp, _vp, _i, _i, _i]),
+    "ffn_conv2d": (_i, [_vp, _i, C.POINTER(Conv2dDesc)]),
+    "ffn_pool2d": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "ffn_mean_hw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    "ffn_fid_prep": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 // C ABI of libfreefine_hip.so (see include/freefine_hip.h), the general unit: version, error state, device info, graph launch, norms, elementwise /
 // scheduler / layout kernels and the two small convolution-side entries.  Host-side launch glue only: argument validation, dynamic-LDS opt-in.  No
 // allocation, no synchronisation, everything on the caller's stream.  Every other unit exports the entries of its own kernels the same way
-// (capi_igemm.hip, capi_attn.hip, capi_splat.hip, attn_causal.hip, dift.hip, imgprep.hip); capi_common.h holds what they share.
+// (capi_igemm.hip, capi_attn.hip, capi_splat.hip, attn_causal.hip, dift.hip, imgprep.hip, inception.hip); capi_common.h holds what they share.
 #include <stdlib.h>
 #include <string.h>
 
@@ -12,7 +12,7 @@
 
 __thread char g_err[512] = "";
 
-extern "C" int ffn_version(void) { return 15; }      // 15: the ImageReward score's BERT (ffn_embed_tokens_ln, ffn_affine_chain); 14: automatic mask generation (ffn_upsample_bicubic_stats, ffn_box_nms); 13: the GeoDiffuser warp of GeoBench-3D (ffn_geo_project, ffn_splat_composite, ffn_mesh_cover); 12: SIFT keypoints for Mean Distance (ffn_sift_base, ffn_gauss_blur_f32, ffn_decimate2_f32, ffn_sift_extrema, ffn_sift_refine_orient, ffn_sift_describe, ffn_knn2_u8; FFN_ENOSPC); 11: click-to-mask (ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic, FFN_ELT_GELU); 10: the correspondence map of the point-cloud warp (ffn_splat_ids, ffn_splat_correspond); 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
+extern "C" int ffn_version(void) { return 16; }      // 16: the Inception-v3 extractor of FID (ffn_conv2d, ffn_pool2d, ffn_mean_hw, ffn_fid_prep); 15: the ImageReward score's BERT (ffn_embed_tokens_ln, ffn_affine_chain); 14: automatic mask generation (ffn_upsample_bicubic_stats, ffn_box_nms); 13: the GeoDiffuser warp of GeoBench-3D (ffn_geo_project, ffn_splat_composite, ffn_mesh_cover); 12: SIFT keypoints for Mean Distance (ffn_sift_base, ffn_gauss_blur_f32, ffn_decimate2_f32, ffn_sift_extrema, ffn_sift_refine_orient, ffn_sift_describe, ffn_knn2_u8; FFN_ENOSPC); 11: click-to-mask (ffn_sam_patch_rows, ffn_sam_patch_rows_pair, ffn_hyper_masks, ffn_upsample_bicubic, FFN_ELT_GELU); 10: the correspondence map of the point-cloud warp (ffn_splat_ids, ffn_splat_correspond); 9: the case preparation of the GeoBench harness (ffn_resize_taps8_u8, ffn_resize_gather_u8, ffn_dilate_u8, ffn_mask_bbox_u8, ffn_coarse_edit_2d); 8: ffn_pool_layernorm, ffn_cosine_rows; 2: FFN_ATT_CAUSAL, FFN_IG_OUT_QGELU, ffn_embed_tokens; 3: the igemm tile query is gone (ffn_igemm_kernel_name answers); 4: ffn_dift_match; 5: ffn_resize_pil_bilinear_u8, ffn_vit_patch_rows; 6: ffn_resize_pil_u8; 7: ffn_vit_patch_rows_pair
 extern "C" const char* ffn_last_error(void) { return g_err; }
 extern "C" int ffn_device_info(int device, char* name, int name_len) {
     hipDeviceProp_t prop;

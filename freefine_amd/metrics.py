@@ -21,8 +21,11 @@ The Human Preference Score (human_preference_score.py) is the cosine between Ope
 caption.  freefine_amd/hps.py HipHPSv2 runs both towers and the cosine on the project's kernels, pinned to transformers' CLIP*ModelWithProjection (the same
 arithmetic; hpsv2 and open_clip exist nowhere this is tested).  calculate_hps below is the driver; weights and tokenizer files from the caller.
 
-The remaining extractors of the suite (Inception-v3 for FID, ImageReward for IRS) need packages that are not installed (torchvision; ImageReward and BLIP), so
-there is nothing to pin them to and they are NOT built; evaluation/metrics/main.py reports them as such.
+FID itself (FID/fid.py) feeds the Frechet distance with the 2048-d pool3 features of pytorch-fid's Inception-v3.  torchvision is not installed, so the network
+is written from its published topology: freefine_amd/inception.py HipFIDInception runs it on the project's convolution and pooling kernels (csrc/convkk.h), held to
+the torch restatement tests/inception_ref.py, whose four patched FID blocks are pinned to the reference's classes by tests/golden/g20_fid_blocks.npz.
+get_inception_activations / calculate_fid below are the drivers; the weights (the pt_inception-2015-12-05 state dict) come from the caller, and parity with that
+checkpoint is unmeasured.  (The ImageReward score: freefine_amd/irs.py, calculate_irs below.)
 
 Mean Distance (MD/mean_distance.py), the one metric of the suite that measures the GEOMETRY of an edit, needs no foreign network: its feature extractor is
 DIFT, i.e. Stable Diffusion itself, and runs on the project's kernels (freefine_amd/dift.py: HipVAE + HipUNet.features; the correspondence search is
@@ -174,6 +177,36 @@ def calculate_fid_kd(data, image_label, real_root_path, model, batch_size=64, re
     model = _dino_model(model, x3)
     real, gen = parse_data(data, image_label, real_root_path)
     return kernel_distance(get_activations(real, model, batch_size, reader), get_activations(gen, model, batch_size, reader)).mean()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# FID (FID/fid.py): pool3 features of pytorch-fid's Inception-v3 into frechet_distance
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+def _inception_model(model, config="full", side=None):
+    """a HipFIDInception as it is; a state dict (pt_inception-2015-12-05 in pytorch-fid's layout) becomes one (fp32: the network has no other arithmetic)"""
+    if isinstance(model, dict):
+        from .inception import HipFIDInception
+        return HipFIDInception(config, model, side=side)
+    return model
+
+
+def get_inception_activations(files, model, batch_size=64):
+    """fid_score.py:get_activations (:93-143) with the Inception-v3 extractor -> float64 [len(files), 2048] in file order.  Every file is opened with
+    Image.open(f).convert("RGB"); any size is accepted.  model: a freefine_amd.inception.HipFIDInception; the dataset's transform (Resize((224, 224)) with PIL's
+    bilinear filter, ToTensor, Normalize(imagenet)) and the network's own resize to 299 and rescale run inside it, on the device.  Grouping by size, batching and
+    the order of the rows are get_activations's."""
+    return get_activations(files, model, batch_size)
+
+
+def calculate_fid(data, image_label, real_root_path, weights, batch_size=64, config="full", side=None):
+    """fid.py:calculate_fid: the Frechet distance between the Inception-v3 pool3 features of the real images and of the generated ones (data[...][image_label]).
+    The reference's parse_data quirk is kept: the real set is the directory listing of real_root_path (parse_data above).  Statistics in float64 (np.mean,
+    np.cov(rowvar=False)).  weights: a HipFIDInception or the state dict it is built from (the reference downloads it; here the caller brings it)."""
+    model = _inception_model(weights, config, side)
+    real, gen = parse_data(data, image_label, real_root_path)
+    m1, s1 = feature_statistics(get_inception_activations(real, model, batch_size))
+    m2, s2 = feature_statistics(get_inception_activations(gen, model, batch_size))
+    return frechet_distance(m1, s1, m2, s2)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------

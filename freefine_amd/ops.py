@@ -1743,3 +1743,79 @@ def tune_table_load(path):
     if not torch.is_tensor(table) or table.ndim != 2 or table.dtype not in (torch.int32, torch.int64):
         return 0
     return tune_table_import(table)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the Inception-v3 kernels of FID (csrc/convkk.h): NHWC fp32 tensors [B, H, W, C] that may be channel slices of a wider tensor (column views)
+# ---------------------------------------------------------------------------------------------------------------
+def _nhwc_view(t):
+    """[B, H, W, C] fp32 with contiguous channels and pixels `ld` apart (a tensor or its [..., a:b] slice) -> ld"""
+    assert t.dtype == torch.float32 and t.ndim == 4 and t.is_cuda
+    B, H, W, C = t.shape
+    ld = t.stride(2) if W > 1 else (t.stride(1) if H > 1 else (t.stride(0) if B > 1 else C))
+    assert C == 1 or t.stride(3) == 1
+    assert (W == 1 or t.stride(2) == ld) and (H == 1 or t.stride(1) == W * ld) and (B == 1 or t.stride(0) == H * W * ld) and ld >= C, (t.shape, t.stride())
+    return ld
+
+
+def conv_out_size(n, k, stride, pad):
+    return (n + 2 * pad - k) // stride + 1
+
+
+def conv2d_kk(x, w, bias, kh, kw, stride=1, pad=(0, 0), relu=True, out=None):
+    """x [B, H, W, Cin] view, w fp32 [N, Kpad] with columns (ky, kx, ci), bias fp32 [N] or None -> out [B, Hout, Wout, N] (a view to write into, or a new tensor):
+    ffn_conv2d, the implicit GEMM on the exact-fp32 MFMA."""
+    lib = L.load()
+    B, H, W, Cin = x.shape
+    N, Kpad = w.shape
+    assert w.dtype == torch.float32 and w.is_contiguous() and (bias is None or (bias.dtype == torch.float32 and bias.numel() == N and bias.is_contiguous()))
+    Ho, Wo = conv_out_size(H, kh, stride, pad[0]), conv_out_size(W, kw, stride, pad[1])
+    if out is None:
+        out = torch.empty(B, Ho, Wo, N, dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == (B, Ho, Wo, N), (tuple(out.shape), (B, Ho, Wo, N))
+    d = L.Conv2dDesc()
+    d.x, d.w, d.bias, d.out = x.data_ptr(), w.data_ptr(), _p(bias), out.data_ptr()
+    d.B, d.Hin, d.Win, d.Cin, d.N = B, H, W, Cin, N
+    d.KH, d.KW, d.stride, d.pad_h, d.pad_w = kh, kw, stride, pad[0], pad[1]
+    d.ldx, d.ldo, d.Kpad, d.flags = _nhwc_view(x), _nhwc_view(out), Kpad, (L.CONV_RELU if relu else 0)
+    M, K = B * Ho * Wo, kh * kw * Cin
+    L.check(_timed(f"convkk_kernel {kh}x{kw} s{stride}", 2.0 * M * N * K, 4.0 * (B * H * W * Cin + N * K + M * N), lambda: lib.ffn_conv2d(_stream(), L.FFN_F32, CT.byref(d))),
+            "ffn_conv2d")
+    return out
+
+
+def pool2d(x, op, k=3, stride=1, pad=0, out=None):
+    """x [B, H, W, C] view -> [B, Hout, Wout, C]: op "max" (max_pool2d) or "avg_valid" (avg_pool2d(count_include_pad=False)); ffn_pool2d"""
+    lib = L.load()
+    B, H, W, C = x.shape
+    Ho, Wo = conv_out_size(H, k, stride, pad), conv_out_size(W, k, stride, pad)
+    if out is None:
+        out = torch.empty(B, Ho, Wo, C, dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == (B, Ho, Wo, C)
+    code = {"max": L.POOL_MAX, "avg_valid": L.POOL_AVG_VALID}[op]
+    L.check(_timed(f"pool2d_kernel<{op}>", 0.0, 4.0 * C * B * (H * W + Ho * Wo),
+                   lambda: lib.ffn_pool2d(_stream(), code, x.data_ptr(), out.data_ptr(), B, H, W, C, _nhwc_view(x), _nhwc_view(out), k, stride, pad)), "ffn_pool2d")
+    return out
+
+
+def mean_hw(x):
+    """x [B, H, W, C] view -> fp32 [B, C]: AdaptiveAvgPool2d(1), pixels summed in ascending order (ffn_mean_hw)"""
+    lib = L.load()
+    B, H, W, C = x.shape
+    out = torch.empty(B, C, dtype=torch.float32, device=x.device)
+    L.check(_timed("mean_hw_kernel", 0.0, 4.0 * C * B * (H * W + 1), lambda: lib.ffn_mean_hw(_stream(), x.data_ptr(), out.data_ptr(), B, H * W, C, _nhwc_view(x))),
+            "ffn_mean_hw")
+    return out
+
+
+def fid_prep(img, lut, side_out):
+    """uint8 [B, S, S, 3] (device) + lut fp32 [3, 256] (vit_norm_table) -> fp32 [B, side_out, side_out, 4]: the lookup, ATen's bilinear resize (align_corners=False),
+    2 v - 1, a zero fourth channel (ffn_fid_prep)"""
+    lib = L.load()
+    assert img.dtype == torch.uint8 and img.ndim == 4 and img.shape[-1] == 3 and img.shape[1] == img.shape[2] and img.is_contiguous() and img.is_cuda
+    assert lut.dtype == torch.float32 and lut.shape == (3, 256) and lut.is_contiguous() and lut.device == img.device
+    B, S = img.shape[0], img.shape[1]
+    out = torch.empty(B, side_out, side_out, 4, dtype=torch.float32, device=img.device)
+    L.check(_timed("fid_prep_kernel", 0.0, 3.0 * B * S * S + 16.0 * B * side_out * side_out,
+                   lambda: lib.ffn_fid_prep(_stream(), img.data_ptr(), lut.data_ptr(), out.data_ptr(), B, S, side_out)), "ffn_fid_prep")
+    return out

@@ -639,6 +639,41 @@ int ffn_upsample_bicubic(void* stream, const float* src, float* dst, uint8_t* ma
 int ffn_upsample_bicubic_stats(void* stream, const float* src, int32_t* stats, uint8_t* mask, int N, int h, int w, int H, int W, float offset);
 int ffn_box_nms(void* stream, const float* boxes, uint64_t* suppress, int M, float thresh);
 
+/* ---- the Inception-v3 feature extractor of FID (ABI version 16; csrc/convkk.h, csrc/inception.hip, freefine_amd/inception.py) ----------------------------
+ * Reference: evaluation/metrics/FID/fid.py, fid_score.py and inception.py (pytorch-fid's InceptionV3).  Everything is fp32 and NHWC as a COLUMN VIEW: a pixel's
+ * channels are contiguous, consecutive pixels are `ld` floats apart (ld >= channels), so an entry reads or writes a slice of a wider tensor -- every branch of a
+ * Mixed block writes straight into its columns of the concatenated output.  Bytes outside the view are never written.  All entries: no allocation, no sync, the
+ * caller's stream; pointers 16-byte aligned and strides multiples of 4 floats; anything outside the stated limits is refused with FFN_EINVAL before any launch.
+ *
+ * ffn_conv2d: out[b][oy][ox][n] = act(bias[n] + sum over (ky, kx, ci) of x[b][oy stride - pad_h + ky][ox stride - pad_w + kx][ci] w[n][(ky KW + kx) Cin + ci]),
+ * taps outside the image contributing zero; Hout = (Hin + 2 pad_h - KH) / stride + 1 (floor), Wout likewise.  An implicit GEMM on the exact-fp32 MFMA
+ * (v_mfma_f32_16x16x4_f32): dtype FFN_F32 only, any other dtype returns FFN_ENOSYS.  x [B][Hin][Win] pixels of Cin channels, stride ldx; w [N][Kpad] with
+ * K = KH KW Cin <= Kpad, Kpad % 4 == 0 (columns K .. Kpad - 1 are not read); bias [N] or NULL; out [B][Hout][Wout] pixels of N channels, stride ldo.
+ * KH, KW in {1, 3, 5, 7} independently; stride 1 or 2 (both axes); pad_h, pad_w >= 0 independently; Cin % 4 == 0, N % 4 == 0.  flags: FFN_CONV_RELU
+ * (act = max(., 0); otherwise the identity).  The summation order is fixed: two runs give the same bits.
+ *
+ * ffn_pool2d: k x k windows, stride and pad on both axes, floor output sizes; FFN_POOL_MAX (max_pool2d: padding never wins) or FFN_POOL_AVG_VALID (the mean over
+ * the window's in-image taps, summed in (ky, kx) order: avg_pool2d(count_include_pad=False)).  k 1 .. 7, stride 1 .. k, 2 pad <= k, C % 4 == 0.
+ * ffn_mean_hw: y [B][C] (contiguous) = the mean over the HW pixels of x [B][HW] (stride ldx), summed in ascending order: AdaptiveAvgPool2d(1).
+ * ffn_fid_prep: src uint8 [B][side_in][side_in][3] -> out fp32 [B][side_out][side_out][4]: v = lut[c][byte] (lut fp32 [3][256]: ToTensor + Normalize, as
+ * ffn_vit_patch_rows takes it), ATen's upsample_bilinear2d with align_corners = False (scale = in / out in fp32, source = max(0, scale (dst + 0.5) - 0.5),
+ * blended as h0 (w0 v00 + w1 v01) + h1 (w0 v10 + w1 v11)), then 2 v - 1; the fourth channel is zero (the stem is a Cin = 4 convolution). */
+typedef struct ffn_conv2d_desc {
+    const float* x;
+    const float* w;
+    const float* bias;
+    float* out;
+    int B, Hin, Win, Cin, N;
+    int KH, KW, stride, pad_h, pad_w;
+    int ldx, ldo, Kpad, flags;
+} ffn_conv2d_desc;
+enum { FFN_CONV_RELU = 1 };
+enum { FFN_POOL_MAX = 0, FFN_POOL_AVG_VALID = 1 };
+int ffn_conv2d(void* stream, int dtype, const ffn_conv2d_desc* d);
+int ffn_pool2d(void* stream, int op, const float* x, float* y, int B, int Hin, int Win, int C, int ldx, int ldy, int k, int stride, int pad);
+int ffn_mean_hw(void* stream, const float* x, float* y, int B, int HW, int C, int ldx);
+int ffn_fid_prep(void* stream, const uint8_t* src, const float* lut, float* out, int B, int side_in, int side_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1005,8 +1005,111 @@ def run_g18():
     assert os.path.getsize(path) < 1_000_000
 
 
+def import_fid_inception():
+    """the reference's FID Inception module (evaluation/DiffusionHandles/Lama/saicinpainting/evaluation/losses/fid/inception.py) by file path, over a stub
+    `torchvision.models` whose inception.InceptionA / InceptionC / InceptionE are restated base classes: torchvision's constructors (the layers and their
+    names), no forward -- the four FID classes override it, and their forward is what G20 records.  Nothing here downloads: fid_inception_v3 and InceptionV3
+    are never called."""
+    import importlib.util
+    import types
+    import torch.nn as nn
+
+    class BasicConv2d(nn.Module):
+        def __init__(self, cin, cout, **kw):
+            super().__init__()
+            self.conv = nn.Conv2d(cin, cout, bias=False, **kw)
+            self.bn = nn.BatchNorm2d(cout, eps=0.001)
+
+        def forward(self, x):
+            return torch.relu(self.bn(self.conv(x)))
+
+    class InceptionA(nn.Module):
+        def __init__(self, in_channels, pool_features):
+            super().__init__()
+            self.branch1x1 = BasicConv2d(in_channels, 64, kernel_size=1)
+            self.branch5x5_1 = BasicConv2d(in_channels, 48, kernel_size=1)
+            self.branch5x5_2 = BasicConv2d(48, 64, kernel_size=5, padding=2)
+            self.branch3x3dbl_1 = BasicConv2d(in_channels, 64, kernel_size=1)
+            self.branch3x3dbl_2 = BasicConv2d(64, 96, kernel_size=3, padding=1)
+            self.branch3x3dbl_3 = BasicConv2d(96, 96, kernel_size=3, padding=1)
+            self.branch_pool = BasicConv2d(in_channels, pool_features, kernel_size=1)
+
+    class InceptionC(nn.Module):
+        def __init__(self, in_channels, channels_7x7):
+            super().__init__()
+            c7 = channels_7x7
+            self.branch1x1 = BasicConv2d(in_channels, 192, kernel_size=1)
+            self.branch7x7_1 = BasicConv2d(in_channels, c7, kernel_size=1)
+            self.branch7x7_2 = BasicConv2d(c7, c7, kernel_size=(1, 7), padding=(0, 3))
+            self.branch7x7_3 = BasicConv2d(c7, 192, kernel_size=(7, 1), padding=(3, 0))
+            self.branch7x7dbl_1 = BasicConv2d(in_channels, c7, kernel_size=1)
+            self.branch7x7dbl_2 = BasicConv2d(c7, c7, kernel_size=(7, 1), padding=(3, 0))
+            self.branch7x7dbl_3 = BasicConv2d(c7, c7, kernel_size=(1, 7), padding=(0, 3))
+            self.branch7x7dbl_4 = BasicConv2d(c7, c7, kernel_size=(7, 1), padding=(3, 0))
+            self.branch7x7dbl_5 = BasicConv2d(c7, 192, kernel_size=(1, 7), padding=(0, 3))
+            self.branch_pool = BasicConv2d(in_channels, 192, kernel_size=1)
+
+    class InceptionE(nn.Module):
+        def __init__(self, in_channels):
+            super().__init__()
+            self.branch1x1 = BasicConv2d(in_channels, 320, kernel_size=1)
+            self.branch3x3_1 = BasicConv2d(in_channels, 384, kernel_size=1)
+            self.branch3x3_2a = BasicConv2d(384, 384, kernel_size=(1, 3), padding=(0, 1))
+            self.branch3x3_2b = BasicConv2d(384, 384, kernel_size=(3, 1), padding=(1, 0))
+            self.branch3x3dbl_1 = BasicConv2d(in_channels, 448, kernel_size=1)
+            self.branch3x3dbl_2 = BasicConv2d(448, 384, kernel_size=3, padding=1)
+            self.branch3x3dbl_3a = BasicConv2d(384, 384, kernel_size=(1, 3), padding=(0, 1))
+            self.branch3x3dbl_3b = BasicConv2d(384, 384, kernel_size=(3, 1), padding=(1, 0))
+            self.branch_pool = BasicConv2d(in_channels, 192, kernel_size=1)
+
+    assert "torchvision" not in sys.modules, "G20 stubs torchvision: run it in a process that has not imported one"
+    tv, models, inc = types.ModuleType("torchvision"), types.ModuleType("torchvision.models"), types.ModuleType("torchvision.models.inception")
+    inc.InceptionA, inc.InceptionC, inc.InceptionE = InceptionA, InceptionC, InceptionE
+    models.inception, tv.models = inc, models
+    sys.modules.update({"torchvision": tv, "torchvision.models": models, "torchvision.models.inception": inc})
+    try:
+        path = os.path.join(RH.REF, "evaluation", "DiffusionHandles", "Lama", "saicinpainting", "evaluation", "losses", "fid", "inception.py")
+        spec = importlib.util.spec_from_file_location("ref_fid_inception", path)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+    finally:
+        for k in ("torchvision", "torchvision.models", "torchvision.models.inception"):
+            sys.modules.pop(k, None)
+    return mod
+
+
+def run_g20():
+    """The reference's four patched FID blocks -- FIDInceptionA(8, 4), FIDInceptionC(16, 8), FIDInceptionE_1(16), FIDInceptionE_2(16) -- in fp64 on 1 x C x 3 x 3
+    and 1 x C x 5 x 4 inputs, with the states tests/inception_ref.py seeded_state makes for tests/inception_ref.py block_shapes.  Stored: seeds, inputs, outputs
+    (the weights are regenerated from the seed by the test).  What it pins: which pool stands in front of branch_pool in each block, and the order of
+    concatenation."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import inception_ref as IR
+    M = import_fid_inception()
+    out = {}
+    cases = [("A", M.FIDInceptionA, 8, 4), ("C", M.FIDInceptionC, 16, 8), ("E1", M.FIDInceptionE_1, 16, None), ("E2", M.FIDInceptionE_2, 16, None)]
+    for i, (kind, cls, cin, arg) in enumerate(cases):
+        seed = 2000 + i
+        net = (cls(cin) if arg is None else cls(cin, arg)).double().eval()
+        state = IR.seeded_state(IR.block_shapes(kind, cin, arg), seed)
+        missing = net.load_state_dict(state, strict=False)
+        assert not missing.unexpected_keys and all(k.endswith("num_batches_tracked") for k in missing.missing_keys), missing
+        out[f"{kind}/seed"], out[f"{kind}/cin"], out[f"{kind}/arg"] = np.array(seed), np.array(cin), np.array(-1 if arg is None else arg)
+        for j, (h, w) in enumerate(((3, 3), (5, 4))):
+            x = rng_tensor(seed * 10 + j, (1, cin, h, w)).double()
+            y = net(x)
+            mine = IR.fid_block(kind, state, x)
+            print(f"[G20] {kind} {h}x{w}: out {tuple(y.shape)}, |y| max {y.abs().max():.3f}, restatement dev {(y - mine).abs().max():.2e}")
+            assert (y - mine).abs().max() <= 1e-12
+            out[f"{kind}/x{j}"], out[f"{kind}/y{j}"] = x.numpy(), y.numpy()
+    path = os.path.join(GOLD, "g20_fid_blocks.npz")
+    np.savez_compressed(path, **out)
+    print(f"[G20] {path}: {os.path.getsize(path)} bytes")
+    assert os.path.getsize(path) < 1_000_000
+
+
 if __name__ == "__main__":
-    only = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g6b", "g7", "g8", "g9", "g11", "g13", "g14", "g15", "g16", "g18"]
+    only = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g6b", "g7", "g8", "g9", "g11", "g13", "g14", "g15", "g16", "g18", "g20"]
     torch.set_grad_enabled(False)
     A, Mo = RH.import_reference() if set(only) & {"g1", "g3", "g4", "g5", "g9"} else (None, None)      # the pipeline's modules: only where a run takes them
     if "g1" in only:
@@ -1039,3 +1142,5 @@ if __name__ == "__main__":
         run_g16()
     if "g18" in only:
         run_g18()
+    if "g20" in only:
+        run_g20()
