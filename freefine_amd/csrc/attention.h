@@ -29,9 +29,7 @@
 #include "common.h"
 #include "../../include/freefine_hip.h"
 
-#ifndef ATT_XCD_MIN_GROUPS
-#define ATT_XCD_MIN_GROUPS 64
-#endif
+#define ATT_XCD_MIN_GROUPS 64      // (row, head) groups from which the attention kernels take the XCD-contiguous block order (see attn_kernel)
 #define ATT_MAXP FFN_ATT_MAXP
 #define ATT_MAXB FFN_ATT_MAXB
 enum { ATT_HEAD_RULE = FFN_ATT_HEAD_RULE, ATT_UNIFORM_SEL1 = FFN_ATT_UNIFORM_SEL1, ATT_UNIFORM_SEL0 = FFN_ATT_UNIFORM_SEL0 };

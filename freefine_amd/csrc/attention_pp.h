@@ -23,12 +23,9 @@
 #pragma once
 #include "attention.h"
 
-#ifndef ATTPP_PRIO
-// 2 (shipped): the softmax (V) segment runs at s_setprio 1 and the MFMA segment at 0 -- the MFMA chain is paced by the matrix pipe and
+// Priorities: the softmax (V) segment runs at s_setprio 1 and the MFMA segment at 0 -- the MFMA chain is paced by the matrix pipe and
 // loses nothing, while a prioritised MFMA wave takes the issue slots the partner's dependent exp -> cvt chains need (measured at
-// S = 4096, 16 rows: 353 -> 335 us one pass, 746 -> 729 us two passes; S = 1024: 73.8 -> 70.3 us); 1: the MFMA segment at 1; 0: none
-#define ATTPP_PRIO 2
-#endif
+// S = 4096, 16 rows: 353 -> 335 us one pass, 746 -> 729 us two passes; S = 1024: 73.8 -> 70.3 us; profiles/r2_pmc_attn_S4096_16rows_1pass.txt)
 #ifndef ATTPP_ABL
 #define ATTPP_ABL 0   // timing-only ablation builds of tools/native/attn_bench.hip: 1 no LDS-DMA, 2 no counted waits, 3 no softmax, 4 no MFMA, 5 no fragment reads, 6 half the MFMAs
 #endif
@@ -288,7 +285,7 @@ __global__ __launch_bounds__(512) void attn_pp_kernel(const AttnParams p) {
         __builtin_amdgcn_sched_barrier(0);
         attpp_barrier();
         mfma_qk();
-        if (ATTPP_PRIO == 2) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
         __builtin_amdgcn_sched_barrier(0);
         attpp_barrier();
 
@@ -310,14 +307,12 @@ __global__ __launch_bounds__(512) void attn_pp_kernel(const AttnParams p) {
             __builtin_amdgcn_sched_barrier(0);
             attpp_barrier();
             // ---- M segment ----
-            if (ATTPP_PRIO == 1) __builtin_amdgcn_s_setprio(1);
-            if (ATTPP_PRIO == 2) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             if (ATTPP_ABL != 4) {
                 mfma_pv();
                 mfma_qk();
             }
-            if (ATTPP_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-            if (ATTPP_PRIO == 2) __builtin_amdgcn_s_setprio(1);
+            __builtin_amdgcn_s_setprio(1);
             __builtin_amdgcn_sched_barrier(0);
             attpp_barrier();
         }

@@ -34,20 +34,9 @@
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((address_space(3))) uint8_t x3w_lds_u8_t;
 
-#ifndef X3W_KRING
-#define X3W_KRING 4   // K ring slots (32-key blocks): 4 = a block is requested one iteration ahead of its first read (measured faster on the same box: 1368 vs 1401 us, profiles/r6_x3w_ring_depth_and_dma_placement_ab.txt); 6 = two ahead, first fragments read ahead of the barrier
-#endif
-#ifndef X3W_SPREAD
-#define X3W_SPREAD 0  // 1: the iteration's LDS-DMA requests ride the vector-free MFMA gaps of its two steps; 0: all at its start (faster: see the header of the key loop)
-#endif
-#ifndef X3W_SUMP1
-#define X3W_SUMP1 0   // 1: the row sums of a unit's probabilities ride the phase-1 gaps of the step that SPLITS them instead of the phase-2 gaps beside their
-                      // exponentials.  Measured SLOWER on one box (profiles/r6_x3w_row_sums_in_phase1_ab.txt: 1461 vs 1412 us two-pass S = 4096, 832 vs 815 one-pass):
-                      // the phase-1 gaps (four split instructions + the fragment reads' issue) have no slack either.  Kept for the A/B only.
-#endif
-#ifndef X3W_PKSUB
-#define X3W_PKSUB 0   // 1: the two subtractions of a P-split pair (lo = x - hi) as ONE packed v_pk_add_f32 -- measured SLOWER (1448 vs 1382 us, profiles/r6_x3w_packed_split_sub_ab.txt); A/B only
-#endif
+// K ring slots (32-key blocks), also the kernel's LDS size (fx3w_lds_bytes, attn_x3w.hip).  Ring of 4, a block requested one iteration ahead of its first
+// read: 1368 vs 1401 us for a ring of 6 requested two ahead, profiles/r6_x3w_ring_depth_and_dma_placement_ab.txt
+constexpr int X3W_NKB = 4;
 #ifndef X3W_ABL
 #define X3W_ABL 0     // timing-only ablations (tools/native/x3w_bench.hip): 1 no softmax / split VALU, 2 no LDS-DMA in the loop, 3 no MFMA
 #endif
@@ -80,7 +69,7 @@ __global__ __launch_bounds__(256) void attn_x3w_kernel(const AttnParams p) {
     constexpr int D = 64, KT = 64;
     constexpr int KBLK = 2 * 4096;                              // one K block slot: 32 rows x 128 B, hi image | lo image
     constexpr int VIMG = 64 * 128, VSLOT = 2 * VIMG;            // one V^T tile slot: 64 rows (d) x 128 B (64 keys), hi image | lo image
-    constexpr int NKB = X3W_KRING, AHEAD = X3W_KRING == 6 ? 2 : 1;                                      // K ring: X3W_KRING block slots; a block is requested AHEAD iterations (= 2 AHEAD blocks) ahead of the iteration that reads it
+    constexpr int NKB = X3W_NKB, AHEAD = 1;                     // K ring: NKB block slots; a block is requested AHEAD iterations (= 2 AHEAD blocks) ahead of the iteration that reads it
     constexpr int OFF_V = NKB * KBLK, OFF_M = OFF_V + 2 * VSLOT, OFF_TOT = OFF_M + 1024;   // K ring | V^T ring of 2 tiles | key-mask bytes 4 x 256 | multi-pass sums 64 KB
     constexpr int OOB = (int)0x80000000;
     constexpr float FAST_THR = 6.0f;
@@ -370,29 +359,15 @@ __global__ __launch_bounds__(256) void attn_x3w_kernel(const AttnParams p) {
             else x3w_mma(fr[buf][0], ph[sp][qb], o[db][qb]);
         };
         // phase-1 group g: the six MFMAs of d k-step g beside the split of part g = (s' = g >> 1, qb = g & 1) of cu, four instructions per gap
-        auto p1_group = [&](auto G, auto&& next_reads, const f32x16 (&cu)[2], f32x16 (&nx)[2], float (&lp)[2][2]) {
+        auto p1_group = [&](auto G, auto&& next_reads, const f32x16 (&cu)[2], f32x16 (&nx)[2]) {
             constexpr int g = std::remove_reference_t<decltype(G)>::value, sp = g >> 1, qp = g & 1;
             typedef std::integral_constant<int, g> GT;
             const f32x16& x = cu[qp];
             uint32_t hw[4], lw[4];
             float d0[4], d1[4];
             auto S1 = [&](int i) { hw[i] = pack_bf16x2(x[8 * sp + 2 * i], x[8 * sp + 2 * i + 1]); };
-            auto S2 = [&](int i) {
-                if (X3W_PKSUB) {
-                    typedef float x3w_f32x2 __attribute__((ext_vector_type(2)));
-                    const x3w_f32x2 xv = {x[8 * sp + 2 * i], x[8 * sp + 2 * i + 1]};
-                    const x3w_f32x2 hv = {__uint_as_float(hw[i] << 16), __uint_as_float(hw[i] & 0xffff0000u)};
-                    x3w_f32x2 dv;                                // (written as `xv - hv` the compiler scalarises it again: two v_add_f32_e64 with neg modifiers)
-                    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(dv) : "v"(xv), "v"(hv));
-                    d0[i] = dv[0]; d1[i] = dv[1];
-                } else {
-                    d0[i] = x[8 * sp + 2 * i] - __uint_as_float(hw[i] << 16); d1[i] = x[8 * sp + 2 * i + 1] - __uint_as_float(hw[i] & 0xffff0000u);
-                }
-                if (X3W_SUMP1) {                                 // the row sums of cu, two adds per gap, pinned to it (otherwise sunk to the end of the step)
-                    lp[qp][0] += x[8 * sp + 2 * i]; lp[qp][1] += x[8 * sp + 2 * i + 1];
-                    asm volatile("" : "+v"(lp[qp][0]), "+v"(lp[qp][1]));
-                }
-            };
+            // two scalar subtractions: one packed v_pk_add_f32 measured slower (1448 vs 1382 us, profiles/r6_x3w_packed_split_sub_ab.txt)
+            auto S2 = [&](int i) { d0[i] = x[8 * sp + 2 * i] - __uint_as_float(hw[i] << 16); d1[i] = x[8 * sp + 2 * i + 1] - __uint_as_float(hw[i] & 0xffff0000u); };
             auto S3 = [&](int i) { lw[i] = pack_bf16x2(d0[i], d1[i]); };
             constexpr bool valu = X3W_ABL != 1;
             next_reads();
@@ -408,15 +383,16 @@ __global__ __launch_bounds__(256) void attn_x3w_kernel(const AttnParams p) {
             X3W_SB();
         };
         // phase-2 group (db, s'): its six MFMAs beside exp2 + row sum of scores [LO, HI) of nx (flat index: qb = idx >> 4, register idx & 15): two
-        // v_exp per gap, the adds one gap behind their exponentials
+        // v_exp per gap, the adds one gap behind their exponentials (the sums in the phase-1 gaps of the step that splits the unit measured slower:
+        // 1461 vs 1412 us, profiles/r6_x3w_row_sums_in_phase1_ab.txt)
         auto p2_group = [&](auto DB, auto SP, auto BUF, auto LO, auto HI, auto DOEXP, auto&& next_reads, f32x16 (&nx)[2], float (&lp)[2][2]) {
             constexpr int lo = decltype(LO)::value, hi = decltype(HI)::value;
             constexpr bool doexp = decltype(DOEXP)::value != 0 && X3W_ABL != 1;
             typedef decltype(DB) DBT; typedef decltype(SP) SPT; typedef decltype(BUF) BT;
             auto EX = [&](int idx) { if (doexp && idx >= lo && idx < hi) nx[idx >> 4][idx & 15] = __builtin_amdgcn_exp2f(nx[idx >> 4][idx & 15]); };
-            auto AD = [&](int idx) { if (!X3W_SUMP1 && doexp && idx >= lo && idx < hi) lp[idx >> 4][idx & 1] += nx[idx >> 4][idx & 15]; };
+            auto AD = [&](int idx) { if (doexp && idx >= lo && idx < hi) lp[idx >> 4][idx & 1] += nx[idx >> 4][idx & 15]; };
             // the sums must EXIST at the end of their gap (pure register arithmetic is otherwise sunk to its first use, the end of the step)
-            auto PIN = [&]() { if (doexp && !X3W_SUMP1) asm volatile("" : "+v"(lp[0][0]), "+v"(lp[0][1]), "+v"(lp[1][0]), "+v"(lp[1][1])); };
+            auto PIN = [&]() { if (doexp) asm volatile("" : "+v"(lp[0][0]), "+v"(lp[0][1]), "+v"(lp[1][0]), "+v"(lp[1][1])); };
             next_reads();
             mma_pv(DBT{}, SPT{}, BT{}, I0{}, I0{}); EX(lo); EX(lo + 1); X3W_SB();
             mma_pv(DBT{}, SPT{}, BT{}, I0{}, I1{}); EX(lo + 2); EX(lo + 3); AD(lo); AD(lo + 1); PIN(); X3W_SB();
@@ -448,7 +424,7 @@ __global__ __launch_bounds__(256) void attn_x3w_kernel(const AttnParams p) {
         //   phase 2:  O += V^T(tile at voff, key k-steps 2 AB, 2 AB + 1).P  (24 MFMAs)             beside   max / exp2 / row sums of nx
         // KPRE: the first two K groups are already in buffers 0 / 1 (requested by the previous step); KNEXT: request the next step's (block at koff_next).
         // Fragment groups rotate through four buffers, each requested two groups (>= 12 MFMAs) ahead of its first use.
-        auto step = [&](auto AB_, auto LAST_, auto KPRE_, auto KNEXT_, int koff, int maddr, int voff, int koff_next, auto&& dmaf) {
+        auto step = [&](auto AB_, auto LAST_, auto KPRE_, auto KNEXT_, int koff, int maddr, int voff, int koff_next) {
             constexpr int ab = decltype(AB_)::value;
             constexpr bool last = decltype(LAST_)::value != 0, kpre = decltype(KPRE_)::value != 0, knext = decltype(KNEXT_)::value != 0;
             typedef std::integral_constant<int, 2 * ab> SV0;
@@ -459,52 +435,36 @@ __global__ __launch_bounds__(256) void attn_x3w_kernel(const AttnParams p) {
             if (!last) {
                 const uint32_t mb = mask_byte(maddr);
                 if (!kpre) { rd_k(koff, I0{}, I0{}); rd_k(koff, I1{}, I1{}); }
-                if (X3W_SUMP1) lpart[0][0] = lpart[0][1] = lpart[1][0] = lpart[1][1] = 0.f;
                 X3W_SB();
-                p1_group(I0{}, [&]() { rd_k(koff, I2{}, I2{}); }, cu, nx, lpart);
-                p1_group(I1{}, [&]() { rd_k(koff, I3{}, I3{}); }, cu, nx, lpart);
-                p1_group(I2{}, [&]() { rd_v(voff, I0{}, SV0{}, I0{}); }, cu, nx, lpart);
-                p1_group(I3{}, [&]() { rd_v(voff, I0{}, SV1{}, I1{}); }, cu, nx, lpart);
+                p1_group(I0{}, [&]() { rd_k(koff, I2{}, I2{}); }, cu, nx);
+                p1_group(I1{}, [&]() { rd_k(koff, I3{}, I3{}); }, cu, nx);
+                p1_group(I2{}, [&]() { rd_v(voff, I0{}, SV0{}, I0{}); }, cu, nx);
+                p1_group(I3{}, [&]() { rd_v(voff, I0{}, SV1{}, I1{}); }, cu, nx);
                 // the augmenting k-step closes the chains: scores relative to the query's reference, masked keys at -1e30; the third V^T group is requested here
                 rd_v(voff, I1{}, SV0{}, I2{});
                 const u32x4 ka = kaug_of(mb);
                 if (X3W_ABL != 3) x3w_mma(ka, qaug[0], nx[0]);
-                dmaf(I0{}); X3W_SB();                           // (the gaps without vector work carry this step's share of the iteration's LDS-DMA requests)
+                X3W_SB();
                 if (X3W_ABL != 3) x3w_mma(ka, qaug[1], nx[1]);
-                dmaf(I1{}); X3W_SB();
+                X3W_SB();
                 // phase 2, group 0: the unit maxima ride its MFMAs
                 mma_pv(I0{}, I0{}, I0{}, I0{}, I0{}); scan_a(I0{}, nx); X3W_SB();
                 mma_pv(I0{}, I0{}, I0{}, I0{}, I1{}); scan_b(I0{}, nx); X3W_SB();
                 mma_pv(I0{}, I0{}, I0{}, I0{}, I2{}); scan_a(I1{}, nx); X3W_SB();
                 mma_pv(I0{}, I0{}, I0{}, I1{}, I0{}); scan_b(I1{}, nx); X3W_SB();
-                mma_pv(I0{}, I0{}, I0{}, I1{}, I1{}); dmaf(I2{}); X3W_SB();
-                mma_pv(I0{}, I0{}, I0{}, I1{}, I2{}); dmaf(I3{}); X3W_SB();
+                mma_pv(I0{}, I0{}, I0{}, I1{}, I1{}); X3W_SB();
+                mma_pv(I0{}, I0{}, I0{}, I1{}, I2{}); X3W_SB();
                 const bool rr = X3W_ABL != 1 && need_reref();
                 if (rr) reref(nx);
-                if (!X3W_SUMP1) lpart[0][0] = lpart[0][1] = lpart[1][0] = lpart[1][1] = 0.f;
+                lpart[0][0] = lpart[0][1] = lpart[1][0] = lpart[1][1] = 0.f;
                 X3W_SB();
                 p2_group(I0{}, I1{}, I1{}, I0{}, std::integral_constant<int, 11>{}, I1{}, [&]() { rd_v(voff, I1{}, SV1{}, I3{}); }, nx, lpart);
                 p2_group(I1{}, I0{}, I2{}, std::integral_constant<int, 11>{}, std::integral_constant<int, 22>{}, I1{}, [&]() { if (knext) rd_k(koff_next, I0{}, I0{}); }, nx, lpart);
                 p2_group(I1{}, I1{}, I3{}, std::integral_constant<int, 22>{}, std::integral_constant<int, 32>{}, I1{}, [&]() { if (knext) rd_k(koff_next, I1{}, I1{}); }, nx, lpart);
-                if (X3W_SUMP1) {                                // lpart = the sums of cu (this unit, at the OLD reference): in before the move
-                    lacc[0] += lpart[0][0] + lpart[0][1];
-                    lacc[1] += lpart[1][0] + lpart[1][1];
-                }
                 if (rr) rescale();                              // O and the sums through this unit are complete at the old reference: now they move
-                if (!X3W_SUMP1) {                               // lpart = the sums of nx (the next unit, exponentiated at the NEW reference)
-                    lacc[0] += lpart[0][0] + lpart[0][1];
-                    lacc[1] += lpart[1][0] + lpart[1][1];
-                }
+                lacc[0] += lpart[0][0] + lpart[0][1];           // lpart = the sums of nx (the next unit, exponentiated at the NEW reference)
+                lacc[1] += lpart[1][0] + lpart[1][1];
             } else {
-                if (X3W_SUMP1) {
-#pragma unroll
-                    for (int qb = 0; qb < 2; ++qb) {
-                        float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-                        for (int i = 0; i < 16; i += 2) { a0 += cu[qb][i]; a1 += cu[qb][i + 1]; }
-                        lacc[qb] += a0 + a1;
-                    }
-                }
                 rd_v(voff, I0{}, SV0{}, I0{}); rd_v(voff, I0{}, SV1{}, I1{}); rd_v(voff, I1{}, SV0{}, I2{}); rd_v(voff, I1{}, SV1{}, I3{});
                 split_part(I0{}, cu); split_part(I1{}, cu); split_part(I2{}, cu); split_part(I3{}, cu);
                 X3W_SB();
@@ -518,7 +478,6 @@ __global__ __launch_bounds__(256) void attn_x3w_kernel(const AttnParams p) {
         for (int bk = 0; bk < 2 * AHEAD + 1; ++bk) { dma_kblk(bk, bk < 2 * ntiles, 0); dma_kblk(bk, bk < 2 * ntiles, 1); }
         dma_v(0, 0); dma_v(0, 1); dma_v(0, 2); dma_v(0, 3);
         dma_mask(0, true); dma_mask(1, ntiles > 1);
-        if (AHEAD == 2) dma_mask(2, ntiles > 2);
         dma_done();
         attpp_barrier();
         {
@@ -526,62 +485,44 @@ __global__ __launch_bounds__(256) void attn_x3w_kernel(const AttnParams p) {
             rd_k(0, I0{}, I0{}); rd_k(0, I1{}, I1{}); rd_k(0, I2{}, I2{}); rd_k(0, I3{}, I3{});
             qk_grp(I0{}, I0{}, s0); qk_grp(I1{}, I1{}, s0); qk_grp(I2{}, I2{}, s0); qk_grp(I3{}, I3{}, s0);
             if (X3W_ABL != 3) aug_grp(ka, s0);
-            if (AHEAD == 2) { rd_k(KBLK, I0{}, I0{}); rd_k(KBLK, I1{}, I1{}); }   // the first two groups of unit 1's K block, for the first step
             scan(I0{}, s0); scan(I1{}, s0);
             if (X3W_ABL != 1 && need_reref()) { reref(s0); rescale(); }
             lpart[0][0] = lpart[0][1] = lpart[1][0] = lpart[1][1] = 0.f;
             expsum(I0{}, std::integral_constant<int, 32>{}, s0);
-            if (!X3W_SUMP1) {                                   // (X3W_SUMP1: unit 0's sums are taken by the step that splits it, like every unit's)
-                lacc[0] += lpart[0][0] + lpart[0][1];
-                lacc[1] += lpart[1][0] + lpart[1][1];
-            }
+            lacc[0] += lpart[0][0] + lpart[0][1];
+            lacc[1] += lpart[1][0] + lpart[1][1];
         }
-        if (AHEAD == 1) {
-            lds_done();
-            attpp_barrier();                                    // every wave has read K block 0: its slot may be re-filled
-        }
-        typedef std::integral_constant<int, AHEAD == 2> PRE;    // fragments of the next K block requested across the step / iteration boundary
+        lds_done();
+        attpp_barrier();                                        // every wave has read K block 0: its slot may be re-filled
 
         // Hazards (iteration t = one barrier interval = units 2 t, 2 t + 1): it reads K blocks 2 t + 1, 2 t + 2, the mask bytes of tiles t, t + 1 and V^T(t) -- all
         // complete since the barrier that started it (every wave waits for its own LDS-DMA pieces, vmcnt(0), before the barrier that ends an iteration).
-        // Shipped form (ring of 4, AHEAD = 1): at its START it requests K blocks 2 t + 3, 2 t + 4 (the slots of blocks 2 t - 1, 2 t, last read in iteration t - 1),
-        // V^T(t + 1) (slot of V^T(t - 1)) and the mask bytes of tile t + 2 (slot of tile t - 2).  Ring of 6 (X3W_KRING = 6, AHEAD = 2; measured slower): blocks
-        // 2 t + 5, 2 t + 6 and the mask bytes of tile t + 3, and the first fragments of block 2 t + 3 are read ahead of the barrier that ends the iteration.
-        // X3W_SPREAD = 1 puts one request into each vector-free MFMA gap instead of the iteration's start (also slower).  Requests past the end of the keys go out
-        // with an out-of-range offset (zeros into a slot nobody reads): no branch in the loop.  No LDS wait at the barrier: every fragment read (except, ring of 6,
-        // the four requested for the next iteration) has been consumed by an MFMA.
+        // At its START it requests K blocks 2 t + 3, 2 t + 4 (the slots of blocks 2 t - 1, 2 t, last read in iteration t - 1), V^T(t + 1) (slot of V^T(t - 1)) and
+        // the mask bytes of tile t + 2 (slot of tile t - 2); one request per vector-free MFMA gap instead measured slower
+        // (1406 vs 1368 us, the x3w_k6s rows of profiles/r6_x3w_ring_depth_and_dma_placement_ab.txt).  Requests past the end of the keys go out with an out-of-range offset (zeros into a slot nobody
+        // reads): no branch in the loop.
         int t = 0;
         for (; t + 1 < ntiles; ++t) {
-            const int koffA = ((2 * t + 1) % NKB) * KBLK, koffB = ((2 * t + 2) % NKB) * KBLK, koffN = ((2 * t + 3) % NKB) * KBLK, voff = OFF_V + (t & 1) * VSLOT;
+            const int koffA = ((2 * t + 1) % NKB) * KBLK, koffB = ((2 * t + 2) % NKB) * KBLK, voff = OFF_V + (t & 1) * VSLOT;
             const int maddrA = OFF_M + (t & 3) * 256 + 32 + mrow, maddrB = OFF_M + ((t + 1) & 3) * 256 + mrow;
             const int bA = 2 * t + 2 * AHEAD + 1, bB = bA + 1, tM = t + AHEAD + 1;
             const bool vA = bA < 2 * ntiles, vB = bB < 2 * ntiles;
-            if (!X3W_SPREAD && X3W_ABL != 2) {
+            if (X3W_ABL != 2) {
                 dma_kblk(bA, vA, 0); dma_kblk(bA, vA, 1); dma_kblk(bB, vB, 0); dma_kblk(bB, vB, 1);
                 dma_v(t + 1, 0); dma_v(t + 1, 1); dma_v(t + 1, 2); dma_v(t + 1, 3);
                 dma_mask(tM, tM < ntiles);
             }
-            step(I0{}, I0{}, PRE{}, I1{}, koffA, maddrA, voff, koffB, [&](auto I) {
-                constexpr int i = decltype(I)::value;
-                if (X3W_ABL == 2 || !X3W_SPREAD) return;
-                if (i == 0) { dma_kblk(bA, vA, 0); dma_mask(tM, tM < ntiles); }
-                else if (i == 1) dma_kblk(bA, vA, 1);
-                else if (i == 2) dma_kblk(bB, vB, 0);
-                else dma_kblk(bB, vB, 1);
-            });
-            step(I1{}, I0{}, I1{}, PRE{}, koffB, maddrB, voff, koffN, [&](auto I) {
-                if (X3W_ABL == 2 || !X3W_SPREAD) return;
-                dma_v(t + 1, decltype(I)::value);
-            });
+            step(I0{}, I0{}, I0{}, I1{}, koffA, maddrA, voff, koffB);
+            step(I1{}, I0{}, I1{}, I0{}, koffB, maddrB, voff, 0);
             dma_done();
-            if (AHEAD == 1) lds_done();
+            lds_done();
             attpp_barrier();
         }
         {   // the last tile: unit 2 t + 1 has no successor
             const int koffA = ((2 * t + 1) % NKB) * KBLK, voff = OFF_V + (t & 1) * VSLOT;
             const int maddrA = OFF_M + (t & 3) * 256 + 32 + mrow;
-            step(I0{}, I0{}, PRE{}, I0{}, koffA, maddrA, voff, 0, [&](auto) {});
-            step(I1{}, I1{}, I0{}, I0{}, 0, 0, voff, 0, [&](auto) {});
+            step(I0{}, I0{}, I0{}, I0{}, koffA, maddrA, voff, 0);
+            step(I1{}, I1{}, I0{}, I0{}, 0, 0, voff, 0);
             lds_done();
             attpp_barrier();                                    // every fragment read of this pass is retired before the next pass's first DMA
         }

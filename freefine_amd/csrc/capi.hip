@@ -36,8 +36,7 @@ extern "C" int ffn_graph_launch(void* stream, void* graph_exec) {
 extern "C" int ffn_split_pair(void* stream, const float* src, void* dst, long rows, int C, int ld_src) {
     REQUIRE(src && dst && rows > 0 && C > 0 && C % 4 == 0 && ld_src >= C && ld_src % 4 == 0, "split_pair: bad arguments (C=%d, ld_src=%d)", C, ld_src);
     REQUIRE(aligned16(src) && aligned16(dst), "split_pair: pointers must be 16-byte aligned");
-    static const int wide = [] { const char* e = getenv("FFN_PAIR8"); return e ? atoi(e) : 1; }();
-    if (wide && C % 8 == 0 && ld_src % 4 == 0) LAUNCH(split_pair8_kernel, dim3(grid_for(rows * (C / 8))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, (bf16*)dst, rows, C, ld_src);
+    if (C % 8 == 0) LAUNCH(split_pair8_kernel, dim3(grid_for(rows * (C / 8))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, (bf16*)dst, rows, C, ld_src);
     else LAUNCH(split_pair_kernel, dim3(grid_for(rows * (C / 4))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, (bf16*)dst, rows, C, ld_src);
     return check_launch("split_pair");
 }
@@ -122,8 +121,6 @@ extern "C" int ffn_groupnorm(void* stream, int dtype, const void* x, void* y, co
     REQUIRE(dtype == FFN_F32 || dtype == FFN_BF16, "groupnorm: bad dtype");
     REQUIRE(x && y && gamma && beta && C % G == 0 && (C / G) % 2 == 0, "groupnorm: bad arguments (C=%d, G=%d)", C, G);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const long slice = (long)HW * (C / G);
-    (void)slice;
     const bool fused = ffn_gn_fused(B, HW, C, G) != 0;
     const bool pair = silu & FFN_NORM_OUT_PAIR;
     REQUIRE(!pair || (dtype == FFN_F32 && C % 4 == 0), "groupnorm: pair output needs fp32 input and C %% 4 == 0");
@@ -185,9 +182,8 @@ extern "C" int ffn_gn_stats(void* stream, int dtype, const void* x, const float*
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int nchunk = ffn_gn_nchunk(HW);
     const int ppc = (HW + nchunk - 1) / nchunk;
-    const int epc_ = dtype == FFN_F32 ? 4 : 8;
-    const int cols_ = C / epc_ < 256 ? C / epc_ : 256;
-    const int lds = (256 / cols_ > 0 ? 256 / cols_ : 1) * cols_ * 2 * epc_ * (int)sizeof(float);      // [pixel rows of threads][columns][2 x EPC]
+    const int cols_ = C / epc < 256 ? C / epc : 256;
+    const int lds = (256 / cols_ > 0 ? 256 / cols_ : 1) * cols_ * 2 * epc * (int)sizeof(float);      // [pixel rows of threads][columns][2 x EPC]
     if (dtype == FFN_F32)
         LAUNCH(gn_partial_kernel<float>, dim3(nchunk, B), dim3(256), lds, s, (const float*)x, partial_ws, HW, C, ppc);
     else
@@ -206,8 +202,7 @@ extern "C" int ffn_gn_apply(void* stream, int dtype, const void* x, void* y, con
     const int grid = grid_for(nch);
     if (silu & FFN_NORM_OUT_PAIR) {
         REQUIRE(dtype == FFN_F32, "gn_apply: pair output needs fp32 input");
-        static const int wide = [] { const char* e = getenv("FFN_PAIR8"); return e ? atoi(e) : 1; }();      // 0: the round-5 kernels (8-byte stores, libm SiLU)
-        if (wide && C % 8 == 0) {
+        if (C % 8 == 0) {
             const long n8 = (long)B * HW * (C / 8);
             if (silu & FFN_NORM_SILU) LAUNCH(gn_apply_pair8_kernel<true>, dim3(grid_for(n8)), dim3(256), 0, s, (const float*)x, (bf16*)y, scale, shift, n8, HW, C);
             else LAUNCH(gn_apply_pair8_kernel<false>, dim3(grid_for(n8)), dim3(256), 0, s, (const float*)x, (bf16*)y, scale, shift, n8, HW, C);

@@ -46,14 +46,8 @@
 #include <type_traits>
 #include "igemm.h"
 
-#ifndef PP_PRIO
-#define PP_PRIO 1     // 1: MFMA sections at s_setprio 1 (shipped); 0: no priorities; 2: load sections at s_setprio 1
-#endif
 #ifndef PP_ABL
 #define PP_ABL 0      // timing-only ablation builds of tools/native/pp_bench.hip: 1 = no global loads, 2 = no counted waits, 3 = GEGLU without the GELU, 4 = no epilogue stores (results garbage)
-#endif
-#ifndef PP_TAPINNER
-#define PP_TAPINNER 1     // split-bf16 convolutions: K walk chunk-major (taps innermost); 0 = tap-major (A/B builds of tools/native/x3_bench.hip)
 #endif
 #ifdef PP_STAMP
 // tools/native/x3_bench.hip -DPP_STAMP: shader-clock stamps (s_memtime) of one workgroup's waves at the 8 segment boundaries of 4 consecutive stages,
@@ -64,11 +58,7 @@ __device__ unsigned long long pp_stamp_out[8 * 64];
 #else
 #define PP_STAMP_AT(k_) do {} while (0)
 #endif
-#ifdef PP_NBE
-#define X3_NBE(FN_, NA_) (PP_NBE)
-#else
-#define X3_NBE(FN_, NA_) ((FN_) + 2 - ((FN_) + (NA_) + 1) / 2)      // early W pieces per wave and stage of the split-bf16 core (see its loop)
-#endif
+#define X3_NBE(FN_, NA_) ((FN_) + 2 - ((FN_) + (NA_) + 1) / 2)      // early W pieces per wave and stage of the split-bf16 core (see its loop; the sweep: profiles/r5_x3_early_w_pieces_sweep.txt)
 template <int N>
 __device__ __forceinline__ void pp_wait_vmcnt() {
     if (PP_ABL != 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -205,7 +195,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IgemmParams p, int 
     // find their lines where the previous stage left them.  (Round 2 measured the same walk 5-13 % SLOWER on the bf16 kernel: there the MFMA section
     // was a third as long and the loader's per-stage tap arithmetic was the pole.)  W rows keep their tap-major packing -- only the walk changes:
     // stage kt reads W columns (tap * cpt + chunk) * 64.
-    constexpr bool TAPIN = X3 && AMODE != AMODE_DENSE && PP_TAPINNER;
+    constexpr bool TAPIN = X3 && AMODE != AMODE_DENSE;      // (profiles/r5_x3_conv_tap_major_vs_chunk_major.txt)
     const int ntap = p.conv == 2 ? 4 : 9;
     auto kt_split = [&](int kt, int& tap, int& c) {
         if (TAPIN) {
@@ -331,8 +321,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IgemmParams p, int 
     };
     auto mfma_rows = [&](auto I0) {
         constexpr int i0 = decltype(I0)::value;
-        if (PP_PRIO == 1) __builtin_amdgcn_s_setprio(1);
-        if (PP_PRIO == 2) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(1);      // MFMA sections at priority 1: of a SIMD's two waves the one in its MFMA chain issues first, the other loads beside it
 #pragma unroll
         for (int i = 0; i < FH; ++i)
 #pragma unroll
@@ -341,8 +330,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IgemmParams p, int 
                 else if constexpr (TRANS) DT<T>::mma(fa[i], fb[j], acc[i0 + i][j]);      // C[m = 4g + r][n = l15]
                 else DT<T>::mma(fb[j], fa[i], acc[i0 + i][j]);                      // C[m = l15][n = 4g + r]
             }
-        if (PP_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-        if (PP_PRIO == 2) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(0);
     };
     typedef std::integral_constant<int, 0> I0_t;
     typedef std::integral_constant<int, FH> I4_t;
@@ -722,7 +710,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IgemmParams p, int 
         };
         auto mfma3 = [&](auto I0, int b_) {
             constexpr int i0 = decltype(I0)::value;
-            if (PP_PRIO == 1) __builtin_amdgcn_s_setprio(1);
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int i = 0; i < FH; ++i)
 #pragma unroll
@@ -748,7 +736,7 @@ __global__ __launch_bounds__(512) void igemm_pp_kernel(const IgemmParams p, int 
 #pragma unroll
                     for (int j = 0; j < FN; ++j) mm(fb[j], fa[i], acc[i0 + i][j]);              // A_lo x W_hi
             }
-            if (PP_PRIO == 1) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
         };
         auto read_a_set = [&](int b_, int i0) {                // a_hi (, a_lo) of fragment rows i0 .. i0 + FH - 1
             read_a(b_, a_rd0, i0);

@@ -87,10 +87,7 @@ def _igemm_name(lib, dcode, d):
 # ---------------------------------------------------------------------------------------------------------------
 # weight packing (host side, once at load time)
 # ---------------------------------------------------------------------------------------------------------------
-_GN_CHUNK_MB = float(os.environ.get("FFN_GN_CHUNK_MB", "0"))           # GroupNorm row chunks (MiB of input per chunk; 0 = whole batch at once)
-_GN_RAW = os.environ.get("FFN_GN_RAW", "1") != "0"                     # ResBlock norm1 also writes the pair rows of its input for the 1x1 shortcut GEMM (0: separate ffn_split_pair pass)
-_KV64 = os.environ.get("FFN_KV64", "1") != "0"                         # self-attention K / V^T projections write the pre-split images themselves (0: fp32 + ffn_attn_presplit)
-_ATTN_PRESPLIT = os.environ.get("FFN_ATTN_PRESPLIT", "1") != "0"      # split-bf16 self attention: pre-split K / V^T once per call (0: split inside the kernel's key loop)
+_ATTN_PRESPLIT = True      # not an option: tests clear it to run attn_x3p_kernel (which serves K / V^T of 2 GiB and more and layouts the image path refuses) at small shapes
 
 
 def _mark_x3(t, order=1):
@@ -150,7 +147,7 @@ def pack_conv3x3_n4(w):
 
 
 def conv3x3_n4_eligible(cout, cin):
-    return cout == 4 and cin % 16 == 0 and cin <= 448 and os.environ.get("FFN_CONV_N4", "1") != "0"
+    return cout == 4 and cin % 16 == 0 and cin <= 448
 
 
 def conv3x3_n4(x, w4, bias, B, H, W, Cin):
@@ -564,7 +561,7 @@ def kv_images_ok(Dh, S, Sk, passes=None, nbytes=0):
     attention(kv_images=True)): the library takes the plan's launches on the images (asked with probe descriptors: the kernel choice depends on the
     shapes and on which entries are active, masked or flagged), and the buffers are within the kernels' 32-bit byte offsets (nbytes = the larger of
     the K and V^T buffers)"""
-    if not (_ATTN_PRESPLIT and _KV64 and nbytes < 2 ** 31 - 65536):
+    if not (_ATTN_PRESPLIT and nbytes < 2 ** 31 - 65536):
         return False
     lib = L.load()
     passes = passes or [[AttnEntrySpec(0, 0)]]
@@ -582,7 +579,6 @@ def kv_images_ok(Dh, S, Sk, passes=None, nbytes=0):
     return True
 
 
-_ROWSPLIT = os.environ.get("FFN_ATT_ROWSPLIT", "1") != "0"
 _CUS = {}
 
 
@@ -630,7 +626,7 @@ def attention(q, k, vt, heads, scale, passes=None, *, Sk=None, out=None, w_dev=N
     dcode = L.FFN_BF16X3 if (x3 and q.dtype == torch.float32) else _dt(q)      # split-bf16 arithmetic on fp32 operands
     descs = []
     chunk = L.ATT_MAXB
-    if _ROWSPLIT and Bo > 1 and Dh == 64 and S >= 128 and Sk % 64 == 0 and q.is_cuda:      # the 256-queries-per-workgroup, one-workgroup-per-CU kernels
+    if Bo > 1 and Dh == 64 and S >= 128 and Sk % 64 == 0 and q.is_cuda:      # the 256-queries-per-workgroup, one-workgroup-per-CU kernels
         di = q.device.index if q.device.index is not None else torch.cuda.current_device()
         if di not in _CUS:
             _CUS[di] = torch.cuda.get_device_properties(di).multi_processor_count
@@ -706,12 +702,6 @@ def groupnorm(x, gamma, beta, G, eps, silu=False, out=None, ws=None, pair=False)
     else:
         partial, scale, shift = ws if ws is not None else gn_workspace(B, HW, Cc, x.device)
     fl = (L.NORM_SILU if silu else 0) | (L.NORM_OUT_PAIR if pair else 0)
-    # Row chunks (three-launch form only): statistics and apply of a chunk run back to back, so that the apply pass finds the chunk's input in the
-    # 256 MiB Infinity Cache instead of fetching it from HBM a second time (the three-launch form reads x twice: 12 bytes per element moved for 8).
-    if partial is not None and _GN_CHUNK_MB > 0 and x.is_contiguous() and out.is_contiguous():
-        row_bytes = HW * Cc * x.element_size()
-        nb = max(1, min(B, int(_GN_CHUNK_MB * 2 ** 20) // row_bytes))
-        nb = -(-B // -(-B // nb))                    # equal chunks
     def call():
         rc = 0
         for b0 in range(0, B, nb):
@@ -734,7 +724,7 @@ def groupnorm_pair_raw(x, gamma, beta, G, eps, silu=False, ws=None):
     the second is what split_pair(x) would give, bit for bit.  Shapes the one-launch fused GroupNorm takes (small tensors) keep that kernel + a split_pair pass."""
     lib = L.load()
     B, HW, Cc = x.shape
-    if not _GN_RAW or Cc % 8 != 0 or lib.ffn_gn_fused(1 if _invariant() else B, HW, Cc, G) or not x.is_contiguous():
+    if Cc % 8 != 0 or lib.ffn_gn_fused(1 if _invariant() else B, HW, Cc, G) or not x.is_contiguous():
         return groupnorm(x, gamma, beta, G, eps, silu=silu, pair=True, ws=ws), split_pair(x, Cc)
     assert x.dtype == torch.float32
     y = _mark_pair(torch.empty(B, HW, 2 * Cc, dtype=torch.bfloat16, device=x.device), Cc)

@@ -14,7 +14,6 @@ MI355X-first layout decisions
     and replayed (capture=True) -- ~700 launches become one graph launch.
 """
 import ctypes as CT
-import os
 import weakref
 
 import torch
@@ -22,8 +21,6 @@ import torch
 from . import _lib as L
 from . import ops
 from .config import UNetConfig
-
-_GRAPH_RAW = os.environ.get("FFN_GRAPH_RAW", "1") != "0"
 
 
 class _Res:
@@ -145,7 +142,7 @@ class HipUNet:
                 if rev_attn[i] else None
             blk.up = self._conv(st, f"up_blocks.{i}.upsamplers.0.conv") if i < n - 1 else None
             blk.up2 = None                                  # the same convolution in its sub-pixel form (4/9 of the FLOPs): bf16 and split-bf16 modes
-            if blk.up is not None and (self.dtype == torch.bfloat16 or self.x3) and os.environ.get("FFN_UP2X", "1") != "0":
+            if blk.up is not None and (self.dtype == torch.bfloat16 or self.x3):
                 wu = st[f"up_blocks.{i}.upsamplers.0.conv.weight"].to(self.device)
                 if ops.up2x_eligible(wu.shape[1], wu.shape[0], 192):
                     blk.up2 = ops.pack_conv3x3_up2x(wu, self.dtype, x3=self.x3)
@@ -338,8 +335,8 @@ class HipUNet:
         """replay a captured forward.  Through the C ABI (ffn_graph_launch = hipGraphLaunch on the current stream): a ctypes call releases the GIL,
         torch's CUDAGraph.replay() holds it -- and a launch of the ~380-node graph keeps the host thread for milliseconds on ROCm 7.2 (measured:
         5.2 ms per replay, profiles/r5_host_profile_batch1.txt), which serialised the host threads of the one-image-per-call layout.  The graphs
-        hold no torch RNG state, so the raw launch is the whole of replay().  FFN_GRAPH_RAW=0 keeps torch's replay()."""
-        if _GRAPH_RAW and hasattr(g["graph"], "raw_cuda_graph_exec"):          # (older torch: no raw handle -> torch's replay())
+        hold no torch RNG state, so the raw launch is the whole of replay()."""
+        if hasattr(g["graph"], "raw_cuda_graph_exec"):          # (older torch: no raw handle -> torch's replay())
             ex = g.get("exec")
             if ex is None:
                 ex = g["exec"] = int(g["graph"].raw_cuda_graph_exec())

@@ -338,7 +338,7 @@ def test_groupnorm_pair_raw_against_fp64(gpu, shape, G):
     from freefine_amd import _lib as L
     from freefine_amd import ops
     B, HW, C = shape
-    assert ops._GN_RAW and C % 8 == 0 and not L.load().ffn_gn_fused(B, HW, C, G), "this shape no longer reaches gn_apply_pair8_kernel<., RAW>"
+    assert C % 8 == 0 and not L.load().ffn_gn_fused(B, HW, C, G), "this shape no longer reaches gn_apply_pair8_kernel<., RAW>"
     case = gn_case(B, HW, C, G, "pair")
     x, gamma, beta, ref = case
     xd, gd, bd = x.to(gpu), gamma.to(gpu), beta.to(gpu)
@@ -399,22 +399,6 @@ def test_groupnorm_batch_invariant(gpu, shape, G, mode):
         rows = torch.cat([_gn(gpu, mode, (x[b:b + 1], gamma, beta, None), G, True) for b in range(B)])
     assert torch.equal(_bits(full), _bits(rows))
     check_gn(mode, True, full, case, G, "batch_invariant")
-
-
-@pytest.mark.parametrize("mode", ["f32", "pair"])
-def test_groupnorm_row_chunks(gpu, monkeypatch, mode):
-    """FFN_GN_CHUNK_MB: statistics + apply per chunk of rows; 5 rows as 2 + 2 + 1 and as single rows, bit-identical to the whole batch at once"""
-    from freefine_amd import _lib as L
-    from freefine_amd import ops
-    (B, HW, C), G = CHUNK_CASE
-    assert not L.load().ffn_gn_fused(1, HW, C, G) and HW * C * 4 == 512 * 1024
-    case = gn_case(B, HW, C, G, mode)
-    monkeypatch.setattr(ops, "_GN_CHUNK_MB", 0.0)
-    whole = _gn(gpu, mode, case, G, True)
-    check_gn(mode, True, whole, case, G, "unchunked")
-    for mb in (1.0, 0.5):                       # 2 rows per chunk -> 3 chunks of (2, 2, 1); 1 row per chunk
-        monkeypatch.setattr(ops, "_GN_CHUNK_MB", mb)
-        assert torch.equal(_bits(_gn(gpu, mode, case, G, True)), _bits(whole)), mb
 
 
 def test_groupnorm_refusals_write_nothing(gpu):
