@@ -13,6 +13,8 @@ comparable with the CPU oracle on identical seeds; set `noise_device="cuda"` to 
 import os
 import random
 import sys
+from collections import namedtuple
+from contextlib import contextmanager
 from copy import deepcopy
 
 import numpy as np
@@ -50,6 +52,19 @@ def images_to_u8(images):
     768 KB-per-image copy to the host instead of K permuted 3 MB ones."""
     u8 = (images.detach().float().permute(0, 2, 3, 1) * 255).to(torch.uint8).contiguous().cpu().numpy()
     return [u8[k] for k in range(u8.shape[0])]
+
+
+# How the three guided-sampling tasks lay out the one loop (FreeFinePipeline._guided_loop).  An image owns n latent rows: row 0 is the stream
+# being sampled, rows 1.. are its references.
+#   pair        n = 2; the CFG batch is the pair twice, de-duplicated by _cfg_row_map; cfg_masked / ctrl_step get both rows (ctrl_step masks only
+#               row 0).  Otherwise n = 1 + R, the UNet batch is rows [0 .. R, 0] against every text row and only row 0 is stepped.
+#   ref_next    loop step j takes rows 1.. of refer[j + 1]; otherwise the whole refer[j] (an inversion of one row per image)
+#   replay      how the reference rows re-enter from the inversion's record: "join" (reference-stream replay), "kv" (stored K / V) or None
+#   record_all  a trajectory entry is all n rows, aliasing the live latents; otherwise row 0
+GuidedLayout = namedtuple("GuidedLayout", "pair ref_next replay record_all")
+EDIT = GuidedLayout(pair=True, ref_next=True, replay="join", record_all=True)
+BACKGROUND = GuidedLayout(pair=True, ref_next=False, replay=None, record_all=False)
+COMPOSE = GuidedLayout(pair=False, ref_next=True, replay="kv", record_all=False)
 
 
 class FreeFinePipeline:
@@ -485,13 +500,6 @@ class FreeFinePipeline:
             return None
         return cache
 
-    @staticmethod
-    def _replay_kv_arg(cache, slot, R, P):
-        """HipUNet.forward's `reuse` argument of a composition step: latent rows per image [edit_u, ref_1 .. ref_R, edit_c], text rows per image
-        [""] * (1 + R) + the P prompts; the edit rows read text row 0 and the prompt rows"""
-        return dict(mode="replay_kv", kv_from=cache["kv_from"], ref=(False,) + (True,) * R + (False,), kv=slot,
-                    text_sel=[0] + list(range(1 + R, 1 + R + P)))
-
     def _cfg_row_map(self, text, n):
         """CFG batch rows are (latent i mod n, text row i).  Rows whose text embeddings coincide are the same UNet input, bit
         for bit (edit / bg-gen: the reference stream with prompt "" appears twice; with an empty edit prompt so does the edit
@@ -509,9 +517,53 @@ class FreeFinePipeline:
             return None, None, None
         return row_map, [li for li, _ in phys], [ti for _, ti in phys]
 
-    def _configure_method(self, method_type, share_attn=True):
+    @staticmethod
+    def _merge_row_maps(maps):
+        """the `_cfg_row_map` results of K images -> the one (row_map, latent rows, text rows) of the image-major batch: theirs where they
+        all agree, else (images disagree on which CFG rows coincide, or de-duplication is off) all four rows"""
+        if all(m[0] is not None and m[0] == maps[0][0] for m in maps):
+            return maps[0]
+        return None, [0, 1, 0, 1], [0, 1, 2, 3]
+
+    def _guided_rows(self, lay, texts, n):
+        """what a guided step feeds to the UNet for the K = len(texts) images of n latent rows each: (row_map, the latent rows of the whole
+        batch, image-major, and per image: the text rows, which of its latent rows are reference rows, the text rows those run against)"""
+        if lay.pair:
+            row_map, lat_rows, txt_rows = self._merge_row_maps([self._cfg_row_map(t, 2) for t in texts])
+        else:                                                 # [edit_u, ref_1 .. ref_R, edit_c] against every text row
+            row_map, lat_rows, txt_rows = None, list(range(n)) + [0], list(range(texts[0].shape[0]))
+        ref_flags = tuple(r > 0 for r in lat_rows)
+        return row_map, [n * k + r for k in range(len(texts)) for r in lat_rows], txt_rows, ref_flags, [txt_rows[p] for p, f in enumerate(ref_flags) if f]
+
+    def _reuse_arg(self, lay, cache, ref_flags, n_txt, num_steps, i):
+        """HipUNet.forward's `reuse` argument of scheduler step i = start_step + j, the loop's step j (None without a record): the reference
+        rows re-enter from what inversion step n_act - j - 1 = num_steps - i - 1 recorded for the same latent, timestep and prompt.
+        n_txt: text rows per image"""
+        if cache is None:
+            return None
+        slot = cache["slots"][num_steps - i - 1]
+        nr = sum(ref_flags)
+        if lay.replay == "kv":
+            # text rows per image: [""] * (1 + R) + the prompts; the edit rows read text row 0 and the prompt rows
+            return dict(mode="replay_kv", kv_from=cache["kv_from"], ref=ref_flags, kv=slot, text_sel=[0] + list(range(1 + nr, n_txt)))
+        # every step but the last overwrites the reference latent before anything reads it: the reference rows' eps is dead there and
+        # their tail behind the last K / V projection is not run
+        return dict(mode="replay", join=cache["join"], ref=ref_flags, state=[s.repeat_interleave(nr, 0) for s in slot] if nr > 1 else slot,
+                    drop_tail=self.drop_ref_tail and i + 1 < num_steps)
+
+    def _step_method(self, ctrls, method_type, i, start_step, end_step, num_steps, end_scale):
+        """the method's schedule at scheduler step i (model.py:587-591)"""
+        for c in ctrls:
+            if method_type == "tca":
+                c.context_guidance = self.linear_param(i, start_step, end_step, num_steps, end_scale=end_scale)
+            elif method_type == "mmsa_es" and i >= end_step:
+                c.use_tca = False
+
+    def _configure_method(self, c, method_type, share_attn, local_edit, prompt_length=None):
         self.method_type = method_type
-        c = self.controller
+        c.local_edit = local_edit
+        if prompt_length is not None:
+            c.prompt_length = prompt_length
         if share_attn:
             if method_type == "tca":
                 c.use_tca, c.layer_idx, c.method = True, list(range(10, 16)), "tca"
@@ -525,15 +577,65 @@ class FreeFinePipeline:
         return mask.detach().cpu().float().reshape(-1).to(self.device)
 
     @torch.no_grad()
+    def _guided_loop(self, lay, ctrls, texts, cfg_f, var_masks, noises, latents, refer, traj, method_type, num_steps, start_step, end_step,
+                     end_scale, guidance_scale, eta):
+        """HOT LOOP 2 (model.py:301-435, 476-622, 656-812) for K = len(texts) images as one image-major batch, laid out by `lay` (EDIT,
+        BACKGROUND or COMPOSE above).  Per image: its controller, its logical text rows, cfg mask vector (or None), variance mask and
+        pre-drawn noise stack (or None).  `latents` [K n, 4, h, w] holds every image's n rows and is WRITTEN: its reference rows are
+        overwritten in place.  `traj`: None, or K lists holding entry 0 that receive one entry per step.  Returns (final latents, traj)."""
+        K, n, shape1 = len(texts), latents.shape[0] // len(texts), tuple(latents.shape[1:])
+        m = n if lay.pair else 1                              # rows per image that cfg_masked / ctrl_step see
+        row_map, lat_rows, txt_rows, ref_flags, ref_txt = self._guided_rows(lay, texts, n)
+        text_phys = torch.cat([t[txt_rows] for t in texts], dim=0).contiguous()
+        lat_idx = torch.tensor(lat_rows, device=self.device)
+        self.scheduler.set_timesteps(num_steps)
+        cache = None
+        if lay.replay:
+            cache = self._take_ref_cache(refer, num_steps - start_step, texts[0], ref_txt, kv=lay.replay == "kv")
+            if cache is not None and any(not torch.equal(t[r], cache["text"][0]) for t in texts for r in ref_txt):
+                cache = None
+        for i, t in enumerate(self.scheduler.timesteps):
+            if i < start_step:
+                continue
+            j = i - start_step
+            lat_v = latents.view(K, n, *shape1)
+            # the reference rows of this step (model.py:582-586; removal: the aligned latent, :756)
+            lat_v[:, 1:] = refer[j + 1].view(K, n, *shape1)[:, 1:] if lay.ref_next else refer[j].view(K, 1, *shape1)
+            self._step_method(ctrls, method_type, i, start_step, end_step, num_steps, end_scale)
+            reuse = self._reuse_arg(lay, cache, ref_flags, texts[0].shape[0], num_steps, i)
+            eps = self.unet(latents.index_select(0, lat_idx), t, encoder_hidden_states=text_phys, row_map=row_map, reuse=reuse)
+            eps = eps.view(K, -1, *shape1)
+            outs = []
+            for k in range(K):
+                e = ops.cfg_masked(eps[k, :m].contiguous(), eps[k, -m:].contiguous(), cfg_f[k], guidance_scale)
+                outs.append(self.ctrl_step(e, t, lat_v[k, :m], var_masks[k], eta=eta, noise=None if noises[k] is None else noises[k][j])[0])
+                if m < n:
+                    outs.append(lat_v[k, m:])
+            latents = outs[0] if len(outs) == 1 else torch.cat(outs)
+            if traj is not None:
+                # like the reference's latents_list (model.py:585-616) an entry of all rows ALIASES the live latents: its reference rows
+                # are overwritten in place by the next step
+                for k in range(K):
+                    traj[k].append(latents[n * k:n * (k + 1)] if lay.record_all else latents[n * k])
+        return latents, traj
+
+    def _noise_per_case(self, seeds, n, shape, eta):
+        """the loop's noise of every case of a batch, each from its own generator seeded like the single call's, drawn in case order"""
+        noises = []
+        for sd in seeds:
+            self._gen = torch.Generator().manual_seed(sd)
+            noises.append(self._predraw_noise(n, shape, eta))
+        return noises
+
+    @torch.no_grad()
     def forward_sampling(self, prompt, prompt_embeds=None, refer_latents=None, batch_size=1, end_step=None, height=512, width=512,
                          num_inference_steps=50, num_actual_inference_steps=None, guidance_scale=7.5, latents=None,
                          unconditioning=None, neg_prompt=None, return_intermediates=False, eta=0.0, end_scale=0.5,
                          local_var_reg=None, completion_mask_cfg=None, local_edit_text=True, share_attn=True, method_type=None,
                          verbose=False, local_perturbation=True, **kwds):
-        """model.py:476-622 (HOT LOOP 2, edit)"""
+        """model.py:476-622 (HOT LOOP 2, edit): `latents` = the pair (edit, reference)"""
         assert guidance_scale > 1.0, "USING THIS MODULE CFG Must > 1.0"
-        self._configure_method(method_type, share_attn)
-        self.controller.local_edit = local_edit_text
+        self._configure_method(self.controller, method_type, share_attn, local_edit_text)
         if prompt_embeds is None:
             if isinstance(prompt, list):
                 batch_size = len(prompt)
@@ -545,50 +647,14 @@ class FreeFinePipeline:
         if latents is None:
             latents = torch.randn((batch_size, self.unet.in_channels, height // 8, width // 8)).to(self.device)
         text = torch.cat([self._encode_text([neg_prompt or ""] * batch_size), text], dim=0).contiguous()
-        self.scheduler.set_timesteps(num_inference_steps)
-        latents_list = [latents]
-        start_step = num_inference_steps - num_actual_inference_steps
-        cfg_f = self._mask_f(completion_mask_cfg) if local_edit_text else None
-        row_map, lat_rows, txt_rows = self._cfg_row_map(text, 2)
-        text_phys = text[txt_rows].contiguous() if row_map is not None else text
-        lat_idx = torch.tensor(lat_rows, device=self.device) if row_map is not None else None
-        noises = self._predraw_noise(num_inference_steps - start_step, (2,) + tuple(latents.shape[1:]), eta)
-        var_mask = local_var_reg if local_perturbation else torch.ones_like(local_var_reg)
-        # reference-stream reuse: physical rows holding the reference latent (row 1 of the pair) re-enter from the inversion's record
-        n_act = num_inference_steps - start_step
-        ref_flags = tuple(r == 1 for r in lat_rows) if row_map is not None else (False, True, False, True)
-        ref_txt = [txt_rows[p] for p, f in enumerate(ref_flags) if f] if row_map is not None else [1, 3]
-        cache = self._take_ref_cache(refer_latents, n_act, text, ref_txt) if batch_size == 2 else None
-        for i, t in enumerate(self.scheduler.timesteps):
-            if i < start_step:
-                continue
-            ref_latent = refer_latents[i - start_step + 1][1]
-            if latents.shape[0] > 1:
-                latents[1:] = ref_latent
-            else:
-                latents = torch.cat([latents, ref_latent[None] if ref_latent.ndim == 3 else ref_latent])
-            if method_type == "tca":
-                self.controller.context_guidance = self.linear_param(i, start_step, end_step, num_inference_steps, end_scale=end_scale)
-            elif method_type == "mmsa_es" and i >= end_step:
-                self.controller.use_tca = False
-            reuse = None
-            if cache is not None:
-                slot = cache["slots"][n_act - (i - start_step) - 1]
-                nr = sum(ref_flags)
-                # every step but the last overwrites the reference latent before anything reads it (`latents[1:] = ref_latent` above):
-                # the reference rows' eps is dead there and their tail behind the last K / V projection is not run
-                reuse = dict(mode="replay", join=cache["join"], ref=ref_flags, state=[s.repeat_interleave(nr, 0) for s in slot] if nr > 1 else slot,
-                             drop_tail=self.drop_ref_tail and i + 1 < len(self.scheduler.timesteps))
-            if row_map is None:
-                noise_pred = self.unet(torch.cat([latents] * 2), t, encoder_hidden_states=text, reuse=reuse)
-            else:
-                noise_pred = self.unet(latents.index_select(0, lat_idx), t, encoder_hidden_states=text_phys, row_map=row_map, reuse=reuse)
-            eu, ec = noise_pred.chunk(2, dim=0)
-            noise_pred = ops.cfg_masked(eu.contiguous(), ec.contiguous(), cfg_f, guidance_scale)
-            latents = self.ctrl_step(noise_pred, t, latents, var_mask, eta=eta, noise=None if noises is None else noises[i - start_step])[0]
-            latents_list.append(latents)
+        noises = self._predraw_noise(num_actual_inference_steps, (2,) + tuple(latents.shape[1:]), eta)
+        latents, traj = self._guided_loop(
+            EDIT, [self.controller], [text], [self._mask_f(completion_mask_cfg) if local_edit_text else None],
+            [local_var_reg if local_perturbation else torch.ones_like(local_var_reg)], [noises], latents, refer_latents,
+            [[latents]] if return_intermediates else None, method_type, num_inference_steps, num_inference_steps - num_actual_inference_steps,
+            end_step, end_scale, guidance_scale, eta)
         image = self.latent2image(latents, return_type="pt")
-        return (image, latents_list) if return_intermediates else (image, None)
+        return (image, traj[0]) if return_intermediates else (image, None)
 
     @torch.no_grad()
     def forward_sampling_background_gen(self, prompt, batch_size=1, end_step=None, height=512, width=512, num_inference_steps=50,
@@ -597,10 +663,10 @@ class FreeFinePipeline:
                                         local_var_reg=None, local_cfg_reg=None, local_text_edit=True, share_attn=True,
                                         method_type="tca", verbose=False, local_perturbation=True, end_scale=0.5,
                                         latent_blended=True, blend_range=(0, 40), **kwds):
-        """model.py:656-812 (removal / background generation); latent_blended / blend_range accepted but inert (:805-806)"""
+        """model.py:656-812 (removal / background generation): row 0 of `latents` is the generated stream, the loop pairs it with the
+        inversion's latent of the step; latent_blended / blend_range accepted but inert (:805-806)"""
         assert guidance_scale > 1.0, "USING THIS MODULE CFG Must > 1.0"
-        self._configure_method(method_type, share_attn)
-        self.controller.local_edit = local_text_edit
+        self._configure_method(self.controller, method_type, share_attn, local_text_edit)
         if isinstance(prompt, list):
             batch_size = len(prompt)
         elif isinstance(prompt, str) and batch_size > 1:
@@ -609,36 +675,19 @@ class FreeFinePipeline:
         if latents is None:
             latents = torch.randn((batch_size, self.unet.in_channels, height // 8, width // 8)).to(self.device)
         text = torch.cat([self._encode_text([neg_prompt or ""] * batch_size), text], dim=0).contiguous()
-        self.scheduler.set_timesteps(num_inference_steps)
-        latents_list = [latents]
-        start_step = num_inference_steps - num_actual_inference_steps
-        cfg_f = self._mask_f(local_cfg_reg) if local_text_edit else None
-        row_map, lat_rows, txt_rows = self._cfg_row_map(text, 2)
-        text_phys = text[txt_rows].contiguous() if row_map is not None else text
-        lat_idx = torch.tensor(lat_rows, device=self.device) if row_map is not None else None
-        noises = self._predraw_noise(num_inference_steps - start_step, (2,) + tuple(latents.shape[1:]), eta)
-        var_mask = local_var_reg if local_perturbation else torch.ones_like(local_var_reg)
-        for i, t in enumerate(self.scheduler.timesteps):
-            if i < start_step:
-                continue
-            ref_latent = refer_latents[i - start_step]
-            if latents.shape[0] > 1:
-                latents = latents[0].unsqueeze(0)
-            latents = torch.cat([latents, ref_latent], dim=0)
-            if method_type == "tca":
-                self.controller.context_guidance = self.linear_param(i, start_step, end_step, num_inference_steps, end_scale=end_scale)
-            elif method_type == "mmsa_es" and i >= end_step:
-                self.controller.use_tca = False
-            if row_map is None:
-                noise_pred = self.unet(torch.cat([latents] * 2), t, encoder_hidden_states=text)
-            else:
-                noise_pred = self.unet(latents.index_select(0, lat_idx), t, encoder_hidden_states=text_phys, row_map=row_map)
-            eu, ec = noise_pred.chunk(2, dim=0)
-            noise_pred = ops.cfg_masked(eu.contiguous(), ec.contiguous(), cfg_f, guidance_scale)
-            latents = self.ctrl_step(noise_pred, t, latents, var_mask, eta=eta, noise=None if noises is None else noises[i - start_step])[0]
-            latents_list.append(latents[0])
-        image = self.latent2image(latents, return_type="pt")
-        return (image, latents_list) if return_intermediates else (image, None)
+        noises = self._predraw_noise(num_actual_inference_steps, (2,) + tuple(latents.shape[1:]), eta)
+        out, traj = self._guided_loop(
+            BACKGROUND, [self.controller], [text], [self._mask_f(local_cfg_reg) if local_text_edit else None],
+            [local_var_reg if local_perturbation else torch.ones_like(local_var_reg)], [noises], self._with_ref_rows(latents[:1]), refer_latents,
+            [[latents]] if return_intermediates else None, method_type, num_inference_steps, num_inference_steps - num_actual_inference_steps,
+            end_step, end_scale, guidance_scale, eta)
+        image = self.latent2image(out, return_type="pt")
+        return (image, traj[0]) if return_intermediates else (image, None)
+
+    @staticmethod
+    def _with_ref_rows(init):
+        """[K,4,h,w] initial latents of K removals -> the loop's [2K,4,h,w] rows (generated_i, reference_i); the loop fills the reference rows"""
+        return torch.stack([init, torch.zeros_like(init)], dim=1).flatten(0, 1)
 
     @torch.no_grad()
     def forward_sampling_compose(self, prompt, prompt_embeds=None, refer_latents=None, batch_size=1, end_step=None, height=512,
@@ -646,48 +695,24 @@ class FreeFinePipeline:
                                  latents=None, unconditioning=None, neg_prompt=None, return_intermediates=False, eta=0.0,
                                  end_scale=0.5, local_var_reg=None, local_edit_text=True, cfg_masks_tensor=None, share_attn=True,
                                  method_type=None, verbose=False, local_perturbation=True, **kwds):
-        """model.py:301-435 (cross-image composition / appearance transfer): UNet batch [edit, ref_1..ref_R, edit]"""
+        """model.py:301-435 (cross-image composition / appearance transfer): `latents` = [edit, ref_1..ref_R], UNet batch [edit, ref_1..ref_R, edit]"""
         assert guidance_scale > 1.0, "USING THIS MODULE CFG Must > 1.0"
-        self._configure_method(method_type, share_attn)
-        self.controller.local_edit = local_edit_text
         prompt.append("")                                      # the reference mutates the caller's list too (model.py:352)
-        self.controller.prompt_length = len(prompt)
+        self._configure_method(self.controller, method_type, share_attn, local_edit_text, prompt_length=len(prompt))
         text = self._encode_text(prompt)
         if latents is None:
             latents = torch.randn((batch_size, self.unet.in_channels, height // 8, width // 8)).to(self.device)
         text = torch.cat([self._encode_text([neg_prompt or ""] * batch_size), text], dim=0).contiguous()
-        self.scheduler.set_timesteps(num_inference_steps)
-        latents_list = [latents]
-        start_step = num_inference_steps - num_actual_inference_steps
-        cfg_f = self._mask_f(cfg_masks_tensor) if local_edit_text else None
-        noises = self._predraw_noise(num_inference_steps - start_step, (1,) + tuple(latents.shape[1:]), eta)
-        var_mask = local_var_reg if local_perturbation else torch.ones_like(local_var_reg)
+        noises = self._predraw_noise(num_actual_inference_steps, (1,) + tuple(latents.shape[1:]), eta)
         # stored reference K / V: the R reference rows (latent, timestep, "") are the very rows the inversion evaluated, and this hook never
         # modulates them -- only the two edit rows run; the modulated blocks read the references' K / V from the inversion's record
-        n_act = num_inference_steps - start_step
-        R, P = refer_latents[0].shape[0] - 1, len(prompt)
-        cache = self._take_ref_cache(refer_latents, n_act, text, list(range(1, 1 + R)), kv=True) if batch_size == 1 + R and batch_size > 1 else None
-        for i, t in enumerate(self.scheduler.timesteps):
-            if i < start_step:
-                continue
-            ref_latent = refer_latents[i - start_step + 1][1:]
-            if latents.shape[0] > 1:
-                latents[1:] = ref_latent
-            else:
-                latents = torch.cat([latents, ref_latent])
-            if method_type == "tca":
-                self.controller.context_guidance = self.linear_param(i, start_step, end_step, num_inference_steps, end_scale=end_scale)
-            elif method_type == "mmsa_es" and i >= end_step:
-                self.controller.use_tca = False
-            reuse = None if cache is None else self._replay_kv_arg(cache, cache["slots"][n_act - (i - start_step) - 1], R, P)
-            noise_pred = self.unet(torch.cat([latents, latents[0][None]]), t, encoder_hidden_states=text, reuse=reuse)
-            eu, ec = noise_pred[0][None].contiguous(), noise_pred[-1][None].contiguous()
-            noise_pred = ops.cfg_masked(eu, ec, cfg_f, guidance_scale)
-            latents = self.ctrl_step(noise_pred, t, latents[0][None].contiguous(), var_mask, eta=eta,
-                                     noise=None if noises is None else noises[i - start_step])[0]
-            latents_list.append(latents[0])
-        image = self.latent2image(latents, return_type="pt")[0]
-        return (image, latents_list) if return_intermediates else (image, None)
+        out, traj = self._guided_loop(
+            COMPOSE, [self.controller], [text], [self._mask_f(cfg_masks_tensor) if local_edit_text else None],
+            [local_var_reg if local_perturbation else torch.ones_like(local_var_reg)], [noises], latents, refer_latents,
+            [[latents]] if return_intermediates else None, method_type, num_inference_steps, num_inference_steps - num_actual_inference_steps,
+            end_step, end_scale, guidance_scale, eta)
+        image = self.latent2image(out[:1], return_type="pt")[0]
+        return (image, traj[0]) if return_intermediates else (image, None)
 
     # ------------------------------------------------------------------------------------------------------------
     # masks (model.py:927-934, 1431-1639) -- uint8 tensors on the host, arithmetic exactly as the reference
@@ -826,23 +851,44 @@ class FreeFinePipeline:
         self.controller.reset()
         return latents_list
 
+    # per-case set-up: the masks and the controller state of one image, shared by the single calls and the image-batched ones
+    def _setup_edit(self, c, hw, init, shifted_mask, ori_mask, draw_mask, method_type, share_attn, **mask_kw):
+        """model.py:1640-1692 -> (completion mask of the CFG, variance mask), both at latent size"""
+        fg, shifted_t, ori_t, cfg_m, var_m = self.prepare_various_mask(shifted_mask, ori_mask, draw_mask, hw[0], hw[1], init, **mask_kw)
+        cfg_m = self._nearest(cfg_m, (init.shape[2], init.shape[3]))
+        c.fg_retain_mask, c.fg_retain_mask_st2, c.fg_ref_mask, c.local_edit_region = fg, shifted_t, ori_t, fg
+        c.reset()
+        c.log_mask = False
+        # NB the caller's `local_text_edit` is forwarded under the wrong keyword by the reference (blending=, model.py:1692), so the loop's
+        # local_edit_text stays True whatever the caller passed; kept.
+        self._configure_method(c, method_type, share_attn, True)
+        return cfg_m, var_m
+
+    def _setup_background(self, c, hw, init, ori_mask, method_type, share_attn, local_text_edit):
+        """model.py:1088-1118 -> the hole mask at latent size (CFG and variance mask alike)"""
+        mask_t, var_m = self.prepare_mask_bggen(ori_mask, hw[0], hw[1], init)
+        c.fg_retain_mask, c.local_edit_region = mask_t, mask_t
+        c.reset()
+        self._configure_method(c, method_type, share_attn, local_text_edit)
+        return var_m
+
+    def _setup_compose(self, c, hw, init, ori_mask_lists, tgt_mask_lists, draw_mask, n_prompts, method_type, share_attn, local_text_edit, **mask_kw):
+        """model.py:1051-1086 -> (variance mask, CFG mask) at latent size; the loop's prompt list is the caller's n_prompts plus the empty one"""
+        tgt_t, ori_t, lp, cfg_m = self.prepare_composition_masks(ori_mask_lists, tgt_mask_lists, hw[0], hw[1], init, draw_mask=draw_mask, **mask_kw)
+        c.src_masks, c.tgt_masks = ori_t, tgt_t
+        c.reset()
+        self._configure_method(c, method_type, share_attn, local_text_edit, prompt_length=n_prompts + 1)
+        return lp, cfg_m
+
     def Details_Preserving_regeneration(self, source_image, inverted_latents, edit_prompt, shifted_mask, ori_mask, draw_mask,
                                         num_steps=100, start_step=30, end_step=10, eta=1, guidance_scale=7.5, share_attn=True,
                                         method_type="tca", verbose=False, local_text_edit=True, local_perturbation=True,
                                         return_intermediates=False, use_auto_draw=False, cons_area=None, use_share_attention=False,
                                         reduce_inp_artifacts=False, end_scale=0.5):
         init_code = deepcopy(inverted_latents[-1])
-        full_h, full_w = source_image.shape[:2]
-        fg, shifted_t, ori_t, cfg_m, var_m = self.prepare_various_mask(shifted_mask, ori_mask, draw_mask, full_h, full_w, init_code,
-                                                                       verbose=verbose, use_auto_draw=use_auto_draw, cons_area=cons_area,
-                                                                       reduce_inp_artifacts=reduce_inp_artifacts)
-        cfg_m = self._nearest(cfg_m, (init_code.shape[2], init_code.shape[3]))
         c = self.controller
-        c.fg_retain_mask, c.fg_retain_mask_st2, c.fg_ref_mask, c.local_edit_region = fg, shifted_t, ori_t, fg
-        c.reset()
-        c.log_mask = False
-        # NB `local_text_edit` is forwarded under the wrong keyword by the reference (blending=, model.py:1692), so the loop's
-        # local_edit_text stays True whatever the caller passed; kept.
+        cfg_m, var_m = self._setup_edit(c, source_image.shape[:2], init_code, shifted_mask, ori_mask, draw_mask, method_type, share_attn,
+                                        use_auto_draw=use_auto_draw, cons_area=cons_area, reduce_inp_artifacts=reduce_inp_artifacts)
         gen_images, intermediates = self.forward_sampling(
             prompt=[edit_prompt, ""], refer_latents=inverted_latents[::-1], end_step=end_step, batch_size=2, latents=init_code,
             guidance_scale=guidance_scale, num_inference_steps=num_steps, num_actual_inference_steps=num_steps - start_step, eta=eta,
@@ -859,13 +905,10 @@ class FreeFinePipeline:
                                                 verbose=False, local_text_edit=True, local_perturbation=True, return_intermediates=False,
                                                 use_share_attention=False, dil_factor=15, end_scale=0.5):
         init_code = deepcopy(inverted_latents[-1])
-        full_h, full_w = source_image.shape[:2]
-        tgt_t, ori_t, lp, cfg_m = self.prepare_composition_masks(ori_mask_lists, tgt_mask_lists, full_h, full_w, init_code,
-                                                                 dil_completion=dil_completion, dil_factor=dil_factor, draw_mask=draw_mask,
-                                                                 appearance_transfer=appearance_transfer)
         c = self.controller
-        c.src_masks, c.tgt_masks = ori_t, tgt_t
-        c.reset()
+        lp, cfg_m = self._setup_compose(c, source_image.shape[:2], init_code, ori_mask_lists, tgt_mask_lists, draw_mask, len(edit_prompt_list),
+                                        method_type, share_attn, local_text_edit, dil_completion=dil_completion, dil_factor=dil_factor,
+                                        appearance_transfer=appearance_transfer)
         img, intermediates = self.forward_sampling_compose(
             prompt=edit_prompt_list, refer_latents=inverted_latents[::-1], end_step=end_step, batch_size=init_code.shape[0],
             latents=init_code, guidance_scale=guidance_scale, num_inference_steps=num_steps,
@@ -880,11 +923,8 @@ class FreeFinePipeline:
                                                    local_perturbation=True, end_scale=0.5, return_intermediates=False, share_attn=True,
                                                    method_type="tca", latent_blended=True, blend_range=(0, 40)):
         init_code = deepcopy(inverted_latents[-1])
-        full_h, full_w = ori_img.shape[:2]
-        mask_t, var_m = self.prepare_mask_bggen(ori_mask, full_h, full_w, init_code)
         c = self.controller
-        c.fg_retain_mask, c.local_edit_region = mask_t, mask_t
-        c.reset()
+        var_m = self._setup_background(c, ori_img.shape[:2], init_code, ori_mask, method_type, share_attn, local_text_edit)
         gen_images, intermediates = self.forward_sampling_background_gen(
             prompt=[edit_prompt, ""], end_step=end_step, batch_size=2, refer_latents=inverted_latents[::-1], latents=init_code,
             guidance_scale=guidance_scale, num_inference_steps=num_steps, num_actual_inference_steps=num_steps - start_step, eta=eta,
@@ -934,6 +974,28 @@ class FreeFinePipeline:
             self._batch_ctrls[K] = ctrls
         return ctrls
 
+    @contextmanager
+    def _batched_controllers(self, K):
+        """K controllers on the UNet for an image-batched call (the registered one alone for K = 1; no graph flush: graphs are keyed by the
+        plans); the registered controller is put back on the way out"""
+        single = self.controller
+        ctrls = self._controllers_for_batch(K)
+        self.unet.controller = ctrls if K > 1 else single
+        try:
+            yield ctrls
+        finally:
+            self.unet.controller = single
+
+    def _invert_batch(self, ctrls, source, num_step, start_step, **record):
+        """the inversion all K cases share (model.py:1341-1388 + 816-925) -> (last latents, `refer_latents` of the guided loop)"""
+        for c in ctrls:
+            c.reset()
+        _, inverted = self.invert(source, "", guidance_scale=1.0, num_inference_steps=num_step, num_actual_inference_steps=num_step - start_step,
+                                  return_intermediates=True, **record)
+        for c in ctrls:
+            c.reset()
+        return inverted[-1], inverted[::-1]
+
     @torch.no_grad()
     def FreeFine_generation_batch(self, cases, guidance_scale, eta, end_step=10, num_step=50, start_step=25, share_attn=True,
                                   method_type="tca", local_perturbation=True, verbose=True, return_ori=False, seeds=42,
@@ -950,118 +1012,36 @@ class FreeFinePipeline:
         assert guidance_scale > 1.0, "USING THIS MODULE CFG Must > 1.0"
         K = len(cases)
         seeds = [seeds] * K if isinstance(seeds, int) else list(seeds)
-        single, hook = self.controller, self.unet.hook
-        ctrls = self._controllers_for_batch(K)
-        self.unet.hook, self.unet.controller = hook, (ctrls if K > 1 else single)      # no graph flush: graphs are keyed by the plans
-        try:
-            return self._generation_batch(cases, ctrls, seeds, guidance_scale, eta, end_step, num_step, start_step, share_attn,
-                                          method_type, local_perturbation, return_ori, return_intermediates, end_scale)
-        finally:
-            self.controller = single
-            self.unet.controller = single
-
-    def _generation_batch(self, cases, ctrls, seeds, guidance_scale, eta, end_step, num_step, start_step, share_attn, method_type,
-                          local_perturbation, return_ori, return_intermediates, end_scale):
-        K = len(cases)
-        seed_everything(seeds[0])
-        gens = [torch.Generator().manual_seed(s) for s in seeds]
         red = self.mask_reduce_dim
-        # ---- inversion of [coarse_i, ori_i] for every image: one 2K-row batch (model.py:1341-1388 + 816-925)
-        source = torch.from_numpy(np.concatenate([np.stack([c["coarse_input"], self.resize_img(c["ori_img"], size=self._work_size(c["coarse_input"]))])
-                                                  for c in cases]))
-        for c in ctrls:
-            c.reset()
-        _, inverted = self.invert(source, "", guidance_scale=1.0, num_inference_steps=num_step,
-                                  num_actual_inference_steps=num_step - start_step, return_intermediates=True,
-                                  record_rows=[2 * i + 1 for i in range(K)])
-        for c in ctrls:
-            c.reset()
-        # ---- per-image masks, controller state, text rows (model.py:1012-1118, 476-526)
-        init = inverted[-1]
-        refer = inverted[::-1]
-        cfg_f, var_masks, texts = [], [], []
-        for case, c in zip(cases, ctrls):
-            full_h, full_w = case["coarse_input"].shape[:2]
-            draw = case.get("draw_mask")
-            fg, shifted_t, ori_t, cfg_m, var_m = self.prepare_various_mask(
-                red(case["target_mask"]), red(case["ori_mask"]), None if draw is None else red(draw), full_h, full_w, init,
-                use_auto_draw=case.get("use_auto_draw", False), cons_area=case.get("cons_area"),
-                reduce_inp_artifacts=case.get("reduce_inp_artifacts", False))
-            cfg_m = self._nearest(cfg_m, (init.shape[2], init.shape[3]))
-            c.fg_retain_mask, c.fg_retain_mask_st2, c.fg_ref_mask, c.local_edit_region = fg, shifted_t, ori_t, fg
-            c.reset()
-            c.log_mask = False
-            self.controller = c
-            self._configure_method(method_type, share_attn)
-            c.local_edit = True                               # see Details_Preserving_regeneration: the reference never turns it off
-            cfg_f.append(self._mask_f(cfg_m))
-            var_masks.append(var_m if local_perturbation else torch.ones_like(var_m))
-            texts.append(torch.cat([self._encode_text(["", ""]), self._encode_text([case["guidance_text"], ""])], dim=0))
-        self.controller = ctrls[0]
-        maps = [self._cfg_row_map(t, 2) for t in texts]
-        if all(m[0] is not None and m[0] == maps[0][0] for m in maps):
-            row_map, lat_rows, txt_rows = maps[0]
-        else:                                                 # images disagree on which CFG rows coincide: evaluate all four
-            row_map, lat_rows, txt_rows = None, [0, 1, 0, 1], [0, 1, 2, 3]
-        Bp = len(lat_rows)
-        text_phys = torch.cat([t[txt_rows] for t in texts], dim=0).contiguous()
-        lat_idx = torch.tensor([2 * i + r for i in range(K) for r in lat_rows], device=self.device)
-        self.scheduler.set_timesteps(num_step)
-        n_act = num_step - start_step
-        shape2 = (2,) + tuple(init.shape[1:])
-        noises = []
-        for g in gens:
-            self._gen = g
-            noises.append(self._predraw_noise(n_act, shape2, eta))
-        latents = init.clone()                                # [2K,4,h,w]: rows (edit_i, ref_i)
-        lat_v = latents.view(K, 2, *init.shape[1:])
-        ref_flags = tuple(r == 1 for r in lat_rows)
-        cache = self._take_ref_cache(refer, n_act, texts[0], [txt_rows[p] for p, f in enumerate(ref_flags) if f])
-        if cache is not None and any(not torch.equal(t[txt_rows[p]], cache["text"][0]) for t in texts for p, f in enumerate(ref_flags) if f):
-            cache = None
-        # like the reference's latents_list (model.py:585-616) the recorded entries ALIAS the live latents: the reference row of
-        # entry j is overwritten in place by step j+1's `latents[1:] = ref_latent`
-        inter = [[latents[2 * i:2 * i + 2]] for i in range(K)] if return_intermediates else None
-        for i, t in enumerate(self.scheduler.timesteps):
-            if i < start_step:
-                continue
-            lat_v[:, 1] = refer[i - start_step + 1].view(K, 2, *init.shape[1:])[:, 1]
+        with self._batched_controllers(K) as ctrls:
+            seed_everything(seeds[0])
+            # rows (coarse_i, ori_i); the original image's row is the guided loop's reference row
+            source = torch.from_numpy(np.concatenate([np.stack([c["coarse_input"], self.resize_img(c["ori_img"], size=self._work_size(c["coarse_input"]))])
+                                                      for c in cases]))
+            init, refer = self._invert_batch(ctrls, source, num_step, start_step, record_rows=[2 * i + 1 for i in range(K)])
+            cfg_f, var_masks, texts = [], [], []
+            for case, c in zip(cases, ctrls):
+                draw = case.get("draw_mask")
+                cfg_m, var_m = self._setup_edit(c, case["coarse_input"].shape[:2], init, red(case["target_mask"]), red(case["ori_mask"]),
+                                                None if draw is None else red(draw), method_type, share_attn, use_auto_draw=case.get("use_auto_draw", False),
+                                                cons_area=case.get("cons_area"), reduce_inp_artifacts=case.get("reduce_inp_artifacts", False))
+                cfg_f.append(self._mask_f(cfg_m))
+                var_masks.append(var_m if local_perturbation else torch.ones_like(var_m))
+                texts.append(torch.cat([self._encode_text(["", ""]), self._encode_text([case["guidance_text"], ""])], dim=0))
+            noises = self._noise_per_case(seeds, num_step - start_step, (2,) + tuple(init.shape[1:]), eta)
+            latents = init.clone()                                # [2K,4,h,w]: rows (edit_i, ref_i)
+            latents, inter = self._guided_loop(EDIT, ctrls, texts, cfg_f, var_masks, noises, latents, refer,
+                                               [[latents[2 * k:2 * k + 2]] for k in range(K)] if return_intermediates else None,
+                                               method_type, num_step, start_step, end_step, end_scale, guidance_scale, eta)
             for c in ctrls:
-                if method_type == "tca":
-                    c.context_guidance = self.linear_param(i, start_step, end_step, num_step, end_scale=end_scale)
-                elif method_type == "mmsa_es" and i >= end_step:
-                    c.use_tca = False
-            reuse = None
-            if cache is not None:        # the reference rows re-enter from the state inversion step n - k - 1 recorded (same latent, timestep, prompt)
-                slot = cache["slots"][n_act - (i - start_step) - 1]
-                nr = sum(ref_flags)
-                # every step but the last overwrites the reference latent before anything reads it (`latents[1:] = ref_latent` above):
-                # the reference rows' eps is dead there and their tail behind the last K / V projection is not run
-                reuse = dict(mode="replay", join=cache["join"], ref=ref_flags, state=[s.repeat_interleave(nr, 0) for s in slot] if nr > 1 else slot,
-                             drop_tail=self.drop_ref_tail and i + 1 < len(self.scheduler.timesteps))
-            eps = self.unet(latents.index_select(0, lat_idx), t, encoder_hidden_states=text_phys, row_map=row_map, reuse=reuse)
-            eps = eps.view(K, 4, *init.shape[1:])
-            new = torch.empty_like(latents)
-            for k in range(K):
-                e = ops.cfg_masked(eps[k, :2].contiguous(), eps[k, 2:].contiguous(), cfg_f[k], guidance_scale)
-                new[2 * k:2 * k + 2] = self.ctrl_step(e, t, latents[2 * k:2 * k + 2], var_masks[k], eta=eta,
-                                                      noise=None if noises[k] is None else noises[k][i - start_step])[0]
-                if inter is not None:
-                    inter[k].append(new[2 * k:2 * k + 2])
-            latents = new
-            lat_v = latents.view(K, 2, *init.shape[1:])
-        for c in ctrls:
-            c.reset()
-        self.last_intermediates = inter
-        if return_ori:
-            images = self.latent2image(latents, return_type="pt")
-            u8 = images_to_u8(images)
-            return [(u8[2 * k], u8[2 * k + 1]) for k in range(K)]
-        # the reference decodes both streams and drops the reference image unless return_ori (model.py:619, 1046-1049): decode only
-        # the edited rows (VAE decode is per row: the kept image is unchanged)
-        images = self.latent2image(latents[0::2].contiguous(), return_type="pt")
-        return images_to_u8(images)
-
+                c.reset()
+            self.last_intermediates = inter
+            if return_ori:
+                u8 = images_to_u8(self.latent2image(latents, return_type="pt"))
+                return [(u8[2 * k], u8[2 * k + 1]) for k in range(K)]
+            # the reference decodes both streams and drops the reference image unless return_ori (model.py:619, 1046-1049): decode only
+            # the edited rows (VAE decode is per row: the kept image is unchanged)
+            return images_to_u8(self.latent2image(latents[0::2].contiguous(), return_type="pt"))
 
     @torch.no_grad()
     def FreeFine_background_generation_batch(self, cases, guidance_scale, eta, end_step=10, num_step=50, start_step=25, share_attn=True,
@@ -1074,79 +1054,24 @@ class FreeFinePipeline:
         assert self.unet.hook == "bggen", "register_attention_control_4bggen(model, controller) first"
         K = len(cases)
         seeds = [seeds] * K if isinstance(seeds, int) else list(seeds)
-        single = self.controller
-        ctrls = self._controllers_for_batch(K)
-        self.unet.controller = ctrls if K > 1 else single
-        try:
+        with self._batched_controllers(K) as ctrls:
             seed_everything(seeds[0])
-            gens = [torch.Generator().manual_seed(sd) for sd in seeds]
-            red = self.mask_reduce_dim
-            source = torch.from_numpy(np.stack([c["ori_img"] for c in cases]))
-            for c in ctrls:
-                c.reset()
-            _, inverted = self.invert(source, "", guidance_scale=1.0, num_inference_steps=num_step,
-                                      num_actual_inference_steps=num_step - start_step, return_intermediates=True)
-            for c in ctrls:
-                c.reset()
-            init, refer = inverted[-1], inverted[::-1]
+            init, refer = self._invert_batch(ctrls, torch.from_numpy(np.stack([c["ori_img"] for c in cases])), num_step, start_step)
             cfg_f, var_masks, texts = [], [], []
             for case, c in zip(cases, ctrls):
-                full_h, full_w = case["ori_img"].shape[:2]
-                mask_t, var_m = self.prepare_mask_bggen(red(case["ori_mask"]), full_h, full_w, init)
-                c.fg_retain_mask, c.local_edit_region = mask_t, mask_t
-                c.reset()
-                self.controller = c
-                self._configure_method(method_type, share_attn)
-                c.local_edit = local_text_edit
+                var_m = self._setup_background(c, case["ori_img"].shape[:2], init, self.mask_reduce_dim(case["ori_mask"]), method_type, share_attn,
+                                               local_text_edit)
                 cfg_f.append(self._mask_f(var_m) if local_text_edit else None)
                 var_masks.append(var_m if local_perturbation else torch.ones_like(var_m))
                 texts.append(torch.cat([self._encode_text(["", ""]), self._encode_text([case["guidance_text"], ""])], dim=0))
-            self.controller = ctrls[0]
-            maps = [self._cfg_row_map(t, 2) for t in texts]
-            if all(m[0] is not None and m[0] == maps[0][0] for m in maps):
-                row_map, lat_rows, txt_rows = maps[0]
-            else:
-                row_map, lat_rows, txt_rows = None, [0, 1, 0, 1], [0, 1, 2, 3]
-            text_phys = torch.cat([t[txt_rows] for t in texts], dim=0).contiguous()
-            lat_idx = torch.tensor([2 * i + r for i in range(K) for r in lat_rows], device=self.device)
-            self.scheduler.set_timesteps(num_step)
-            shape1 = tuple(init.shape[1:])
-            noises = []
-            for g in gens:
-                self._gen = g
-                noises.append(self._predraw_noise(num_step - start_step, (2,) + shape1, eta))
-            latents = torch.zeros((2 * K,) + shape1, dtype=init.dtype, device=init.device)     # rows (generated_i, reference_i)
-            lat_v = latents.view(K, 2, *shape1)
-            lat_v[:, 0] = init
-            inter = [[init[k:k + 1]] for k in range(K)] if return_intermediates else None
-            for i, t in enumerate(self.scheduler.timesteps):
-                if i < start_step:
-                    continue
-                lat_v[:, 1] = refer[i - start_step]                     # aligned reference latent (model.py:756)
-                for c in ctrls:
-                    if method_type == "tca":
-                        c.context_guidance = self.linear_param(i, start_step, end_step, num_step, end_scale=end_scale)
-                    elif method_type == "mmsa_es" and i >= end_step:
-                        c.use_tca = False
-                eps = self.unet(latents.index_select(0, lat_idx), t, encoder_hidden_states=text_phys, row_map=row_map)
-                eps = eps.view(K, 4, *shape1)
-                new = torch.empty_like(latents)
-                for k in range(K):
-                    e = ops.cfg_masked(eps[k, :2].contiguous(), eps[k, 2:].contiguous(), cfg_f[k], guidance_scale)
-                    new[2 * k:2 * k + 2] = self.ctrl_step(e, t, latents[2 * k:2 * k + 2], var_masks[k], eta=eta,
-                                                          noise=None if noises[k] is None else noises[k][i - start_step])[0]
-                    if inter is not None:
-                        inter[k].append(new[2 * k])
-                latents = new
-                lat_v = latents.view(K, 2, *shape1)
+            noises = self._noise_per_case(seeds, num_step - start_step, (2,) + tuple(init.shape[1:]), eta)
+            latents, inter = self._guided_loop(BACKGROUND, ctrls, texts, cfg_f, var_masks, noises, self._with_ref_rows(init), refer,
+                                               [[init[k:k + 1]] for k in range(K)] if return_intermediates else None,
+                                               method_type, num_step, start_step, end_step, end_scale, guidance_scale, eta)
             for c in ctrls:
                 c.reset()
-            images = self.latent2image(latents[0::2].contiguous(), return_type="pt")      # only the generated rows are returned (model.py:1118)
             self.last_intermediates = inter
-            return images_to_u8(images)
-        finally:
-            self.controller = single
-            self.unet.controller = single
+            return images_to_u8(self.latent2image(latents[0::2].contiguous(), return_type="pt"))      # only the generated rows are returned (model.py:1118)
 
     @torch.no_grad()
     def FreeFine_cross_image_composition_batch(self, cases, guidance_scale, eta, end_step=10, num_step=50, start_step=25, share_attn=True,
@@ -1165,82 +1090,30 @@ class FreeFinePipeline:
         R, P = len(cases[0]["img_lists"]), len(cases[0]["guidance_text_list"]) + 1
         assert all(len(c["img_lists"]) == R and len(c["guidance_text_list"]) + 1 == P for c in cases), "batched compositions share R and the prompt count"
         seeds = [seeds] * K if isinstance(seeds, int) else list(seeds)
-        single = self.controller
-        ctrls = self._controllers_for_batch(K)
-        self.unet.controller = ctrls if K > 1 else single
-        try:
+        red = self.mask_reduce_dim
+        with self._batched_controllers(K) as ctrls:
             seed_everything(seeds[0])
-            gens = [torch.Generator().manual_seed(sd) for sd in seeds]
-            red = self.mask_reduce_dim
+            # rows (coarse_i, ref_i1 .. ref_iR): the composition hook leaves the reference rows unmodulated, so their K / V are recorded
             source = torch.from_numpy(np.concatenate([np.stack([c["coarse_input"]] + [self.resize_img(r, size=self._work_size(c["coarse_input"]))
                                                                                       for r in c["img_lists"]]) for c in cases]))
-            for c in ctrls:
-                c.reset()
-            _, inverted = self.invert(source, "", guidance_scale=1.0, num_inference_steps=num_step,
-                                      num_actual_inference_steps=num_step - start_step, return_intermediates=True,
-                                      record_rows=[k * (1 + R) + r for k in range(K) for r in range(1, 1 + R)], record_kv=True)
-            for c in ctrls:
-                c.reset()
-            init, refer = inverted[-1], inverted[::-1]                     # [K (1 + R), 4, h, w]
-            shape1 = tuple(init.shape[1:])
+            init, refer = self._invert_batch(ctrls, source, num_step, start_step,
+                                             record_rows=[k * (1 + R) + r for k in range(K) for r in range(1, 1 + R)], record_kv=True)
             cfg_f, var_masks, texts = [], [], []
             for case, c in zip(cases, ctrls):
-                full_h, full_w = case["coarse_input"].shape[:2]
-                tgt_t, ori_t, lp, cfg_m = self.prepare_composition_masks([red(m) for m in case["ori_mask_lists"]], [red(m) for m in case["tgt_mask_lists"]],
-                                                                         full_h, full_w, init, dil_completion=dil_completion, dil_factor=dil_factor,
-                                                                         draw_mask=case.get("draw_mask"), appearance_transfer=appearance_transfer)
-                c.src_masks, c.tgt_masks = ori_t, tgt_t
-                c.reset()
-                self.controller = c
-                self._configure_method(method_type, share_attn)
-                c.local_edit = local_text_edit
-                c.prompt_length = P
+                lp, cfg_m = self._setup_compose(c, case["coarse_input"].shape[:2], init, [red(m) for m in case["ori_mask_lists"]],
+                                                [red(m) for m in case["tgt_mask_lists"]], case.get("draw_mask"), P - 1, method_type, share_attn,
+                                                local_text_edit, dil_completion=dil_completion, dil_factor=dil_factor, appearance_transfer=appearance_transfer)
                 cfg_f.append(self._mask_f(cfg_m) if local_text_edit else None)
                 var_masks.append(lp if local_perturbation else torch.ones_like(lp))
                 texts.append(torch.cat([self._encode_text([""] * (1 + R)), self._encode_text(list(case["guidance_text_list"]) + [""])], dim=0))
-            self.controller = ctrls[0]
-            text_all = torch.cat(texts, dim=0).contiguous()
-            self.scheduler.set_timesteps(num_step)
-            n_act = num_step - start_step
-            noises = []
-            for g in gens:
-                self._gen = g
-                noises.append(self._predraw_noise(n_act, (1,) + shape1, eta))
-            latents = init.clone().view(K, 1 + R, *shape1)                 # rows (edit_i, ref_i1 .. ref_iR)
-            # latent rows of the UNet batch: per image [0 .. R, 0]
-            row_idx = torch.tensor([i * (1 + R) + r for i in range(K) for r in list(range(1 + R)) + [0]], device=self.device)
-            inter = [[init.view(K, 1 + R, *shape1)[k]] for k in range(K)] if return_intermediates else None
-            cache = self._take_ref_cache(refer, n_act, texts[0], list(range(1, 1 + R)), kv=True)
-            if cache is not None and any(not torch.equal(tx[r], cache["text"][0]) for tx in texts for r in range(1, 1 + R)):
-                cache = None
-            for i, t in enumerate(self.scheduler.timesteps):
-                if i < start_step:
-                    continue
-                latents[:, 1:] = refer[i - start_step + 1].view(K, 1 + R, *shape1)[:, 1:]
-                for c in ctrls:
-                    if method_type == "tca":
-                        c.context_guidance = self.linear_param(i, start_step, end_step, num_step, end_scale=end_scale)
-                    elif method_type == "mmsa_es" and i >= end_step:
-                        c.use_tca = False
-                reuse = None if cache is None else self._replay_kv_arg(cache, cache["slots"][n_act - (i - start_step) - 1], R, P)
-                eps = self.unet(latents.view(K * (1 + R), *shape1).index_select(0, row_idx), t, encoder_hidden_states=text_all, reuse=reuse)
-                eps = eps.view(K, R + 2, *shape1)
-                new = latents.clone()
-                for k in range(K):
-                    e = ops.cfg_masked(eps[k, :1].contiguous(), eps[k, -1:].contiguous(), cfg_f[k], guidance_scale)
-                    new[k, :1] = self.ctrl_step(e, t, latents[k, :1].contiguous(), var_masks[k], eta=eta,
-                                                noise=None if noises[k] is None else noises[k][i - start_step])[0]
-                    if inter is not None:
-                        inter[k].append(new[k, 0])
-                latents = new
+            noises = self._noise_per_case(seeds, num_step - start_step, (1,) + tuple(init.shape[1:]), eta)
+            latents, inter = self._guided_loop(COMPOSE, ctrls, texts, cfg_f, var_masks, noises, init.clone(), refer,
+                                               [[init[(1 + R) * k:(1 + R) * (k + 1)]] for k in range(K)] if return_intermediates else None,
+                                               method_type, num_step, start_step, end_step, end_scale, guidance_scale, eta)
             for c in ctrls:
                 c.reset()
-            images = self.latent2image(latents[:, 0].contiguous(), return_type="pt")
             self.last_intermediates = inter
-            return images_to_u8(images)
-        finally:
-            self.controller = single
-            self.unet.controller = single
+            return images_to_u8(self.latent2image(latents[0::1 + R].contiguous(), return_type="pt"))
 
     def FreeFine_background_generation(self, ori_img, ori_mask, guidance_text, guidance_scale, eta, end_step=10, num_step=50,
                                        start_step=25, share_attn=True, method_type="tca", local_text_edit=True, local_perturbation=True,
