@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "igemm.h"
 #include "../../include/freefine_hip.h"
 
 #define ATT_XCD_MIN_GROUPS 64      // (row, head) groups from which the attention kernels take the XCD-contiguous block order (see attn_kernel)
@@ -59,6 +60,25 @@ __device__ __forceinline__ float att_max_groups(float x) {
     return att_max(__uint_as_float(c[0]), __uint_as_float(c[1]));
 }
 
+// ---- the pass table in code: every attention kernel reads ffn_attn_desc through these (the prose above is the one statement of the semantics) ----
+// The predicates that load entry fields behind short-circuit tests are MACROS, not functions: hipcc simplifies a helper function on its own before it
+// inlines it (merged loads, if-converted tests), and the kernels' instruction schedules and register numbering then change down into the key loops.
+// With the macros, and the functions below, the code objects of all attention kernels are byte-identical to the hand-repeated form they replace.
+// An entry takes part in its row's sum.  Also the host's test (attn_plan, capi_attn.hip).
+#define ATT_ENTRY_SKIPPED(e) ((e).w_const == 0.f && (e).w_slope == 0.f)
+#define ATT_ENTRY_ACTIVE(e) (!ATT_ENTRY_SKIPPED(e))
+// w_const + w_slope * *w_dev.  The short-key kernels (attention_x.h, attention_xx3.h) keep their own form, w_const + (w_slope != 0 ? w_slope * *w_dev : 0),
+// because this one changes their code: the host plan admits them only when w_slope == 0 || w_dev on every active entry (xok in attn_plan), and under
+// that condition the two forms give the same value.
+__device__ __forceinline__ float att_pass_weight(const AttnParams& p, const AttnEntry& e) {
+    float w = e.w_const;
+    if (p.w_dev) w += e.w_slope * (*p.w_dev);
+    return w;
+}
+// The entry's key mask applies on (output row b, head): the tiled-head rule tests the parity of j = row * heads + head, row = the pinned hr_row or b.  Block-uniform.
+#define ATT_HEAD_ROW(e, b) ((e).hr_row > 0 ? (e).hr_row - 1 : (b))
+#define ATT_ENTRY_MASKED(p, e, hb, head) ((e).kmask && (!((e).flags & ATT_HEAD_RULE) || ((((hb) * (p).heads + (head)) & 1) == 0)))
+
 // Duplicate passes of a self-referencing row.  The TCA tables give EVERY row two passes -- (q = b, kv = ref(b), key mask under the
 // tiled-head rule, weight cg) and (q = b, kv = b, no mask, weight 1 - cg) -- and for a reference row ref(b) = b
 // (attention.py:1033-1035, 1060-1083).  Under the tiled-head rule the mask applies to the heads with even b * heads + head only
@@ -69,18 +89,61 @@ __device__ __forceinline__ int att_duplicate_pass(const AttnParams& p, int b, in
     if (p.npass != 2) return -1;
     const AttnEntry& a0 = p.e[b];
     const AttnEntry& a1 = p.e[ATT_MAXB + b];
-    if ((a0.w_const == 0.f && a0.w_slope == 0.f) || (a1.w_const == 0.f && a1.w_slope == 0.f)) return -1;
+    if (ATT_ENTRY_SKIPPED(a0) || ATT_ENTRY_SKIPPED(a1)) return -1;
     if (a0.q_row != a1.q_row || a0.kv_row != a1.kv_row || a0.wq != a1.wq) return -1;
     auto masked = [&](const AttnEntry& e) {
-        const int hb = e.hr_row > 0 ? e.hr_row - 1 : b;
-        return e.kmask && (!(e.flags & ATT_HEAD_RULE) || (((hb * p.heads + head) & 1) == 0));
+        const int hb = ATT_HEAD_ROW(e, b);
+        return ATT_ENTRY_MASKED(p, e, hb, head);
     };
     return (masked(a0) || masked(a1)) ? -1 : 1;
 }
-__device__ __forceinline__ float att_pass_weight(const AttnParams& p, const AttnEntry& e) {
-    float w = e.w_const;
-    if (p.w_dev) w += e.w_slope * (*p.w_dev);
+// The plan of an output row on one head: returns how many passes it runs (0: the row is zeros); dup = the pass folded into pass 0 (-1: none).
+// (attn_kernel and attn_x3_kernel keep these lines in place: through this function their scalar registers are numbered differently.)
+__device__ __forceinline__ int att_row_plan(const AttnParams& p, int b, int head, int& dup) {
+    int nactive = 0;
+    for (int pass = 0; pass < p.npass; ++pass) {
+        const AttnEntry& e0 = p.e[pass * ATT_MAXB + b];
+        nactive += ATT_ENTRY_ACTIVE(e0) ? 1 : 0;
+    }
+    dup = att_duplicate_pass(p, b, head);
+    if (dup >= 0) nactive = 1;
+    return nactive;
+}
+// One pass of the row.  Skipped: an inactive entry, or the duplicate folded into pass 0.  Its weight: the entry's, the folded duplicate's added.
+// Whether its key mask applies on this head: ATT_ENTRY_MASKED at row ATT_HEAD_ROW (kernels compiled without key masks, MASKS = false, put that in front).
+#define ATT_PASS_SKIPPED(en, pass, dup) (ATT_ENTRY_SKIPPED(en) || (pass) == (dup))
+__device__ __forceinline__ float att_pass_total_weight(const AttnParams& p, const AttnEntry& en, int dup, int b) {
+    float w = att_pass_weight(p, en);
+    if (dup >= 0) w += att_pass_weight(p, p.e[dup * ATT_MAXB + b]);
     return w;
+}
+// The query side of a pass: the per-query weight; under a masked pass the selector (1: the query wants the keys with mask != 0), as attn_kernel's
+// mode (0 = all keys, 1 = keys with mask != 0, 2 = keys with mask == 0, 3 = uniform over all keys) and as the selector word of the mask k-step
+// (bf16 1.0 in the half that penalises the keys the query does not want: [wants mask != 0 | wants mask == 0]).
+#define ATT_QUERY_WEIGHT(en, q, qok) (((en).wq && (qok)) ? (en).wq[q] : 1.f)
+#define ATT_QUERY_SEL(en, q, qok) (((en).qsel && (qok)) ? ((en).qsel[q] != 0) : 1)
+#define ATT_QUERY_MODE(en, pass_masked, q, qok)                                                                                        \
+    ({ int md_ = 0;                                                                                                                    \
+       if (pass_masked) { const int sel_ = ATT_QUERY_SEL(en, q, qok); md_ = sel_ ? 1 : 2;                                              \
+                          if (sel_ && ((en).flags & ATT_UNIFORM_SEL1)) md_ = 3; if (!sel_ && ((en).flags & ATT_UNIFORM_SEL0)) md_ = 3; } \
+       md_; })
+__device__ __forceinline__ uint32_t att_sel_word(int sel) { return sel ? 0x3f80u : 0x3f800000u; }
+// Four consecutive columns head * D + d .. + 3 of output row (b, q): fp32 / bf16 row, or (PAIR kernels, out_pair) the bf16 pair form hi | lo at ldo / 2.
+template <bool PAIR, typename T>
+__device__ __forceinline__ void att_store_out(const AttnParams& p, T* Og, int b, int head, int D, int q, int d, const float* vv) {
+    if (PAIR && p.out_pair) store_pair_row4(reinterpret_cast<bf16*>(p.out) + ((long)b * p.S + q) * p.ldo, head * D + d, p.ldo / 2, vv);
+    else store4(Og + ((long)b * p.S + q) * p.ldo + head * D + d, vv);
+}
+// bytes of the multi-pass sums of `waves` waves holding o[fd][qf] f32x4 per lane
+constexpr int att_totl_bytes(int waves, int fd, int qf) { return waves * fd * qf * 64 * 16; }
+constexpr int ATT_LDS_MAX = 160 * 1024;      // LDS of a gfx950 CU: every attention kernel's size function is checked against it
+
+// attn_kernel's LDS geometry: K tile rows of 128 bytes are XOR-swizzled, others padded by 16; V^T tile rows of 128 bytes (bf16, d = 64: global -> LDS
+// directly) are swizzled, others padded by 16.  LDS = double-buffered K and V^T tiles | the multi-pass sums | the key-mask bytes of the two staged tiles.
+constexpr int attn_kernel_krow(int esz, int dp) { return dp * esz == 128 ? 128 : dp * esz + 16; }
+constexpr int attn_kernel_vrow(int esz, int dp, int kt) { return (dp * esz == 128 && kt * esz == 128) ? 128 : kt * esz + 16; }
+constexpr int attn_kernel_lds(int esz, int dp, int qf, int kt) {
+    return 2 * (kt * attn_kernel_krow(esz, dp) + dp * attn_kernel_vrow(esz, dp, kt)) + att_totl_bytes(4, dp / 16, qf) + 2 * kt;
 }
 
 // KT = keys per tile, OCC = min waves per SIMD, MASKS = some entry of the launch carries a key mask (bf16: compiles the
@@ -91,9 +154,9 @@ __global__ __launch_bounds__(256, OCC) void attn_kernel(const AttnParams p) {
     constexpr int SZ = sizeof(T);
     constexpr int NT = KT / 16;                 // 16-key fragments per tile
     constexpr bool KSWZ = (DP * SZ == 128);     // 128-byte K rows: XOR-swizzled chunks (conflict-free ds_read_b128, like igemm)
-    constexpr int KROW = KSWZ ? 128 : DP * SZ + 16;   // otherwise +16 B row padding (2-way conflicts on some lane groups)
+    constexpr int KROW = attn_kernel_krow(SZ, DP);    // otherwise +16 B row padding (2-way conflicts on some lane groups)
     constexpr bool GLDS = KSWZ && (KT * SZ == 128);    // bf16, d = 64: K and V^T tiles go global -> LDS directly (no register staging)
-    constexpr int VROW = GLDS ? 128 : KT * SZ + 16;   // V^T tile row stride (GLDS: unpadded 128-byte rows, chunks XOR-swizzled by (row>>1)&7)
+    constexpr int VROW = attn_kernel_vrow(SZ, DP, KT);   // V^T tile row stride (GLDS: unpadded 128-byte rows, chunks XOR-swizzled by (row>>1)&7)
     constexpr int DCH = DP / EPC;               // 16-byte chunks per K row
     constexpr int DSL = DP * SZ / 64;           // 64-byte d-slabs (MFMA k-substeps of QK^T)
     constexpr int FD = DP / 16;                 // d fragments of O^T
@@ -132,12 +195,15 @@ __global__ __launch_bounds__(256, OCC) void attn_kernel(const AttnParams p) {
     const float c_exp = FAST ? 1.0f : c_pre;                 // softmax in base 2: p = exp2(s*c - m)
 
     // multi-pass sums live in LDS between passes (touched once per pass), not in registers: [wave][FD][QF][lane] f32x4
-    f32x4* totl = reinterpret_cast<f32x4*>(smem + 2 * (KBUF + VBUF)) + wave * (FD * QF * 64) + lane;
-    uint8_t* Ms = reinterpret_cast<uint8_t*>(smem + 2 * (KBUF + VBUF) + 4 * FD * QF * 64 * 16);   // FAST: [2][KT] key-mask bytes of the staged tiles
+    constexpr int OFF_TOT = 2 * (KBUF + VBUF), OFF_M = OFF_TOT + att_totl_bytes(4, FD, QF);
+    static_assert(OFF_M + 2 * KT == attn_kernel_lds(SZ, DP, QF, KT) && OFF_M + 2 * KT <= ATT_LDS_MAX, "attn_kernel_lds is this kernel's LDS layout");
+    f32x4* totl = reinterpret_cast<f32x4*>(smem + OFF_TOT) + wave * (FD * QF * 64) + lane;
+    uint8_t* Ms = reinterpret_cast<uint8_t*>(smem + OFF_M);   // FAST: [2][KT] key-mask bytes of the staged tiles
+    // (the row plan in place, not att_row_plan: as a function it renumbers this kernel's scalar registers)
     int nactive = 0, nseen = 0;
     for (int pass = 0; pass < p.npass; ++pass) {
         const AttnEntry& e0 = p.e[pass * ATT_MAXB + b];
-        nactive += (e0.w_const != 0.f || e0.w_slope != 0.f) ? 1 : 0;
+        nactive += ATT_ENTRY_ACTIVE(e0) ? 1 : 0;
     }
     const int dup = att_duplicate_pass(p, b, head);      // a self-referencing row's second pass on a head the mask skips: folded into the first
     if (dup >= 0) nactive = 1;
@@ -160,13 +226,10 @@ __global__ __launch_bounds__(256, OCC) void attn_kernel(const AttnParams p) {
 
     for (int pass = 0; pass < p.npass; ++pass) {
         const AttnEntry& en = p.e[pass * ATT_MAXB + b];
-        if (en.w_const == 0.f && en.w_slope == 0.f) continue;   // block-uniform skip
-        if (pass == dup) continue;
-        float w = en.w_const;
-        if (p.w_dev) w += en.w_slope * (*p.w_dev);
-        if (dup >= 0) w += att_pass_weight(p, p.e[dup * ATT_MAXB + b]);
-        const int hb = en.hr_row > 0 ? en.hr_row - 1 : b;   // batch row the reference's j = b*heads + head refers to
-        const bool pass_masked = en.kmask && (!(en.flags & ATT_HEAD_RULE) || (((hb * p.heads + head) & 1) == 0));  // block-uniform
+        if (ATT_PASS_SKIPPED(en, pass, dup)) continue;         // block-uniform skip
+        const float w = att_pass_total_weight(p, en, dup, b);
+        const int hb = ATT_HEAD_ROW(en, b);
+        const bool pass_masked = ATT_ENTRY_MASKED(p, en, hb, head);   // block-uniform
 
         // ---- Q^T fragments (B operand of S^T = K.Q^T): lane = query l15 of fragment f, chunk 4s+g ------------
         u32x4 qf[QF][DSL];
@@ -190,15 +253,8 @@ __global__ __launch_bounds__(256, OCC) void attn_kernel(const AttnParams p) {
                     qf[f][s] = DT<T>::pack(tmp);
                 }
             }
-            wq[f] = (en.wq && qok) ? en.wq[q] : 1.f;
-            int md = 0;
-            if (pass_masked) {
-                const int sel = (en.qsel && qok) ? (en.qsel[q] != 0) : 1;
-                md = sel ? 1 : 2;
-                if (sel && (en.flags & ATT_UNIFORM_SEL1)) md = 3;
-                if (!sel && (en.flags & ATT_UNIFORM_SEL0)) md = 3;
-            }
-            mode[f] = md;
+            wq[f] = ATT_QUERY_WEIGHT(en, q, qok);
+            mode[f] = ATT_QUERY_MODE(en, pass_masked, q, qok);
         }
         // FAST: the query side of the mask k-step (see tile_fast) and whether this wave holds a degenerate uniform-softmax query
         u32x4 qaug[QF];

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(384) void attn_causal_kernel(const AttnParams p) {
     const u32x4 zero4 = u32x4{0u, 0u, 0u, 0u};
     const f32x4 zerof = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    if (e.w_const == 0.f && e.w_slope == 0.f) {        // skipped entry: the row's sum over passes is empty
+    if (ATT_ENTRY_SKIPPED(e)) {               // skipped entry: the row's sum over passes is empty
         if (qok) {
             const float z[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll

@@ -39,12 +39,19 @@ __device__ __forceinline__ void attpp_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// attn_pp_kernel's LDS: rings of four slots each of K tiles, V^T tiles (64 rows of 128 bytes) and key-mask bytes (256 per slot) | the multi-pass sums of its 8 waves
+constexpr int ATTPP_TILE = 64 * 128, ATTPP_NSLOT = 4, ATTPP_MSLOT = 256;
+constexpr int ATTPP_OFF_V = ATTPP_NSLOT * ATTPP_TILE, ATTPP_OFF_M = ATTPP_OFF_V + ATTPP_NSLOT * ATTPP_TILE, ATTPP_OFF_TOT = ATTPP_OFF_M + ATTPP_NSLOT * ATTPP_MSLOT;
+constexpr int attn_pp_lds_bytes() { return ATTPP_OFF_TOT + att_totl_bytes(8, 4, 2); }
+
 template <bool MASKS>
 __global__ __launch_bounds__(512) void attn_pp_kernel(const AttnParams p) {
     typedef bf16 T;
     constexpr int D = 64, KT = 64, QF = 2, NT = 4, FD = 4, DSL = 2, NC = 2;     // NC = 32-key chunks per tile (PV k-steps)
-    constexpr int KBUF = KT * 128, VBUF = D * 128, NSLOT = 4;
-    constexpr int OFF_V = NSLOT * KBUF, OFF_M = OFF_V + NSLOT * VBUF, OFF_TOT = OFF_M + NSLOT * 256;
+    constexpr int KBUF = ATTPP_TILE, VBUF = ATTPP_TILE, NSLOT = ATTPP_NSLOT;
+    constexpr int OFF_V = ATTPP_OFF_V, OFF_M = ATTPP_OFF_M, OFF_TOT = ATTPP_OFF_TOT;
+    static_assert(KBUF == KT * 128 && VBUF == D * 128, "ATTPP_TILE is a 64-row bf16 tile");
+    static_assert(OFF_TOT + att_totl_bytes(8, FD, QF) == attn_pp_lds_bytes() && attn_pp_lds_bytes() <= ATT_LDS_MAX, "attn_pp_lds_bytes is this kernel's LDS layout");
     constexpr int OOB = 0x7ffff000;
     constexpr float FAST_THR = 6.0f;
     constexpr float NEG = -1e30f;
@@ -62,13 +69,9 @@ __global__ __launch_bounds__(512) void attn_pp_kernel(const AttnParams p) {
     const float c_pre = p.scale * 1.44269504088896340736f;
 
     f32x4* totl = reinterpret_cast<f32x4*>(smem + OFF_TOT) + wave * (FD * QF * 64) + lane;     // multi-pass sums, wave private
-    int nactive = 0, nseen = 0;
-    for (int pass = 0; pass < p.npass; ++pass) {
-        const AttnEntry& e0 = p.e[pass * ATT_MAXB + b];
-        nactive += (e0.w_const != 0.f || e0.w_slope != 0.f) ? 1 : 0;
-    }
-    const int dup = att_duplicate_pass(p, b, head);      // a self-referencing row's second pass on a head the mask skips: folded into the first
-    if (dup >= 0) nactive = 1;
+    int dup;                                             // a self-referencing row's second pass on a head the mask skips: folded into the first
+    const int nactive = att_row_plan(p, b, head, dup);
+    int nseen = 0;
     if (nactive == 0) {   // nothing contributes to this output row: zeros (workgroup-uniform: no barrier has been executed yet)
 #pragma unroll
         for (int f = 0; f < QF; ++f) {
@@ -104,13 +107,10 @@ __global__ __launch_bounds__(512) void attn_pp_kernel(const AttnParams p) {
 
     for (int pass = 0; pass < p.npass; ++pass) {
         const AttnEntry& en = p.e[pass * ATT_MAXB + b];
-        if (en.w_const == 0.f && en.w_slope == 0.f) continue;   // workgroup-uniform skip
-        if (pass == dup) continue;
-        float w = en.w_const;
-        if (p.w_dev) w += en.w_slope * (*p.w_dev);
-        if (dup >= 0) w += att_pass_weight(p, p.e[dup * ATT_MAXB + b]);
-        const int hb = en.hr_row > 0 ? en.hr_row - 1 : b;
-        const bool pass_masked = MASKS && en.kmask && (!(en.flags & ATT_HEAD_RULE) || (((hb * p.heads + head) & 1) == 0));
+        if (ATT_PASS_SKIPPED(en, pass, dup)) continue;          // workgroup-uniform skip
+        const float w = att_pass_total_weight(p, en, dup, b);
+        const int hb = ATT_HEAD_ROW(en, b);
+        const bool pass_masked = MASKS && ATT_ENTRY_MASKED(p, en, hb, head);
 
         // ---- Q^T fragments, pre-scaled by scale * log2(e) ---------------------------------------------------------------
         u32x4 qf[QF][DSL], qaug[QF];
@@ -129,12 +129,9 @@ __global__ __launch_bounds__(512) void attn_pp_kernel(const AttnParams p) {
                 for (int e = 0; e < 8; ++e) tmp[e] *= c_pre;
                 qf[f][s] = DT<T>::pack(tmp);
             }
-            wq[f] = (en.wq && qok) ? en.wq[q] : 1.f;
+            wq[f] = ATT_QUERY_WEIGHT(en, q, qok);
             qaug[f] = u32x4{0, 0, 0, 0};
-            if (MASKS && pass_masked && g == 0) {
-                const int sel = (en.qsel && qok) ? (en.qsel[q] != 0) : 1;
-                qaug[f][0] = sel ? 0x3f80u : 0x3f800000u;       // [wants mask != 0 | wants mask == 0]
-            }
+            if (MASKS && pass_masked && g == 0) qaug[f][0] = att_sel_word(ATT_QUERY_SEL(en, q, qok));
         }
 
         f32x4 o[FD][QF], lacc[QF], st[NT][QF];
@@ -160,7 +157,7 @@ __global__ __launch_bounds__(512) void attn_pp_kernel(const AttnParams p) {
             const int so = t < ntiles ? t * KT * p.ldk * 2 : OOB;
             if (ATTPP_ABL == 1) return;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsK, (att_lptr_t)(smem + slot * KBUF + wave * 1024), 16, k_voff, so, 0, 0);
-            if (MASKS) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsM, (att_lptr_t)(smem + OFF_M + slot * 256), 4, m_voff, t < ntiles ? t * KT : OOB, 0, 0);
+            if (MASKS) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsM, (att_lptr_t)(smem + OFF_M + slot * ATTPP_MSLOT), 4, m_voff, t < ntiles ? t * KT : OOB, 0, 0);
         };
         auto issue_v = [&](int t) {
             const int slot = t & (NSLOT - 1);
@@ -178,7 +175,7 @@ __global__ __launch_bounds__(512) void attn_pp_kernel(const AttnParams p) {
                 for (int tt = 0; tt < NT; ++tt) ka[s][tt] = *reinterpret_cast<const u32x4*>(Kb + ka_rd[s] + tt * 2048);
             if (MASKS && pass_masked) {
                 constexpr uint32_t NB = 0xf14au;                // bf16(-1e30)
-                const uint8_t* Mb = reinterpret_cast<const uint8_t*>(smem + OFF_M + (t & (NSLOT - 1)) * 256);
+                const uint8_t* Mb = reinterpret_cast<const uint8_t*>(smem + OFF_M + (t & (NSLOT - 1)) * ATTPP_MSLOT);
 #pragma unroll
                 for (int tt = 0; tt < NT; ++tt) {
                     const bool m1 = Mb[32 * (tt >> 1) + 8 * (l15 >> 2) + 4 * (tt & 1) + (l15 & 3)] != 0;    // key of LDS row 16 tt + l15

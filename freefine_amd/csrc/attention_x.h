@@ -193,12 +193,17 @@ __global__ __launch_bounds__(256) void xattn_kernel(const AttnParams p, int wave
 // (row, head) do not fit one wave's registers, so a workgroup (4 waves) keeps them in LDS as FRAGMENT IMAGES (the 16 bytes a lane
 // would hold, lane-major: 1 KiB per fragment, conflict-free by construction), 22 KiB per pass at 77 keys, and its waves stream query
 // blocks of 32 past them, pass by pass, summing the weighted pass results in registers.
+// fragments per pass (K: NKF x 2 d-steps, V^T: 4 d-fragments x ceil(NKF / 2) key steps), 1 KiB each; the LDS of a launch = the images of all its passes
+constexpr int xattn_nfr(int nkf) { return nkf * 2 + 4 * ((nkf + 1) / 2); }
+constexpr int xattn_mp_lds_bytes(int nkf, int npass) { return npass * xattn_nfr(nkf) * 1024; }
+static_assert(xattn_mp_lds_bytes(6, ATT_MAXP) <= ATT_LDS_MAX, "xattn_mp_kernel's fragment images do not fit the LDS");
+
 template <int NKF>
 __global__ __launch_bounds__(256) void xattn_mp_kernel(const AttnParams p, int wgs_per_pair, int blocks_per_wave) {
     typedef bf16 T;
     constexpr int NKS = (NKF + 1) / 2;
     constexpr int QF = 2;
-    constexpr int NFR = NKF * 2 + 4 * NKS;            // fragments per pass (K: NKF x 2 d-steps, V^T: 4 d-fragments x NKS key steps)
+    constexpr int NFR = xattn_nfr(NKF);
     constexpr int OOB = (int)0x80000000;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -215,7 +220,7 @@ __global__ __launch_bounds__(256) void xattn_mp_kernel(const AttnParams p, int w
     // ---- fragment images of every active pass -> LDS (fragment i of pass ps at (ps * NFR + i) KiB; the waves share the fragments) ----
     for (int ps = 0; ps < p.npass; ++ps) {
         const AttnEntry& e = p.e[ps * ATT_MAXB + b];
-        if (e.w_const == 0.f && e.w_slope == 0.f) continue;
+        if (ATT_ENTRY_SKIPPED(e)) continue;
         for (int i = wave; i < NFR; i += 4) {
             u32x4 v;
             if (i < 2 * NKF) {
@@ -254,7 +259,7 @@ __global__ __launch_bounds__(256) void xattn_mp_kernel(const AttnParams p, int w
             for (int qf = 0; qf < QF; ++qf) acc[df][qf] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int ps = 0; ps < p.npass; ++ps) {
             const AttnEntry& e = p.e[ps * ATT_MAXB + b];
-            if (e.w_const == 0.f && e.w_slope == 0.f) continue;
+            if (ATT_ENTRY_SKIPPED(e)) continue;
             const float w = e.w_const + (e.w_slope != 0.f ? e.w_slope * *p.w_dev : 0.f);
             const char* img = smem + ps * NFR * 1024 + lane * 16;
             u32x4 qa[QF][2];

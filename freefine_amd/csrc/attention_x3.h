@@ -26,6 +26,10 @@ __device__ __forceinline__ void x3_split8(const f32x4& a, const f32x4& b, u32x4&
 }
 __device__ __forceinline__ void x3_mma(const u32x4& a, const u32x4& b, f32x4& c) { DT<bf16>::mma(a, b, c); }
 
+// attn_x3_kernel's LDS: two stages of [K_hi | K_lo | V^T_hi | V^T_lo] bf16 tiles (64 rows of 128 bytes each) | the multi-pass sums of its 8 waves
+constexpr int X3_TILE = 64 * 128, X3_STAGE = 4 * X3_TILE, X3_OFF_TOT = 2 * X3_STAGE;
+constexpr int attn_x3_lds_bytes() { return X3_OFF_TOT + att_totl_bytes(8, 4, 2); }
+
 template <bool MASKS>
 __global__ __launch_bounds__(512) void attn_x3_kernel(const AttnParams p) {
     constexpr int DP = 64, QF = 2, KT = 64, NW = 8;
@@ -34,8 +38,10 @@ __global__ __launch_bounds__(512) void attn_x3_kernel(const AttnParams p) {
     constexpr int DSL = DP / 32;                // 32-element d-slabs = MFMA k-steps of QK^T
     constexpr int FD = DP / 16;                 // d fragments of O^T
     constexpr int NPC = KT / 32;                // 32-key chunks = MFMA k-steps of PV
-    constexpr int KBUF = KT * KROW, VBUF = DP * VROW, BUF = 2 * KBUF + 2 * VBUF;      // one stage: K_hi | K_lo | V_hi | V_lo
+    constexpr int KBUF = X3_TILE, VBUF = X3_TILE, BUF = X3_STAGE;      // one stage: K_hi | K_lo | V_hi | V_lo
     constexpr float NEG = -1e30f;
+    static_assert(KBUF == KT * KROW && VBUF == DP * VROW && BUF == 2 * KBUF + 2 * VBUF, "X3_TILE is a 64-row bf16 tile");
+    static_assert(X3_OFF_TOT + att_totl_bytes(NW, FD, QF) == attn_x3_lds_bytes() && attn_x3_lds_bytes() <= ATT_LDS_MAX, "attn_x3_lds_bytes is this kernel's LDS layout");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -51,19 +57,17 @@ __global__ __launch_bounds__(512) void attn_x3_kernel(const AttnParams p) {
     float* __restrict__ Og = reinterpret_cast<float*>(p.out);
     const float c_exp = p.scale * 1.44269504088896340736f;      // softmax in base 2: p = exp2(s * c - m)
 
-    f32x4* totl = reinterpret_cast<f32x4*>(smem + 2 * BUF) + wave * (FD * QF * 64) + lane;     // multi-pass sums: [wave][FD][QF][lane]
+    f32x4* totl = reinterpret_cast<f32x4*>(smem + X3_OFF_TOT) + wave * (FD * QF * 64) + lane;     // multi-pass sums: [wave][FD][QF][lane]
+    // (the row plan in place, not att_row_plan: as a function it renumbers this kernel's scalar registers)
     int nactive = 0, nseen = 0;
     for (int pass = 0; pass < p.npass; ++pass) {
         const AttnEntry& e0 = p.e[pass * ATT_MAXB + b];
-        nactive += (e0.w_const != 0.f || e0.w_slope != 0.f) ? 1 : 0;
+        nactive += ATT_ENTRY_ACTIVE(e0) ? 1 : 0;
     }
     const int dup = att_duplicate_pass(p, b, head);      // a self-referencing row's second pass on a head the mask skips: folded into the first
     if (dup >= 0) nactive = 1;
-    // output row q of batch row b, columns head * D + d .. + 3: fp32, or (out_pair) the bf16 pair form hi | lo at ldo / 2
-    auto store_out = [&](int q, int d, const float* vv) {
-        if (p.out_pair) store_pair_row4(reinterpret_cast<bf16*>(p.out) + ((long)b * p.S + q) * p.ldo, head * D + d, p.ldo / 2, vv);
-        else store4(Og + ((long)b * p.S + q) * p.ldo + head * D + d, vv);
-    };
+    // output row q of batch row b, columns head * D + d .. + 3
+    auto store_out = [&](int q, int d, const float* vv) { att_store_out<true>(p, Og, b, head, D, q, d, vv); };
     if (nactive == 0) {
 #pragma unroll
         for (int f = 0; f < QF; ++f) {
@@ -83,13 +87,10 @@ __global__ __launch_bounds__(512) void attn_x3_kernel(const AttnParams p) {
 
     for (int pass = 0; pass < p.npass; ++pass) {
         const AttnEntry& en = p.e[pass * ATT_MAXB + b];
-        if (en.w_const == 0.f && en.w_slope == 0.f) continue;
-        if (pass == dup) continue;
-        float w = en.w_const;
-        if (p.w_dev) w += en.w_slope * (*p.w_dev);
-        if (dup >= 0) w += att_pass_weight(p, p.e[dup * ATT_MAXB + b]);
-        const int hb = en.hr_row > 0 ? en.hr_row - 1 : b;
-        const bool pass_masked = MASKS && en.kmask && (!(en.flags & ATT_HEAD_RULE) || (((hb * p.heads + head) & 1) == 0));
+        if (ATT_PASS_SKIPPED(en, pass, dup)) continue;
+        const float w = att_pass_total_weight(p, en, dup, b);
+        const int hb = ATT_HEAD_ROW(en, b);
+        const bool pass_masked = MASKS && ATT_ENTRY_MASKED(p, en, hb, head);
 
         // ---- Q^T fragments, split: lane = query l15 of fragment f, d elements 32 s + 8 g .. + 7
         u32x4 qh[QF][DSL], ql[QF][DSL];
@@ -108,15 +109,8 @@ __global__ __launch_bounds__(512) void attn_x3_kernel(const AttnParams p) {
                 if (qok && d + 4 < D) c = *reinterpret_cast<const f32x4*>(src + 4);
                 x3_split8(a, c, qh[f][s], ql[f][s]);
             }
-            wq[f] = (en.wq && qok) ? en.wq[q] : 1.f;
-            int md = 0;
-            if (pass_masked) {
-                const int sel = (en.qsel && qok) ? (en.qsel[q] != 0) : 1;
-                md = sel ? 1 : 2;
-                if (sel && (en.flags & ATT_UNIFORM_SEL1)) md = 3;
-                if (!sel && (en.flags & ATT_UNIFORM_SEL0)) md = 3;
-            }
-            mode[f] = md;
+            wq[f] = ATT_QUERY_WEIGHT(en, q, qok);
+            mode[f] = ATT_QUERY_MODE(en, pass_masked, q, qok);
         }
         f32x4 o[FD][QF];
         float mrun[QF], lrun[QF];

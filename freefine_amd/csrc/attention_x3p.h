@@ -33,12 +33,17 @@
 // tile, repeated by all 16 query-block workgroups of a (row, head) -- costs 16-25 % of the launch (timing ablation, profiles/r5_x3p_staging_ablation.txt).
 // Launches whose K / V^T can be split once per call (ffn_attn_presplit, 2-5 %) run attn_x3w_kernel on the pre-split images instead; this kernel
 // serves the rest (strided or oversized K / V^T).
+// attn_x3p_kernel's LDS: K slots 0, 1 | V^T slots 0, 1, 2 (a slot = the hi | lo bf16 images of a tile, 64 rows x 128 B each) | the multi-pass sums of its 8 waves (144 KB in all)
+constexpr int X3P_TILE = 64 * 128, X3P_SLOT = 2 * X3P_TILE;
+constexpr int X3P_OFF_V = 2 * X3P_SLOT, X3P_OFF_TOT = X3P_OFF_V + 3 * X3P_SLOT;
+constexpr int attn_x3p_lds_bytes() { return X3P_OFF_TOT + att_totl_bytes(8, 4, 2); }
+
 template <bool MASKS>
 __global__ __launch_bounds__(512) void attn_x3p_kernel(const AttnParams p) {
     constexpr int D = 64, KT = 64, QF = 2, NT = 4, FD = 4, DSL = 2, NC = 2;     // NC = 32-key chunks per tile (PV k-steps)
-    constexpr int TILE = KT * 128;                              // one bf16 image: 64 rows x 128 B
-    constexpr int SLOT = 2 * TILE;                              // hi | lo
-    constexpr int OFF_V = 2 * SLOT, OFF_TOT = OFF_V + 3 * SLOT; // K slots 0, 1 | V^T slots 0, 1, 2 | multi-pass sums (144 KB in all)
+    constexpr int TILE = X3P_TILE, SLOT = X3P_SLOT, OFF_V = X3P_OFF_V, OFF_TOT = X3P_OFF_TOT;
+    static_assert(TILE == KT * 128 && TILE == D * 128, "X3P_TILE is a 64-row bf16 image");
+    static_assert(OFF_TOT + att_totl_bytes(8, FD, QF) == attn_x3p_lds_bytes() && attn_x3p_lds_bytes() <= ATT_LDS_MAX, "attn_x3p_lds_bytes is this kernel's LDS layout");
     constexpr float FAST_THR = 6.0f;
     constexpr float NEG = -1e30f;
 
@@ -57,17 +62,10 @@ __global__ __launch_bounds__(512) void attn_x3p_kernel(const AttnParams p) {
     const float c_pre = p.scale * 1.44269504088896340736f;
 
     f32x4* totl = reinterpret_cast<f32x4*>(smem + OFF_TOT) + wave * (FD * QF * 64) + lane;     // multi-pass sums, wave private
-    int nactive = 0, nseen = 0;
-    for (int pass = 0; pass < p.npass; ++pass) {
-        const AttnEntry& e0 = p.e[pass * ATT_MAXB + b];
-        nactive += (e0.w_const != 0.f || e0.w_slope != 0.f) ? 1 : 0;
-    }
-    const int dup = att_duplicate_pass(p, b, head);      // a self-referencing row's second pass on a head the mask skips: folded into the first
-    if (dup >= 0) nactive = 1;
-    auto store_out = [&](int q, int d, const float* vv) {
-        if (p.out_pair) store_pair_row4(reinterpret_cast<bf16*>(p.out) + ((long)b * p.S + q) * p.ldo, head * D + d, p.ldo / 2, vv);
-        else store4(Og + ((long)b * p.S + q) * p.ldo + head * D + d, vv);
-    };
+    int dup;                                             // a self-referencing row's second pass on a head the mask skips: folded into the first
+    const int nactive = att_row_plan(p, b, head, dup);
+    int nseen = 0;
+    auto store_out = [&](int q, int d, const float* vv) { att_store_out<true>(p, Og, b, head, D, q, d, vv); };
     if (nactive == 0) {   // nothing contributes to this output row: zeros (workgroup-uniform: no barrier has been executed yet)
 #pragma unroll
         for (int f = 0; f < QF; ++f) {
@@ -97,13 +95,10 @@ __global__ __launch_bounds__(512) void attn_x3p_kernel(const AttnParams p) {
 
     for (int pass = 0; pass < p.npass; ++pass) {
         const AttnEntry& en = p.e[pass * ATT_MAXB + b];
-        if (en.w_const == 0.f && en.w_slope == 0.f) continue;   // workgroup-uniform skip
-        if (pass == dup) continue;
-        float w = en.w_const;
-        if (p.w_dev) w += en.w_slope * (*p.w_dev);
-        if (dup >= 0) w += att_pass_weight(p, p.e[dup * ATT_MAXB + b]);
-        const int hb = en.hr_row > 0 ? en.hr_row - 1 : b;
-        const bool pass_masked = MASKS && en.kmask && (!(en.flags & ATT_HEAD_RULE) || (((hb * p.heads + head) & 1) == 0));
+        if (ATT_PASS_SKIPPED(en, pass, dup)) continue;          // workgroup-uniform skip
+        const float w = att_pass_total_weight(p, en, dup, b);
+        const int hb = ATT_HEAD_ROW(en, b);
+        const bool pass_masked = MASKS && ATT_ENTRY_MASKED(p, en, hb, head);
 
         // ---- Q^T fragments: pre-scaled in fp32, then split ------------------------------------------------------------------
         u32x4 qh[QF][DSL], ql[QF][DSL], qaug[QF];
@@ -122,12 +117,9 @@ __global__ __launch_bounds__(512) void attn_x3p_kernel(const AttnParams p) {
                 }
                 x3_split8(a * c_pre, c * c_pre, qh[f][s], ql[f][s]);
             }
-            wq[f] = (en.wq && qok) ? en.wq[q] : 1.f;
+            wq[f] = ATT_QUERY_WEIGHT(en, q, qok);
             qaug[f] = u32x4{0, 0, 0, 0};
-            if (MASKS && pass_masked && g == 0) {
-                const int sel = (en.qsel && qok) ? (en.qsel[q] != 0) : 1;
-                qaug[f][0] = sel ? 0x3f80u : 0x3f800000u;       // [wants mask != 0 | wants mask == 0]
-            }
+            if (MASKS && pass_masked && g == 0) qaug[f][0] = att_sel_word(ATT_QUERY_SEL(en, q, qok));
         }
 
         f32x4 o[FD][QF], lacc[QF], st[NT][QF];

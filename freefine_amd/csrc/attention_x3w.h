@@ -34,9 +34,14 @@
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((address_space(3))) uint8_t x3w_lds_u8_t;
 
-// K ring slots (32-key blocks), also the kernel's LDS size (fx3w_lds_bytes, attn_x3w.hip).  Ring of 4, a block requested one iteration ahead of its first
+// K ring slots (32-key blocks).  Ring of 4, a block requested one iteration ahead of its first
 // read: 1368 vs 1401 us for a ring of 6 requested two ahead, profiles/r6_x3w_ring_depth_and_dma_placement_ab.txt
 constexpr int X3W_NKB = 4;
+// attn_x3w_kernel's LDS: K ring of X3W_NKB block slots (32 rows x 128 B, hi image | lo image) | V^T ring of 2 tile slots (64 rows x 128 B, hi | lo) |
+// key-mask bytes 4 x 256 | the multi-pass sums of its 4 waves ([16 f32x4][64 lanes] each: 64 KB)
+constexpr int X3W_KBLK = 2 * 4096, X3W_VIMG = 64 * 128, X3W_VSLOT = 2 * X3W_VIMG;
+constexpr int X3W_OFF_V = X3W_NKB * X3W_KBLK, X3W_OFF_M = X3W_OFF_V + 2 * X3W_VSLOT, X3W_OFF_TOT = X3W_OFF_M + 4 * 256;
+constexpr int attn_x3w_lds_bytes() { return X3W_OFF_TOT + 4 * 16 * 64 * 16; }
 #ifndef X3W_ABL
 #define X3W_ABL 0     // timing-only ablations (tools/native/x3w_bench.hip): 1 no softmax / split VALU, 2 no LDS-DMA in the loop, 3 no MFMA
 #endif
@@ -67,10 +72,10 @@ __device__ __forceinline__ float x3w_sum_halves(float x) {
 template <bool MASKS>
 __global__ __launch_bounds__(256) void attn_x3w_kernel(const AttnParams p) {
     constexpr int D = 64, KT = 64;
-    constexpr int KBLK = 2 * 4096;                              // one K block slot: 32 rows x 128 B, hi image | lo image
-    constexpr int VIMG = 64 * 128, VSLOT = 2 * VIMG;            // one V^T tile slot: 64 rows (d) x 128 B (64 keys), hi image | lo image
+    constexpr int KBLK = X3W_KBLK;                              // one K block slot: 32 rows x 128 B, hi image | lo image
+    constexpr int VIMG = X3W_VIMG, VSLOT = X3W_VSLOT;           // one V^T tile slot: 64 rows (d) x 128 B (64 keys), hi image | lo image
     constexpr int NKB = X3W_NKB, AHEAD = 1;                     // K ring: NKB block slots; a block is requested AHEAD iterations (= 2 AHEAD blocks) ahead of the iteration that reads it
-    constexpr int OFF_V = NKB * KBLK, OFF_M = OFF_V + 2 * VSLOT, OFF_TOT = OFF_M + 1024;   // K ring | V^T ring of 2 tiles | key-mask bytes 4 x 256 | multi-pass sums 64 KB
+    constexpr int OFF_V = X3W_OFF_V, OFF_M = X3W_OFF_M, OFF_TOT = X3W_OFF_TOT;
     constexpr int OOB = (int)0x80000000;
     constexpr float FAST_THR = 6.0f;
     constexpr float NEG = -1e30f;
@@ -89,17 +94,11 @@ __global__ __launch_bounds__(256) void attn_x3w_kernel(const AttnParams p) {
     const float c_pre = p.scale * 1.44269504088896340736f;
 
     f32x4* totl = reinterpret_cast<f32x4*>(smem + OFF_TOT) + wave * (16 * 64) + lane;       // multi-pass sums, wave private: [16 f32x4][64 lanes]
-    int nactive = 0, nseen = 0;
-    for (int pass = 0; pass < p.npass; ++pass) {
-        const AttnEntry& e0 = p.e[pass * ATT_MAXB + b];
-        nactive += (e0.w_const != 0.f || e0.w_slope != 0.f) ? 1 : 0;
-    }
-    const int dup = att_duplicate_pass(p, b, head);
-    if (dup >= 0) nactive = 1;
-    auto store_out = [&](int q, int d, const float* vv) {
-        if (p.out_pair) store_pair_row4(reinterpret_cast<bf16*>(p.out) + ((long)b * p.S + q) * p.ldo, head * D + d, p.ldo / 2, vv);
-        else store4(Og + ((long)b * p.S + q) * p.ldo + head * D + d, vv);
-    };
+    static_assert(OFF_TOT + 4 * (16 * 64) * (int)sizeof(f32x4) == attn_x3w_lds_bytes() && attn_x3w_lds_bytes() <= ATT_LDS_MAX, "attn_x3w_lds_bytes is this kernel's LDS layout");
+    int dup;                                             // a self-referencing row's second pass on a head the mask skips: folded into the first
+    const int nactive = att_row_plan(p, b, head, dup);
+    int nseen = 0;
+    auto store_out = [&](int q, int d, const float* vv) { att_store_out<true>(p, Og, b, head, D, q, d, vv); };
     if (nactive == 0) {   // nothing contributes to this output row: zeros (workgroup-uniform, before any barrier)
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
@@ -129,13 +128,10 @@ __global__ __launch_bounds__(256) void attn_x3w_kernel(const AttnParams p) {
 
     for (int pass = 0; pass < p.npass; ++pass) {
         const AttnEntry& en = p.e[pass * ATT_MAXB + b];
-        if (en.w_const == 0.f && en.w_slope == 0.f) continue;   // workgroup-uniform skip
-        if (pass == dup) continue;
-        float w = en.w_const;
-        if (p.w_dev) w += en.w_slope * (*p.w_dev);
-        if (dup >= 0) w += att_pass_weight(p, p.e[dup * ATT_MAXB + b]);
-        const int hb = en.hr_row > 0 ? en.hr_row - 1 : b;
-        const bool pass_masked = MASKS && en.kmask && (!(en.flags & ATT_HEAD_RULE) || (((hb * p.heads + head) & 1) == 0));
+        if (ATT_PASS_SKIPPED(en, pass, dup)) continue;          // workgroup-uniform skip
+        const float w = att_pass_total_weight(p, en, dup, b);
+        const int hb = ATT_HEAD_ROW(en, b);
+        const bool pass_masked = MASKS && ATT_ENTRY_MASKED(p, en, hb, head);
 
         // ---- Q^T fragments (B operand: query r, d elements 16 s + 8 h .. + 7): pre-scaled in fp32, then split --------------------
         u32x4 qh[2][4], ql[2][4];
@@ -159,12 +155,9 @@ __global__ __launch_bounds__(256) void attn_x3w_kernel(const AttnParams p) {
                 asm volatile("" : "+a"(qh[qb][s]));
                 asm volatile("" : "+a"(ql[qb][s]));
             }
-            wq[qb] = (en.wq && qok) ? en.wq[q] : 1.f;
+            wq[qb] = ATT_QUERY_WEIGHT(en, q, qok);
             qaug[qb] = u32x4{0, 0, 0, 0};
-            if (MASKS && pass_masked) {
-                const int sel = (en.qsel && qok) ? (en.qsel[q] != 0) : 1;
-                qaug[qb][0] = sel ? 0x3f80u : 0x3f800000u;      // k index 0: wants mask != 0 (penalise mask == 0) | k index 1: wants mask == 0
-            }
+            if (MASKS && pass_masked) qaug[qb][0] = att_sel_word(ATT_QUERY_SEL(en, q, qok));      // k index 0: wants mask != 0 (penalise mask == 0) | k index 1: wants mask == 0
         }
         const bool maskon = MASKS && pass_masked && h == 0;
 

@@ -13,11 +13,14 @@
 #include "attention_x.h"
 #include "attention_x3.h"
 
+// xattn_nfr fragments per pass (attention_x.h) x 2 images (hi, lo) of 1 KiB; the host plan admits a launch only if the images of all its passes fit the LDS
+constexpr int xattn_x3_lds_bytes(int nkf, int npass) { return npass * 2 * xattn_nfr(nkf) * 1024; }
+
 template <int NKF, int NW>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xattn_x3_kernel(const AttnParams p, int wgs_per_pair, int blocks_per_wave) {
     constexpr int NKS = (NKF + 1) / 2;
     constexpr int QF = 2;
-    constexpr int NFR = NKF * 2 + 4 * NKS;            // fragments per pass (K: NKF x 2 d-steps, V^T: 4 d-fragments x NKS key steps); x 2 images (hi, lo)
+    constexpr int NFR = xattn_nfr(NKF);
     constexpr int OOB = (int)0x80000000;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -34,7 +37,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xattn_x3_kernel(cons
     // ---- fragment images of every active pass -> LDS: fragment i of pass ps, hi image at (ps * 2 NFR + i) KiB, lo image NFR KiB behind it ----
     for (int ps = 0; ps < p.npass; ++ps) {
         const AttnEntry& e = p.e[ps * ATT_MAXB + b];
-        if (e.w_const == 0.f && e.w_slope == 0.f) continue;
+        if (ATT_ENTRY_SKIPPED(e)) continue;
         for (int i = wave; i < NFR; i += NW) {
             f32x4 a, c;
             if (i < 2 * NKF) {                        // K fragment (key fragment f, d-step ks): lane = key 16 f + l15, d = 32 ks + 8 g .. + 7
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void xattn_x3_kernel(cons
     auto active_from = [&](int ps) {
         for (; ps < p.npass; ++ps) {
             const AttnEntry& e = p.e[ps * ATT_MAXB + b];
-            if (e.w_const != 0.f || e.w_slope != 0.f) break;
+            if (ATT_ENTRY_ACTIVE(e)) break;
         }
         return ps;
     };

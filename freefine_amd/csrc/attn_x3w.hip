@@ -12,6 +12,6 @@
 #include "attention_x3w.h"
 #include "attn_units.h"
 
-int fx3w_lds_bytes(void) { return X3W_NKB * 8192 + 2 * 16384 + 1024 + 65536; }
+int fx3w_lds_bytes(void) { return attn_x3w_lds_bytes(); }
 
 attn_kernel_t fx3w_kernel(int masks) { return masks ? attn_x3w_kernel<true> : attn_x3w_kernel<false>; }

@@ -30,11 +30,6 @@ extern "C" int ffn_attn_variant(int dtype, int D, int* dp, int* qf) {
     *qf = t.qf;
     return FFN_OK;
 }
-// double-buffered K and V^T tiles + the per-wave multi-pass accumulator + the key-mask bytes of the two staged tiles
-static constexpr int attn_kernel_lds(int esz, int dp, int qf, int kt) {
-    return 2 * (kt * (dp * esz == 128 ? 128 : dp * esz + 16) + dp * ((dp * esz == 128 && kt * esz == 128) ? 128 : kt * esz + 16)) + 4 * (dp / 16) * qf * 64 * 16 + 2 * kt;
-}
-static_assert(attn_kernel_lds(4, 160, 1, 32) <= 160 * 1024 && attn_kernel_lds(2, 160, 1, 64) <= 160 * 1024, "attention tile does not fit the 160 KiB LDS");
 
 enum AttnKind { ATT_KERNEL, ATT_PP, ATT_X, ATT_X_MP, ATT_X3, ATT_X3P, ATT_X3W, ATT_XX3, ATT_CAUSAL_K };
 struct AttnPlan {
@@ -58,6 +53,8 @@ struct AttnPlan {
 //   Any dtype, an active entry carrying FFN_ATT_CAUSAL: attn_causal_kernel (attention_causal.h) under the flag's preconditions, FFN_EINVAL outside them; a
 //     descriptor without the flag never reaches that branch.
 // FFN_EINVAL: kv_pair for a launch that does not run attn_x3w_kernel; FFN_ENOSYS: head dim beyond 160.
+// The dynamic LDS of a launch is its kernel's own size function, stated beside the kernel from the constants it uses (attn_kernel_lds, attn_pp_lds_bytes,
+// attn_x3_lds_bytes, attn_x3p_lds_bytes, xattn_mp_lds_bytes, xattn_x3_lds_bytes; attn_x3w_lds_bytes through fx3w_lds_bytes) and checked there against the layout.
 static int attn_plan(int dtype, const ffn_attn_desc& d, AttnPlan* p) {
     bool masks = false, uniform = false, xok = true, multi = d.npass != 1;
     bool causal = false, causal_ok = true;
@@ -65,7 +62,7 @@ static int attn_plan(int dtype, const ffn_attn_desc& d, AttnPlan* p) {
     for (int pi = 0; pi < d.npass; ++pi)
         for (int b = 0; b < d.Bo; ++b) {
             const ffn_attn_entry& e = d.e[pi * FFN_ATT_MAXB + b];
-            if (e.w_const == 0.f && e.w_slope == 0.f) { multi = true; continue; }
+            if (ATT_ENTRY_SKIPPED(e)) { multi = true; continue; }
             causal |= (e.flags & FFN_ATT_CAUSAL) != 0;
             causal_ok &= (e.flags & FFN_ATT_CAUSAL) && !e.kmask && !e.qsel && !e.wq && e.w_slope == 0.f;
             masks |= e.kmask != nullptr;
@@ -100,13 +97,12 @@ static int attn_plan(int dtype, const ffn_attn_desc& d, AttnPlan* p) {
     p->block = dim3(512);
     if (dtype == FFN_BF16X3 && d.D <= 64) {
         p->nkf = xattn_nkf(4);
-        const int nfr = p->nkf * 2 + 4 * ((p->nkf + 1) / 2);   // 1 KiB fragment images per pass: hi and lo each
-        if (p->nkf && d.npass * 2 * nfr * 1024 <= 160 * 1024) {
+        if (p->nkf && xattn_x3_lds_bytes(p->nkf, d.npass) <= ATT_LDS_MAX) {
             // 8 waves per workgroup where the fragment images are large against a workgroup's share of the queries (two passes: 88 KiB, one workgroup
             // per CU either way) or the launch is long; 4 (two workgroups per CU) for the short single-pass launches (profiles/r5_xattn_x3_waves_and_stores.txt)
             p->kind = ATT_XX3;
             p->nw = (d.npass >= 2 || d.S >= 4096) ? 8 : 4;
-            p->lds = d.npass * 2 * nfr * 1024;
+            p->lds = xattn_x3_lds_bytes(p->nkf, d.npass);
             p->block = dim3(64 * p->nw);
         } else if (pp && d.kv_pair) {                           // one wave per SIMD on 32x32x16 MFMAs
             p->kind = ATT_X3W;
@@ -114,21 +110,21 @@ static int attn_plan(int dtype, const ffn_attn_desc& d, AttnPlan* p) {
             p->block = dim3(256);
         } else if (pp) {
             p->kind = ATT_X3P;
-            p->lds = 5 * (2 * 8192) + 8 * 4 * 2 * 64 * 16;      // K ring of 2 + V^T ring of 3 [hi | lo] images, multi-pass sums
+            p->lds = attn_x3p_lds_bytes();
         } else {
             p->kind = ATT_X3;
-            p->lds = 2 * (4 * 8192) + 8 * 4 * 2 * 64 * 16;
+            p->lds = attn_x3_lds_bytes();
         }
     } else if (dtype == FFN_BF16 && (p->nkf = xattn_nkf(2))) {
         // one pass of plain active entries: K / V^T of a (row, head) in a wave's registers; several passes, skipped entries or per-query
         // weights: one workgroup of 4 waves per (row, head, chunk) with the fragment images of every pass in LDS
         p->kind = multi ? ATT_X_MP : ATT_X;
         p->nw = multi ? 4 : 1;
-        p->lds = multi ? d.npass * (p->nkf * 2 + 4 * ((p->nkf + 1) / 2)) * 1024 : 0;
+        p->lds = multi ? xattn_mp_lds_bytes(p->nkf, d.npass) : 0;
         p->block = dim3(256);
     } else if (dtype == FFN_BF16 && pp) {
         p->kind = ATT_PP;
-        p->lds = 4 * 8192 + 4 * 8192 + 4 * 256 + 8 * 4 * 2 * 64 * 16;
+        p->lds = attn_pp_lds_bytes();
     } else {
         p->kind = ATT_KERNEL;
         p->f32 = dtype != FFN_BF16;

@@ -515,6 +515,59 @@ def test_image_batched_rows_across_row_splits(gpu, monkeypatch, mode):
     assert torch.equal(outs[5], outs[None]) and torch.equal(outs[7], outs[None])
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# F. the pass table itself, through each of the five multi-pass kernels at the smallest shape it takes
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# (mode, S, Sk, out_pair): S = 40 / Sk = 72 leaves attn_kernel and attn_x3_kernel a ragged query block and a ragged last key tile; S = 128 / Sk = 64 is
+# the smallest launch of the ping-pong kernels (one query block, one key tile)
+TABLE_PARAMS = ([("f32", 40, 72, False), ("bf16", 40, 72, False), ("x3", 40, 72, False), ("x3", 40, 72, True), ("bf16", 128, 64, False)] +
+                [(m, 128, 64, pair) for m in ("x3", "x3-inkernel") for pair in (False, True)])
+
+
+def _table_kernels(mode, Sk):
+    if Sk % 64:
+        return {"f32": {F32_K}, "bf16": {bf16_k(True)}, "x3": {tk("attn_x3_kernel", True)}}[mode]
+    return {"bf16": {tk("attn_pp_kernel", True)}, "x3": {PRESPLIT, tk("attn_x3w_kernel", True)}, "x3-inkernel": {tk("attn_x3p_kernel", True)}}[mode]
+
+
+@pytest.mark.parametrize("mode,S,Sk,out_pair", TABLE_PARAMS)
+def test_pass_table_at_smallest_shapes(gpu, monkeypatch, mode, S, Sk, out_pair):
+    """one two-pass table of three output rows that takes a kernel through every branch of the pass-table helpers (attention.h), against ref_passes:
+    row 0: a masked entry whose tiled-head rule is pinned to row 1 (hr_row: not the output row), blended through w_dev with its own plain attention;
+    row 1: a self-referencing row (both passes q = kv = 1): on the heads the rule leaves unmasked its second pass is folded into the first;
+    row 2: no active entry (skipped in pass 1, zero weight in pass 2): exact zeros, also in the pair form of the split-bf16 kernels.
+    Three heads, not two: with an even head count the parity of row * heads + head does not depend on the row, and the pin could not be told from
+    the output row (the reference evaluated on the output rows instead must miss the gate)."""
+    from freefine_amd import ops
+    from test_ops_gpu import pair_value
+    g = torch.Generator().manual_seed(S + Sk)
+    heads, D, B = 3, 64, 3
+    C = heads * D
+    dt = torch.bfloat16 if mode == "bf16" else torch.float32
+    q, k, v = (torch.randn(B, n, C, generator=g).to(gpu, dt) for n in (S, Sk, Sk))
+    vt = ops.transpose(v, ld_dst=(Sk + 7) // 8 * 8)
+    km = (torch.rand(Sk, generator=g) > 0.5).to(torch.uint8).to(gpu)
+    qs = (torch.rand(S, generator=g) > 0.5).to(torch.uint8).to(gpu)
+    p0 = [ops.AttnEntrySpec(0, 1, 0.0, 1.0, kmask=km, qsel=qs, flags=HEAD_RULE, hr_row=1),
+          ops.AttnEntrySpec(1, 1, 0.0, 1.0, kmask=km, qsel=qs, flags=HEAD_RULE), None]
+    p1 = [ops.AttnEntrySpec(0, 0, 1.0, -1.0), ops.AttnEntrySpec(1, 1, 1.0, -1.0), ops.AttnEntrySpec(2, 2, 0.0, 0.0)]
+    passes = [p0, p1]
+    cg = torch.tensor([0.35], dtype=torch.float32, device=gpu)
+    if mode == "x3-inkernel":
+        monkeypatch.setattr(ops, "_ATTN_PRESPLIT", False)
+    out, names = run(q, k, vt, heads, D ** -0.5, passes, Sk=Sk, w_dev=cg, x3=mode.startswith("x3"), out_pair=out_pair)
+    assert names == _table_kernels(mode, Sk), names
+    if out_pair:
+        assert out.dtype == torch.bfloat16 and out.shape == (B, S, 2 * C)
+        out = pair_value(out, C)
+    kind = operand_kind(names)
+    ref = ref_passes(q, k, v, heads, D ** -0.5, passes, cg, kind)
+    wrong = ref_passes(q, k, v, heads, D ** -0.5, passes, cg, kind, head_rows=[0, 1, 2])
+    assert relerr(wrong[0], ref[0]) > 20 * TOL[kind]
+    e = check(out, ref, TOL[kind], (mode, S, Sk, out_pair))
+    print(f"pass table {mode} S={S} Sk={Sk} pair={out_pair} ({kind}): {e:.2e}")
+
+
 def test_every_kernel_kind_is_expected():
     """the cases of this module expect, together, every kernel kind of the plan (from the tables the tests assert against)"""
     names = set()

@@ -43,12 +43,12 @@ int main(int argc, char** argv) {
             }
         }
         if (which == 0) {
-            const int lds = 2 * (64 * 128 + 64 * 128) + 4 * 4 * 2 * 64 * 16 + 2 * 64;
+            const int lds = attn_kernel_lds(2, 64, 2, 64);
             dim3 grid(((S + 127) / 128) * heads * nb);
             if (masks) { CK(hipFuncSetAttribute((const void*)attn_kernel<bf16, 64, 2, 64, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); hipLaunchKernelGGL((attn_kernel<bf16, 64, 2, 64, 2, true>), grid, dim3(256), lds, 0, d); }
             else { CK(hipFuncSetAttribute((const void*)attn_kernel<bf16, 64, 2, 64, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); hipLaunchKernelGGL((attn_kernel<bf16, 64, 2, 64, 2, false>), grid, dim3(256), lds, 0, d); }
         } else {
-            const int lds = 4 * 8192 + 4 * 8192 + 4 * 256 + 8 * 4 * 2 * 64 * 16;
+            const int lds = attn_pp_lds_bytes();
             dim3 grid(((S + 255) / 256) * heads * nb);
             if (masks) { CK(hipFuncSetAttribute((const void*)attn_pp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); hipLaunchKernelGGL(attn_pp_kernel<true>, grid, dim3(512), lds, 0, d); }
             else { CK(hipFuncSetAttribute((const void*)attn_pp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); hipLaunchKernelGGL(attn_pp_kernel<false>, grid, dim3(512), lds, 0, d); }

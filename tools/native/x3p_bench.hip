@@ -36,7 +36,7 @@ int main(int argc, char** argv) {
                 ffn_attn_entry& f = d.e[FFN_ATT_MAXB + b]; f.q_row = b0 + b; f.kv_row = b0 + b; f.w_const = 1.f; f.w_slope = -1.f;
             }
         }
-        constexpr int lds = 5 * (2 * 8192) + 8 * 4 * 2 * 64 * 16;
+        constexpr int lds = attn_x3p_lds_bytes();
         dim3 grid(((S + 255) / 256) * heads * nb);
         if (masks) { CK(hipFuncSetAttribute((const void*)attn_x3p_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); hipLaunchKernelGGL(attn_x3p_kernel<true>, grid, dim3(512), lds, 0, d); }
         else { CK(hipFuncSetAttribute((const void*)attn_x3p_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); hipLaunchKernelGGL(attn_x3p_kernel<false>, grid, dim3(512), lds, 0, d); }

@@ -128,8 +128,8 @@ static ffn_attn_desc desc_for(const Problem& P, int b0, int nb, bool pair, int v
     }
     return d;
 }
-constexpr int LDS_P = 5 * (2 * 8192) + 8 * 4 * 2 * 64 * 16;
-constexpr int LDS_W = 6 * 8192 + 2 * 16384 + 1024 + 65536;
+constexpr int LDS_P = attn_x3p_lds_bytes();
+constexpr int LDS_W = attn_x3w_lds_bytes();
 static void run_p(const Problem& P, int variant, float* out) {
     for (int b0 = 0; b0 < P.B; b0 += 16) {
         const int nb = std::min(16, P.B - b0);
